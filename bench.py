@@ -83,6 +83,44 @@ def hbm_traffic(kname, clips, seconds):
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(batch, out_dir):
+    """Writes what the timed path hands its caller after the last step - one finished .flo file per clip, as
+    Batch.fetch returns it - so that two builds can be compared output for output:
+      file_bytes.npy    float64 [n_clips]  length of every clip's file
+      file_crc32.npy    float64 [n_clips]  zlib CRC32 of every clip's file
+      sample_clips.npy  float64 [k]        a seeded sample of clip indices (the same for the same arguments)
+      sample_files.npy  float32 [sum]      those clips' files, concatenated in sample order, one byte (0..255) per float
+    The sample takes whole files while the four arrays stay within DUMP_LIMIT_BYTES; a single file larger than that is
+    cut to its head."""
+    import zlib
+    import numpy as np
+    n = batch.n_clips
+    sizes, crcs = np.zeros(n, np.float64), np.zeros(n, np.float64)
+    for i in range(n):
+        f = batch.fetch(i)
+        sizes[i], crcs[i] = len(f), zlib.crc32(f)
+    room = (DUMP_LIMIT_BYTES - 4096 - 24 * n) // 4      # floats left beside the per-clip arrays and four .npy headers
+    picked, parts = [], []
+    for i in np.random.default_rng(DUMP_SAMPLE_SEED).permutation(n):
+        take = min(int(sizes[i]), room)
+        if take <= 0 or (take < sizes[i] and picked):
+            break
+        picked.append(int(i))
+        parts.append(np.frombuffer(batch.fetch(int(i))[:take], np.uint8).astype(np.float32))
+        room -= take
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "file_bytes.npy"), sizes)
+    np.save(os.path.join(out_dir, "file_crc32.npy"), crcs)
+    np.save(os.path.join(out_dir, "sample_clips.npy"), np.array(picked, np.float64))
+    np.save(os.path.join(out_dir, "sample_files.npy"), np.concatenate(parts) if parts else np.zeros(0, np.float32))
+    print(f"[bench] outputs of the last timed step in {out_dir}: {n} files (lengths + CRC32), {len(picked)} of them "
+          f"sampled", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -100,7 +138,11 @@ def main():
     ap.add_argument("--no-shard", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--cpu-clips", type=int, default=200)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write rank 0's files of the last step under DIR as .npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -268,6 +310,8 @@ def main():
     dt = time.perf_counter() - t0
     ctx.profile_enable(False)
     dt = all_max(dt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, args.dump_outputs)
 
     # the dominant kernel is whichever chain form ran (auto picks the three-wave pipeline for stereo batches)
     kname, k_ms, k_n = "lossy_frames", 0.0, 0

@@ -2,7 +2,8 @@
 (an error, or PCM), the device decoder must make the same (lossless: same integers; lossy: within 2e-6)."""
 import sys
 import os
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, flo_amd, flofile, signals
 from oracle import oracle as O
 ctx = flo_amd.Context(0)

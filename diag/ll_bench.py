@@ -1,5 +1,5 @@
-import time, sys
-sys.path.insert(0, "/root/repo")
+import os, time, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, flo_amd
 ctx = flo_amd.Context(0)
 for (sr, secs, n) in ((96000, 10, 64), (44100, 10, 256), (44100, 10, 1250)):

@@ -1,6 +1,7 @@
 """Randomised differential test of the lossless encoder: device bytes vs oracle bytes on random clips."""
-import sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, flo_amd
 from oracle import oracle as O
 ctx = flo_amd.Context(0)

@@ -1,6 +1,6 @@
 # lossless decode: parallel form against the serial kernel (same bytes out), per-kernel times
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, flo_amd
 ctx = flo_amd.Context(0)
 sr, ch = 44100, 2

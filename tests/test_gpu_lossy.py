@@ -432,8 +432,12 @@ def test_pack_streams_and_single_rank_rccl_gather(ctx):
         whole = b.fetch(i)
         assert fhost[foffs[i]:foffs[i] + len(whole)].tobytes() == whole and foffs[i] % 16 == 0
         assert flofile.parse(whole).crc_valid
+    import socket
+    with socket.socket() as s:     # a port nobody holds: the host may be running other groups
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", "29533")
+    os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
     try:
         got, sizes = gather_payloads(dist, buf[: offs[-1]], 0, 1, 0)
