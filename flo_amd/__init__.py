@@ -6,3 +6,4 @@ this package is only the host-side mirror of the reference's encoder interface.
 from ._native import FloError, MODE_LOSSLESS, MODE_LOSSY  # noqa: F401
 from .api import (Batch, Context, Decoder, EncodedFrame, Encoder, LossyEncoder, QualityPreset, StreamingEncoder,  # noqa: F401
                   TransformEncoder, default_context, decode, encode, encode_lossy, encode_with_bitrate, probe_container)
+from .api import Corpus, SeekResult, TocEntry, decode_frame_at, get_toc, seek_to_time  # noqa: F401

@@ -30,6 +30,9 @@ EXPORTS = [
     "flo_stream_create", "flo_stream_destroy", "flo_stream_push", "flo_stream_pending_samples", "flo_stream_pending_frames",
     "flo_stream_next_frame", "flo_stream_flush", "flo_stream_finalize",
     "flo_analyze", "flo_analysis_metadata", "flo_batch_analysis_metadata", "flo_batch_set_bit_depth",
+    "flo_get_toc", "flo_seek_to_time", "flo_decode_frame_at",
+    "flo_corpus_create", "flo_corpus_destroy", "flo_corpus_format", "flo_corpus_file_frames", "flo_corpus_decode_windows",
+    "flo_corpus_sync",
 ]
 
 
@@ -47,6 +50,16 @@ class ContainerInfo(C.Structure):
                 ("flags", C.c_uint16), ("pad2", C.c_uint16), ("sample_rate", C.c_uint32), ("data_crc32", C.c_uint32),
                 ("n_frames", C.c_uint32), ("total_samples", C.c_uint64), ("data_start", C.c_uint64), ("data_size", C.c_uint64),
                 ("frame_samples_sum", C.c_uint64)]
+
+
+class TocEntryC(C.Structure):
+    _fields_ = [("frame_index", C.c_uint32), ("frame_size", C.c_uint32), ("byte_offset", C.c_uint64), ("timestamp_ms", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class SeekResultC(C.Structure):
+    _fields_ = [("frame_index", C.c_uint32), ("timestamp_ms", C.c_uint32), ("byte_offset", C.c_uint64), ("sample_offset", C.c_uint32),
+                ("next_timestamp_ms", C.c_uint32)]
 
 
 class FloError(RuntimeError):
@@ -148,5 +161,15 @@ def lib():
     L.flo_decode.argtypes = [vp, C.c_char_p, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
     L.flo_decode_lossless_i32.argtypes = L.flo_decode.argtypes
     L.flo_probe_container.argtypes = [C.c_char_p, sz, C.POINTER(ContainerInfo), C.c_char_p, sz]
+    L.flo_get_toc.argtypes = [C.c_char_p, sz, C.POINTER(C.POINTER(TocEntryC)), C.POINTER(sz), C.c_char_p, sz]
+    L.flo_seek_to_time.argtypes = [C.c_char_p, sz, C.c_uint32, C.POINTER(SeekResultC), C.c_char_p, sz]
+    L.flo_decode_frame_at.argtypes = [vp, C.c_char_p, sz, C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
+    L.flo_corpus_create.argtypes = [vp, sz, C.POINTER(C.c_char_p), C.POINTER(sz), C.POINTER(vp)]
+    L.flo_corpus_destroy.argtypes = [vp]
+    L.flo_corpus_destroy.restype = None
+    L.flo_corpus_format.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
+    L.flo_corpus_file_frames.argtypes = [vp, sz, C.POINTER(C.c_uint64)]
+    L.flo_corpus_decode_windows.argtypes = [vp, sz, vp, vp, C.c_uint32, vp, sz, vp]
+    L.flo_corpus_sync.argtypes = [vp]
     _LIB = L
     return L

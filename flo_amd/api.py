@@ -13,6 +13,7 @@ Errors surface as FloError(message), the analogue of FloResult<T> = Result<T, St
 import ctypes as C
 import enum
 import weakref
+from typing import NamedTuple
 
 import numpy as np
 
@@ -90,6 +91,7 @@ class Context:
         if rc != 0:
             raise FloError(self._L.flo_last_create_error().decode())
         self._h = h
+        self.device = device
         self._batches = weakref.WeakSet()   # batches hold device memory of this context: they go first
 
     def close(self):
@@ -191,6 +193,21 @@ class Context:
             self._L.flo_free(out)
             a = np.zeros(0, dtype)
         return (a, sr.value, ch.value) if with_info else a
+
+    def decode_frame_at(self, flo: bytes, frame_index: int):
+        """seeking::decode_frame_at (seeking.rs:43-63): the interleaved f32 samples of one frame, decoded on the device"""
+        flo = bytes(flo)
+        out, n = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.flo_decode_frame_at(self._h, flo, len(flo), int(frame_index), C.byref(out), C.byref(n)))
+        a = np.ctypeslib.as_array((C.c_float * n.value).from_address(out.value)).copy() if n.value else np.zeros(0, np.float32)
+        self._L.flo_free(out)
+        return a
+
+    def get_toc(self, flo: bytes):
+        return get_toc(flo)
+
+    def seek_to_time(self, flo: bytes, target_ms: int):
+        return seek_to_time(flo, target_ms)
 
     # -- analysis metadata of libflo::encode* (lib.rs:219-283) ---------------------------------------------------
     def analyze(self, samples, sample_rate, channels, peaks_per_second=50):
@@ -579,6 +596,118 @@ def probe_container(data: bytes):
 def decode(data: bytes):
     """libflo::decode (lib.rs:296-315)"""
     return default_context().decode(data)
+
+
+# -- seeking (libflo/src/seeking.rs) -------------------------------------------------------------------------------
+class TocEntry(NamedTuple):
+    """core/types.rs:174-179"""
+    frame_index: int
+    byte_offset: int
+    frame_size: int
+    timestamp_ms: int
+
+
+class SeekResult(NamedTuple):
+    """seeking.rs:7-19"""
+    frame_index: int
+    byte_offset: int
+    timestamp_ms: int
+    sample_offset: int
+    next_timestamp_ms: int
+
+
+def get_toc(data: bytes):
+    """seeking::get_toc (seeking.rs:28-32): the TOC as the reader returns it; no device needed"""
+    L = _native.lib()
+    data = bytes(data)
+    p, n = C.POINTER(_native.TocEntryC)(), C.c_size_t()
+    err = C.create_string_buffer(256)
+    if L.flo_get_toc(data, len(data), C.byref(p), C.byref(n), err, len(err)) != 0:
+        raise FloError(err.value.decode() or "not a .flo file")
+    res = [TocEntry(p[i].frame_index, p[i].byte_offset, p[i].frame_size, p[i].timestamp_ms) for i in range(n.value)]
+    L.flo_free(C.cast(p, C.c_void_p))
+    return res
+
+
+def seek_to_time(data: bytes, target_ms: int):
+    """seeking::seek_to_time (seeking.rs:75-132); no device needed"""
+    L = _native.lib()
+    data = bytes(data)
+    r = _native.SeekResultC()
+    err = C.create_string_buffer(256)
+    if L.flo_seek_to_time(data, len(data), int(target_ms), C.byref(r), err, len(err)) != 0:
+        raise FloError(err.value.decode() or "not a .flo file")
+    return SeekResult(r.frame_index, r.byte_offset, r.timestamp_ms, r.sample_offset, r.next_timestamp_ms)
+
+
+def decode_frame_at(data: bytes, frame_index: int):
+    """seeking::decode_frame_at (seeking.rs:43-63)"""
+    return default_context().decode_frame_at(data, frame_index)
+
+
+class Corpus:
+    """Many .flo files resident in HBM (flo_corpus); short windows of their decoded signals decoded in batches.
+
+    decode_windows(file_idx, starts, length) returns a float32 tensor [n, length, channels] on the context's device that
+    equals torch.from_numpy(decode(files[f]).reshape(-1, channels))[start:start + length] bit for bit, zero-padded past the
+    end of the file. The decode is enqueued behind torch's current stream and the result is ordered before whatever is
+    queued on that stream afterwards: no explicit synchronisation is needed."""
+
+    def __init__(self, files, ctx=None):
+        self._ctx = ctx or default_context()
+        self._L = self._ctx._L
+        blobs = [bytes(f) for f in files]
+        arr = (C.c_char_p * len(blobs))(*blobs)
+        lens = (C.c_size_t * len(blobs))(*[len(b) for b in blobs])
+        h = C.c_void_p()
+        self._ctx._chk(self._L.flo_corpus_create(self._ctx._h, len(blobs), arr, lens, C.byref(h)))
+        self._h = h
+        self._ctx._batches.add(self)   # closed before its context
+        sr, ch = C.c_uint32(), C.c_uint8()
+        self._L.flo_corpus_format(h, C.byref(sr), C.byref(ch))
+        self.sample_rate, self.channels = sr.value, ch.value
+        n = C.c_uint64()
+        lengths = []
+        for i in range(len(blobs)):
+            self._L.flo_corpus_file_frames(h, i, C.byref(n))
+            lengths.append(n.value)
+        self.lengths = np.array(lengths, np.uint64)
+
+    def decode_windows(self, file_idx, starts, length: int, out=None):
+        import torch
+        fi = np.ascontiguousarray(np.asarray(file_idx).reshape(-1), dtype=np.uint32)
+        st = np.ascontiguousarray(np.asarray(starts).reshape(-1), dtype=np.uint64)
+        if fi.size != st.size:
+            raise FloError("file_idx and starts differ in length")
+        if fi.size and int(fi.max()) >= len(self.lengths):
+            raise FloError("window file index out of range")
+        dev = torch.device("cuda", self._device_index())
+        shape = (fi.size, int(length), self.channels)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise FloError(f"out must be a contiguous float32 tensor of shape {shape} on {dev}")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._ctx._chk(self._L.flo_corpus_decode_windows(self._h, fi.size, fi.ctypes.data, st.ctypes.data, int(length),
+                                                         out.data_ptr(), out.numel(), C.c_void_p(stream)))
+        return out
+
+    def _device_index(self):
+        return self._ctx.device
+
+    def sync(self):
+        self._ctx._chk(self._L.flo_corpus_sync(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.flo_corpus_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _encode_analysed(mode, samples, sample_rate, channels, quality_or_level, bit_depth, metadata) -> bytes:

@@ -114,28 +114,27 @@ int parse_file(const uint8_t *data, size_t len, ParsedFile &f, const char **err)
     uint64_t extra_size = c.u64();
     uint64_t meta_size = c.u64();
     if (c.err) { *err = kEof; return -1; }
-    struct Toc { uint64_t off; uint32_t size; };
-    std::vector<Toc> toc;
+    std::vector<TocDesc> &toc = f.toc;
     if (toc_size >= 4) {   // reader.rs:76-99
         size_t n = c.u32();
         if (c.err) { *err = kEof; return -1; }
         if (n > 100000) { *err = "Invalid TOC: too many entries"; return -1; }
         toc.resize(n);
         for (size_t i = 0; i < n; i++) {
-            (void)c.u32();
-            toc[i].off = c.u64();
-            toc[i].size = c.u32();
-            (void)c.u32();
+            toc[i].frame_index = c.u32();
+            toc[i].byte_offset = c.u64();
+            toc[i].frame_size = c.u32();
+            toc[i].timestamp_ms = c.u32();
             if (c.err) { *err = kEof; return -1; }
         }
     }
     f.data_start = c.pos;
     const size_t data_end = c.pos + (size_t)f.data_size;
     for (size_t i = 0; i < toc.size(); i++) {   // reader.rs:101-166
-        size_t fs = (size_t)f.data_start + (size_t)toc[i].off;
+        size_t fs = (size_t)f.data_start + (size_t)toc[i].byte_offset;
         if (fs >= data_end) break;
         c.pos = fs;
-        const size_t frame_end = fs + toc[i].size;
+        const size_t frame_end = fs + toc[i].frame_size;
         FrameDesc fr{};
         fr.type = c.u8();
         fr.samples = c.u32();

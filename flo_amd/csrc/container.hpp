@@ -28,6 +28,13 @@ struct FrameDesc {
     uint32_t samples;     // frame_samples
     uint32_t first_channel;  // index into ParsedFile::channels
 };
+// One TOC entry as Reader::read_toc returns it (reader.rs:76-100, core/types.rs:174-179)
+struct TocDesc {
+    uint32_t frame_index;
+    uint64_t byte_offset;
+    uint32_t frame_size;
+    uint32_t timestamp_ms;
+};
 struct ParsedFile {
     uint8_t version_major = 0, version_minor = 0;
     uint16_t flags = 0;
@@ -37,6 +44,7 @@ struct ParsedFile {
     uint32_t data_crc32 = 0;
     uint64_t data_start = 0, data_size = 0;
     bool is_transform = false;   // any frame of type 253 (lib.rs:302-306)
+    std::vector<TocDesc> toc;    // every entry the TOC declares (the frames read stop at the end of DATA)
     std::vector<FrameDesc> frames;
     std::vector<ChannelDesc> channels_desc;
 };

@@ -1,0 +1,86 @@
+// ctx_internal.hpp — the context object and the host helpers that the library's source files share (flo_api.cpp owns
+// the definitions; corpus.cpp uses them). Not part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/flo_hip.h"
+#include "analysis_kernels.hpp"
+#include "lossy_device.hpp"
+#include "stager.hpp"
+#include "tables.hpp"
+
+using namespace flo;
+
+struct TableSet {
+    LossyTablesHost host;
+    void *blob = nullptr;  // one device allocation holding every table
+    LossyDevTables dev{};
+    const float *dev_window = nullptr;  // [2048], decode side
+};
+
+struct ProfRec {
+    std::string name;
+    hipEvent_t a, b;
+};
+struct ProfSum {   // launches already read out (their events are destroyed)
+    double ms = 0;
+    uint64_t n = 0;
+};
+
+struct flo_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    std::vector<TableSet *> tables;
+    bool profile = false;
+    std::vector<ProfRec> prof;              // bracketed launches not yet read out
+    std::map<std::string, ProfSum> prof_sum;
+    int force_path = 0;
+    hipDeviceProp_t prop{};
+    Stager *stager = nullptr;   // pinned staging ring + copy threads of the host-buffer entry points (made on first use)
+    hipStream_t up_stream = nullptr, down_stream = nullptr;   // uploads / downloads of flo_encode_batch's pipeline
+    int reserve_cus = -1;   // compute units the persistent chain kernel leaves free (-1: not set; see flo_ctx_reserve_cus)
+    AnalysisSide an_side;   // side streams of the analysis (made on first use)
+    bool an_side_ready = false;
+};
+
+int fail(flo_ctx *c, int code, const std::string &msg);
+#define HIPCHK(ctx, expr)                                                                               \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return fail(ctx, FLO_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));        \
+    } while (0)
+int profile_drain(flo_ctx *c, bool wait);
+// the constant tables of one sample rate (made on first use, kept by the context)
+int get_tables(flo_ctx *c, uint32_t sr, float quality, TableSet **out);
+// the context's pinned staging ring and copy threads (made on first use)
+int ctx_stager(flo_ctx *c);
+
+// Launch through `launch` on the ctx stream; with profiling on, bracketed by events under `name`.
+template <typename F>
+inline int timed_launch(flo_ctx *c, const char *name, F &&launch) {
+    if (!c->profile) {
+        int rc = launch();
+        return rc == 0 ? FLO_OK : fail(c, FLO_ERR_DEVICE, std::string("launch ") + name + " failed: " +
+                                                              hipGetErrorString((hipError_t)(rc > 0 ? rc : 1)));
+    }
+    if (c->prof.size() >= 256) {   // bound the queue of live events
+        int drc = profile_drain(c, false);
+        if (drc != FLO_OK) return drc;
+    }
+    ProfRec r;
+    r.name = name;
+    HIPCHK(c, hipEventCreate(&r.a));
+    HIPCHK(c, hipEventCreate(&r.b));
+    HIPCHK(c, hipEventRecord(r.a, c->stream));
+    int rc = launch();
+    HIPCHK(c, hipEventRecord(r.b, c->stream));
+    c->prof.push_back(r);
+    return rc == 0 ? FLO_OK : fail(c, FLO_ERR_DEVICE, std::string("launch ") + name + " failed");
+}
+

@@ -43,7 +43,11 @@ constexpr int kBlobStage = 2304;
 #else
 #define DSTAMP(i) do {} while (0)
 #endif
+// WIN = false: whole clips (flo_decode, flo_batch_decode). WIN = true: corpus windows (launch_lossy_window): the unit of work
+// is one run of blocks of one window, the run is trimmed to the window's blocks and its stores to the window's samples.
+template <bool WIN>
 __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
+    const LossyWinArgs &W = D.win;
     // One 8 KiB buffer serves three phases of a channel-frame in turn: the parse table of the record headers, then the
     // integers + the FFT exchange buffer, then the windowed output. Everything that does not change from frame to frame
     // lives in REGISTERS for the whole run (window x 2/1024 at the 32 positions the lane writes, rotation and FFT
@@ -76,14 +80,38 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     const unsigned L = blockIdx.x;
     const uint32_t c = (L >> 3) % nc;
     const unsigned long long P = (unsigned long long)(L / (8u * nc)) * 8u + (L & 7u);
+    unsigned clip, run, h0, h1;
+    float *out;
+    unsigned long long wfirst = 0, wend = 0, frame0 = 0;   // (WIN) the window's samples [wfirst, wend), its file's first frame
+    if constexpr (!WIN) {
     if (P >= (unsigned long long)D.n_clips * D.n_runs) return;
-    const unsigned clip = (unsigned)(P % (unsigned)D.n_clips);   // (clips fastest)
+    clip = (unsigned)(P % (unsigned)D.n_clips);   // (clips fastest)
     const unsigned nframes = D.clip_frames[clip];
-    const unsigned run = (unsigned)D.run;
-    const unsigned h0 = (unsigned)(P / (unsigned)D.n_clips) * run;   // first frame of the run = first output block
+    run = (unsigned)D.run;
+    h0 = (unsigned)(P / (unsigned)D.n_clips) * run;   // first frame of the run = first output block
     if (nframes < 2 || h0 + 1 >= nframes) return;
-    const unsigned h1 = h0 + run < nframes - 1 ? h0 + run : nframes - 1;   // last frame of the run
-    float *out = D.out + D.clip_out[clip];
+    h1 = h0 + run < nframes - 1 ? h0 + run : nframes - 1;   // last frame of the run
+    out = D.out + D.clip_out[clip];
+    } else {
+        // window w, run r of its runs (runs fastest): blocks b0 + r run .. of the window's blocks b0 .. b1, which need frames
+        // b0 .. b1 + 1 of the file; output past the file's last block is the zero tail, written by window_tail_kernel
+        if (P >= (unsigned long long)W.n_windows * W.runs_per_window) return;
+        run = (unsigned)D.run;
+        const unsigned w = (unsigned)(P / W.runs_per_window), r = (unsigned)(P % W.runs_per_window);
+        const LossyWinDev wd = W.win[w];
+        if (wd.n_frames < 2) return;
+        const unsigned long long n_samples = (unsigned long long)(wd.n_frames - 1) * 1024ull;
+        if (wd.start >= n_samples) return;
+        wfirst = wd.start;
+        wend = wd.start + W.length < n_samples ? wd.start + W.length : n_samples;
+        const unsigned b0 = (unsigned)(wfirst >> 10), b1 = (unsigned)((wend - 1) >> 10);
+        clip = 0;
+        h0 = b0 + r * run;
+        if (h0 > b1) return;
+        h1 = h0 + run < b1 + 1 ? h0 + run : b1 + 1;
+        frame0 = wd.frame0;
+        out = D.out + wd.dst;
+    }
     const float scale = 2.0f / 1024.0f;
     // loop invariants of the run, in registers
     float wn[8][2];        // window x 2/1024 (a power of two: exact) at the positions row r of this lane writes: four positions,
@@ -119,7 +147,9 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     auto index_run = [&](const uint32_t c) -> bool {
         wave_sync();
         if ((unsigned)lane <= h1 - h0) {
-            const unsigned long long f = D.clip_frame0[clip] + h0 + (unsigned)lane;
+            unsigned long long f;
+            if constexpr (WIN) f = frame0 + h0 + (unsigned)lane;
+            else f = D.clip_frame0[clip] + h0 + (unsigned)lane;
             const unsigned long long foff = D.blob_off[f];
             const uint32_t flen = D.blob_len[f];
             const uint8_t *g = D.bytes + foff;
@@ -464,6 +494,7 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
             // overlap-add (mdct.rs:449-456): block h - 1 = first half of this frame + second half of the previous one
             // (carried in registers). A channel the frame does not carry gives a silent block and leaves the overlap
             // alone (the reference would fail on such a frame; the oracle behaves like this).
+            if constexpr (!WIN) {
             if (h > h0) {
                 // (a uniform block base and a 32-bit lane offset: the stores take the scalar-base form, no 64-bit address
                 // arithmetic per store)
@@ -474,6 +505,21 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
                     const uint32_t j = (uint32_t)ln + 64u * (uint32_t)k;
                     const float a = present ? recon[j] + pv[k] : 0.0f;
                     ob[j * nchu] = a;
+                }
+            }
+            } else if (h > h0) {
+                // the block's samples inside the window [wfirst, wend) only, at their place in the window's slot (the slot
+                // of window w starts at w * length * channels floats: stores are not 16-byte aligned in general)
+                const unsigned long long bs = (unsigned long long)(h - 1) * 1024ull;
+                const uint32_t lo = wfirst > bs ? (uint32_t)(wfirst - bs) : 0u;
+                const uint32_t hi = wend - bs < 1024ull ? (uint32_t)(wend - bs) : 1024u;
+                float *ob = out + (long long)(bs - wfirst) * D.channels + c;   // (j >= lo keeps every store inside the slot)
+                const uint32_t nchu = (uint32_t)D.channels;
+#pragma unroll
+                for (int k = 0; k < 16; k++) {
+                    const uint32_t j = (uint32_t)ln + 64u * (uint32_t)k;
+                    const float a = present ? recon[j] + pv[k] : 0.0f;
+                    if (j >= lo && j < hi) ob[(long long)j * nchu] = a;
                 }
             }
             if (present) {
@@ -747,6 +793,37 @@ __global__ __launch_bounds__(256) void ll_finish_kernel(LlFinishArgs A) {
     }
 }
 
+// Corpus windows, lossless files: mid/side, interleave and * 1/32767 exactly as ll_finish_kernel, for the part of one
+// decoded frame that lies in one window, written to its place in the window's slot (channels the frame does not carry are
+// zeros, as the cleared output of flo_decode holds them). Items in x, the samples of an item across y.
+__global__ __launch_bounds__(256) void ll_window_finish_kernel(LlWinFinishArgs A) {
+    const unsigned t = blockIdx.x;
+    if (t >= A.n_items) return;
+    const LlWinItem it = A.items[t];
+    const float scale = 1.0f / 32767.0f;
+    const unsigned nch = (unsigned)A.channels;
+    for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < it.count; i += gridDim.y * blockDim.x) {
+        const unsigned j = it.from + i;
+        float *o = A.out + it.dst + (unsigned long long)i * nch;
+        if (it.mid_side && it.n_channels == 2) {
+            const int m = A.scratch[A.ch[it.first_channel].out_off + j], sd = A.scratch[A.ch[it.first_channel + 1].out_off + j];
+            const int l = (int)((unsigned)m + (unsigned)sd) / 2, r = (int)((unsigned)m - (unsigned)sd) / 2;
+            o[0] = (float)l * scale;
+            o[1] = (float)r * scale;
+        } else {
+            for (unsigned c = 0; c < nch; c++)
+                o[c] = c < it.n_channels ? (float)A.scratch[A.ch[it.first_channel + c].out_off + j] * scale : 0.0f;
+        }
+    }
+}
+
+// the zeros of windows that reach past the end of their file (one workgroup per window that has any)
+__global__ __launch_bounds__(256) void window_tail_kernel(const WinTailDev *tails, unsigned n, float *out) {
+    if (blockIdx.x >= n) return;
+    const WinTailDev t = tails[blockIdx.x];
+    for (unsigned i = t.first + threadIdx.x; i < t.end; i += blockDim.x) out[t.dst + i] = 0.0f;
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
 #define FLO_LAUNCH_CHECK()                      \
     do {                                        \
@@ -769,7 +846,7 @@ int launch_lossy_decode(const LossyDecArgs &A0, unsigned max_frames, hipStream_t
     if (hipMalloc(&d_dbg, 80) != hipSuccess || hipMemset(d_dbg, 0, 80) != hipSuccess) return -1;
     A.dbg = d_dbg;
 #endif
-    hipLaunchKernelGGL(lossy_decode_kernel, dim3((unsigned)wgs), dim3(64), 0, s, A);
+    hipLaunchKernelGGL(lossy_decode_kernel<false>, dim3((unsigned)wgs), dim3(64), 0, s, A);
     FLO_LAUNCH_CHECK();
 #ifdef FLO_DEC_STAMPS
     {
@@ -786,6 +863,33 @@ int launch_lossy_decode(const LossyDecArgs &A0, unsigned max_frames, hipStream_t
         fprintf(stderr, " total=%.0f\n", tot / fc);
     }
 #endif
+    return 0;
+}
+int launch_lossy_window(const LossyDecArgs &A0, const LossyWinArgs &W, unsigned run, hipStream_t s) {
+    if (!W.n_windows || !W.runs_per_window || A0.channels < 1 || run < 1 || run > (unsigned)kDecRunLong) return 0;
+    LossyDecArgs A = A0;
+    A.run = (int)run;
+    // the grid of lossy_decode_kernel: runs in groups of eight, the channels of a group eight workgroups apart (one XCD)
+    const unsigned long long units = (unsigned long long)W.n_windows * W.runs_per_window;
+    const unsigned long long wgs = (units + 7ull) / 8ull * 8ull * (unsigned)A.channels;
+    if (wgs > 0x7FFFFFFFull) return -1;
+    A.win = W;
+    hipLaunchKernelGGL(lossy_decode_kernel<true>, dim3((unsigned)wgs), dim3(64), 0, s, A);
+    FLO_LAUNCH_CHECK();
+    return 0;
+}
+int launch_ll_window_finish(const LlWinFinishArgs &A, unsigned max_count, hipStream_t s) {
+    if (!A.n_items || !max_count) return 0;
+    unsigned by = (max_count + 255) / 256;
+    if (by > 64) by = 64;
+    hipLaunchKernelGGL(ll_window_finish_kernel, dim3(A.n_items, by), dim3(256), 0, s, A);
+    FLO_LAUNCH_CHECK();
+    return 0;
+}
+int launch_window_tail(const WinTailDev *tails, unsigned n, float *out, hipStream_t s) {
+    if (!n) return 0;
+    hipLaunchKernelGGL(window_tail_kernel, dim3(n), dim3(256), 0, s, tails, n, out);
+    FLO_LAUNCH_CHECK();
     return 0;
 }
 int launch_ll_decode(const LlDecArgs &A, hipStream_t s) {

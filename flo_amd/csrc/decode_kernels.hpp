@@ -7,6 +7,20 @@
 
 namespace flo {
 
+// Corpus windows (lossy_decode_kernel<true>): one descriptor per window, built per call.
+struct LossyWinDev {
+    unsigned long long frame0;        // the file's first frame in the corpus's compacted frame list (blob_off / blob_len)
+    unsigned long long start;         // first sample-frame of the window in the file's decoded signal
+    unsigned long long dst;           // float offset of the window's slot in `out`
+    unsigned int n_frames;            // the file's frames (the decoded signal is (n_frames - 1) * 1024 sample-frames)
+    unsigned int pad;
+};
+struct LossyWinArgs {
+    const LossyWinDev *win;
+    unsigned int n_windows;
+    unsigned int runs_per_window;     // runs of LossyDecArgs::run blocks per window
+    unsigned int length;              // window_frames
+};
 // One transform frame = one wavefront. Frames of a clip are addressed by (clip, local frame index).
 struct LossyDecArgs {
     LossyDevTables T;                 // pack (rotation + FFT twiddles) and the coefficient -> band map of the file's sample rate
@@ -24,6 +38,7 @@ struct LossyDecArgs {
     int run;                          // output blocks per wavefront (set by the launcher)
     unsigned int n_runs;              // runs per clip (set by the launcher)
     unsigned long long *dbg;          // FLO_DEC_STAMPS builds only: phase tick sums (set by the launcher)
+    LossyWinArgs win;                 // corpus windows only (set by launch_lossy_window)
 };
 
 // One ALPC / raw / silent channel wrapper of one frame = one thread.
@@ -81,9 +96,36 @@ struct LlFinishArgs {
     int *out_i32;                     // zero-filled interleaved i32 (nullable; parity tests)
 };
 
+// Zeros of every window past the end of its file: floats [first, end) of the window's slot.
+struct WinTailDev {
+    unsigned long long dst;           // float offset of the window's slot
+    unsigned int first, end;
+};
+// Lossless windows: one item = one decoded frame of one window (a frame two windows touch is decoded once for each).
+struct LlWinItem {
+    unsigned long long dst;           // float offset of the sample-frame `from` lands on, in the window's slot
+    unsigned int first_channel;       // the frame's wrappers in the call's wrapper list (scratch offsets in out_off)
+    unsigned int n_channels;
+    unsigned int from, count;         // sample-frames [from, from + count) of the frame go to the window
+    unsigned int mid_side;
+    unsigned int pad;
+};
+struct LlWinFinishArgs {
+    const LlWinItem *items;
+    const LlChannelDev *ch;
+    unsigned int n_items;
+    int channels;
+    const int *scratch;
+    float *out;
+};
+
 int launch_lossy_decode(const LossyDecArgs &A, unsigned max_frames, hipStream_t s);
 int launch_ll_decode(const LlDecArgs &A, hipStream_t s);
 int launch_ll_decode_parallel(const LlParArgs &A, unsigned max_tiles, hipStream_t s);
 int launch_ll_finish(const LlFinishArgs &A, unsigned max_samples, hipStream_t s);
+// corpus windows: runs of `run` blocks (<= 16), runs_per_window of them per window
+int launch_lossy_window(const LossyDecArgs &A, const LossyWinArgs &W, unsigned run, hipStream_t s);
+int launch_ll_window_finish(const LlWinFinishArgs &A, unsigned max_count, hipStream_t s);
+int launch_window_tail(const WinTailDev *tails, unsigned n, float *out, hipStream_t s);
 
 }  // namespace flo

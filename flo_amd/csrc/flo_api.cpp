@@ -26,56 +26,18 @@
 #include "lossless_kernels.hpp"
 #include "lossy_kernels.hpp"
 #include "tables.hpp"
+#include "ctx_internal.hpp"
 
 using namespace flo;
 
-// ------------------------------------------------------------------------------------------------ context
-struct TableSet {
-    LossyTablesHost host;
-    void *blob = nullptr;  // one device allocation holding every table
-    LossyDevTables dev{};
-    const float *dev_window = nullptr;  // [2048], decode side
-};
-
-struct ProfRec {
-    std::string name;
-    hipEvent_t a, b;
-};
-struct ProfSum {   // launches already read out (their events are destroyed)
-    double ms = 0;
-    uint64_t n = 0;
-};
-
-struct flo_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    std::vector<TableSet *> tables;
-    bool profile = false;
-    std::vector<ProfRec> prof;              // bracketed launches not yet read out
-    std::map<std::string, ProfSum> prof_sum;
-    int force_path = 0;
-    hipDeviceProp_t prop{};
-    Stager *stager = nullptr;   // pinned staging ring + copy threads of the host-buffer entry points (made on first use)
-    hipStream_t up_stream = nullptr, down_stream = nullptr;   // uploads / downloads of flo_encode_batch's pipeline
-    int reserve_cus = -1;   // compute units the persistent chain kernel leaves free (-1: not set; see flo_ctx_reserve_cus)
-    AnalysisSide an_side;   // side streams of the analysis (made on first use)
-    bool an_side_ready = false;
-};
 static const int kDefaultReservedCus = 8;
 
 static thread_local std::string g_create_err;
 
-static int fail(flo_ctx *c, int code, const std::string &msg) {
+int fail(flo_ctx *c, int code, const std::string &msg) {
     if (c) c->err = msg;
     return code;
 }
-#define HIPCHK(ctx, expr)                                                                               \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(ctx, FLO_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-    } while (0)
 
 // A decoded file's PCM goes to the caller in fresh memory (flo_free = free). A fresh 60 MB of 4 KB pages is 15 000 page
 // faults under the copy that fills it - 30 ms for a 3-minute file whose kernels take 1 ms - so large results are asked for
@@ -196,7 +158,7 @@ extern "C" int flo_ctx_profile_reset(flo_ctx *c) {
 }
 // Fold every finished bracket into the per-kernel sums and destroy its events (a long profiled run keeps at most the
 // launches since the last drain alive).
-static int profile_drain(flo_ctx *c, bool wait) {
+int profile_drain(flo_ctx *c, bool wait) {
     size_t keep = 0;
     for (size_t i = 0; i < c->prof.size(); i++) {
         ProfRec &r = c->prof[i];
@@ -227,30 +189,8 @@ extern "C" int flo_ctx_profile_query(flo_ctx *c, const char *kernel, double *tot
     return FLO_OK;
 }
 
-template <typename F>
-static int timed_launch(flo_ctx *c, const char *name, F &&launch) {
-    if (!c->profile) {
-        int rc = launch();
-        return rc == 0 ? FLO_OK : fail(c, FLO_ERR_DEVICE, std::string("launch ") + name + " failed: " +
-                                                              hipGetErrorString((hipError_t)(rc > 0 ? rc : 1)));
-    }
-    if (c->prof.size() >= 256) {   // bound the queue of live events
-        int drc = profile_drain(c, false);
-        if (drc != FLO_OK) return drc;
-    }
-    ProfRec r;
-    r.name = name;
-    HIPCHK(c, hipEventCreate(&r.a));
-    HIPCHK(c, hipEventCreate(&r.b));
-    HIPCHK(c, hipEventRecord(r.a, c->stream));
-    int rc = launch();
-    HIPCHK(c, hipEventRecord(r.b, c->stream));
-    c->prof.push_back(r);
-    return rc == 0 ? FLO_OK : fail(c, FLO_ERR_DEVICE, std::string("launch ") + name + " failed");
-}
-
 // ---- constant tables -----------------------------------------------------------------------------------
-static int get_tables(flo_ctx *c, uint32_t sr, float quality, TableSet **out) {
+int get_tables(flo_ctx *c, uint32_t sr, float quality, TableSet **out) {
     float q = quality < 0.f ? 0.f : (quality > 1.f ? 1.f : quality);
     if (quality != quality) q = 0.f;  // NaN clamps to NaN in Rust; the threshold formula then yields NaN -> treat as 0
     for (auto *t : c->tables)
@@ -912,7 +852,7 @@ extern "C" int flo_batch_fetch(flo_batch *b, size_t clip, const uint8_t *meta, s
 }
 
 // ------------------------------------------------------------------------------------------------ one-shot API
-static int ctx_stager(flo_ctx *c) {
+int ctx_stager(flo_ctx *c) {
     if (c->stager && c->up_stream) return FLO_OK;
     if (c->stager) {
         HIPCHK(c, hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
@@ -1804,6 +1744,119 @@ extern "C" int flo_decode(flo_ctx *c, const uint8_t *flo, size_t len, float **pc
 extern "C" int flo_decode_lossless_i32(flo_ctx *c, const uint8_t *flo, size_t len, int32_t **pcm, size_t *n_interleaved,
                                        uint32_t *sample_rate, uint8_t *channels) {
     return decode_impl(c, flo, len, nullptr, pcm, n_interleaved, sample_rate, channels);
+}
+
+// decode_frame_at (seeking.rs:43-63): one frame, by its type. Lossless (decode_frame_lossless, :161-176): the frame alone
+// through the device lossless path. Transform (decode_frame_lossy, :179-207): the reference warms a TransformDecoder up on
+// every earlier frame, which leaves the second half of the last earlier frame with channels in the overlap buffer
+// (mdct.rs:437-468); here flo_decode's kernel runs on just that frame and frame i (a two-byte blob of no channels
+// stands in for a missing predecessor: it leaves the overlap at zero), so the block is flo_decode's bit for bit.
+extern "C" int flo_decode_frame_at(flo_ctx *c, const uint8_t *flo, size_t len, uint32_t frame_index, float **pcm,
+                                   size_t *n_interleaved) {
+    if (!c || !flo || !pcm || !n_interleaved) return fail(c, FLO_ERR_ARG, "null argument");
+    *pcm = nullptr;
+    *n_interleaved = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    ParsedFile f;
+    const char *perr = "";
+    if (parse_file(flo, len, f, &perr) != 0) return fail(c, FLO_ERR_FORMAT, perr);
+    if ((size_t)frame_index >= f.frames.size())
+        return fail(c, FLO_ERR_FORMAT, "Frame index " + std::to_string(frame_index) + " out of bounds (total frames: " +
+                                           std::to_string(f.frames.size()) + ")");
+    const FrameDesc &fr = f.frames[frame_index];
+    const int nch = f.channels;
+    DevMem d_bytes;
+    QuiesceOnExit quiesce_d_bytes(c);
+    HIPCHK(c, pool_alloc(&d_bytes.p, len + 32));
+    HIPCHK(c, hipMemcpyAsync(d_bytes.p, flo, len, hipMemcpyHostToDevice, c->stream));
+    if (fr.type != 253) {
+        ParsedFile one;
+        one.channels = f.channels;
+        one.frames.push_back(fr);
+        one.frames[0].first_channel = 0;
+        for (unsigned k = 0; k < fr.n_channels; k++) one.channels_desc.push_back(f.channels_desc[fr.first_channel + k]);
+        LlWork w;
+        w.add(one, 0, nch);
+        const size_t n_out = nch ? (size_t)w.out_sf * (size_t)nch : 0;
+        float *host = (float *)malloc(n_out ? n_out * sizeof(float) : 1);
+        if (!host) return fail(c, FLO_ERR_NOMEM, "out of host memory");
+        if (n_out) {
+            DevMem d_out;
+            QuiesceOnExit quiesce_d_out(c);
+            int rc;
+            if (pool_alloc(&d_out.p, n_out * sizeof(float)) != hipSuccess) {
+                free(host);
+                return fail(c, FLO_ERR_NOMEM, "decode buffers");
+            }
+            if ((rc = ll_decode_device(c, w, d_bytes.as<uint8_t>(), nch, d_out.as<float>(), nullptr)) != FLO_OK ||
+                (rc = download(c, host, d_out.p, n_out * sizeof(float))) != FLO_OK) {
+                free(host);
+                return rc;
+            }
+        }
+        *pcm = host;
+        *n_interleaved = n_out;
+        return FLO_OK;
+    }
+    if (!fr.n_channels) return fail(c, FLO_ERR_FORMAT, "Transform frame has no channel data");
+    if (nch == 0) return fail(c, FLO_ERR_FORMAT, "Failed to deserialize transform frame");
+    // the two blobs: the last earlier frame with channels (or the empty stand-in behind the file's bytes), then frame i
+    static const uint8_t kNoChannels[2] = {0, 0};   // deserialize_frame: Long block, zero channels
+    std::vector<unsigned long long> blob_off(2);
+    std::vector<unsigned int> blob_len(2);
+    blob_off[0] = len;
+    blob_len[0] = 2;
+    for (size_t j = frame_index; j-- > 0;)
+        if (f.frames[j].n_channels) {
+            const ChannelDesc &cd = f.channels_desc[f.frames[j].first_channel];
+            blob_off[0] = cd.off;
+            blob_len[0] = cd.len;
+            break;
+        }
+    blob_off[1] = f.channels_desc[fr.first_channel].off;
+    blob_len[1] = f.channels_desc[fr.first_channel].len;
+    HIPCHK(c, hipMemcpyAsync(d_bytes.as<uint8_t>() + len, kNoChannels, 2, hipMemcpyHostToDevice, c->stream));
+    TableSet *ts;
+    int rc = get_tables(c, f.sample_rate, 0.5f, &ts);
+    if (rc != FLO_OK) return rc;
+    const size_t n_out = 1024 * (size_t)nch;
+    DevMem d_off, d_len, d_c0, d_cn, d_co, d_out, d_err;
+    QuiesceOnExit quiesce_d_off(c);
+    std::vector<unsigned long long> c0{0}, co{0};
+    std::vector<unsigned int> cn{2u};
+    std::vector<int> zero{0};
+    if ((rc = upload(c, d_off, blob_off)) || (rc = upload(c, d_len, blob_len)) || (rc = upload(c, d_c0, c0)) ||
+        (rc = upload(c, d_cn, cn)) || (rc = upload(c, d_co, co)) || (rc = upload(c, d_err, zero)))
+        return rc;
+    HIPCHK(c, pool_alloc(&d_out.p, n_out * sizeof(float)));
+    LossyDecArgs A{};
+    A.T = ts->dev;
+    A.window = ts->dev_window;
+    A.bytes = d_bytes.as<uint8_t>();
+    A.blob_off = d_off.as<unsigned long long>();
+    A.blob_len = d_len.as<unsigned int>();
+    A.clip_frame0 = d_c0.as<unsigned long long>();
+    A.clip_frames = d_cn.as<unsigned int>();
+    A.clip_out = d_co.as<unsigned long long>();
+    A.n_clips = 1;
+    A.channels = nch;
+    A.out = d_out.as<float>();
+    A.error = d_err.as<int>();
+    if ((rc = timed_launch(c, "lossy_decode", [&] { return launch_lossy_decode(A, 2u, c->stream); })) != FLO_OK) return rc;
+    float *host = (float *)malloc(n_out * sizeof(float));
+    if (!host) return fail(c, FLO_ERR_NOMEM, "out of host memory");
+    int herr = 0;
+    hipError_t e = hipMemcpyAsync(&herr, d_err.p, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(host, d_out.p, n_out * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || herr) {
+        free(host);
+        return e != hipSuccess ? fail(c, FLO_ERR_DEVICE, std::string("decode_frame_at: ") + hipGetErrorString(e))
+                               : fail(c, FLO_ERR_FORMAT, "Failed to deserialize transform frame");
+    }
+    *pcm = host;
+    *n_interleaved = n_out;
+    return FLO_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ multi-GPU

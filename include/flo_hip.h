@@ -97,6 +97,67 @@ typedef struct flo_container_info {
 } flo_container_info;
 int flo_probe_container(const uint8_t *flo, size_t len, flo_container_info *out, char *err, size_t err_cap);
 
+/* ---- seeking: libflo/src/seeking.rs (wasm exports get_toc / decode_frame_at / seek_to_time, lib.rs:478-530) ----------
+ * The reference's semantics, quirks included. A lossy file's TOC stamps frame i at i * 1024 / sample_rate ms, but frame i
+ * decodes input samples [(i - 1) * 1024, i * 1024): the encoder's first frame is pre-roll that flo_decode drops. So
+ * seek_to_time answers in the TOC's time base and decode_frame_at(i) is output block i - 1 of flo_decode (frame 0: the
+ * pre-roll block flo_decode never returns). The corpus window decode below counts in flo_decode's samples instead. */
+typedef struct flo_toc_entry {   /* core/types.rs:174-179 */
+    uint32_t frame_index;
+    uint32_t frame_size;
+    uint64_t byte_offset;
+    uint32_t timestamp_ms;
+    uint32_t pad;
+} flo_toc_entry;
+typedef struct flo_seek_result {   /* seeking.rs:7-19 */
+    uint32_t frame_index;
+    uint32_t timestamp_ms;
+    uint64_t byte_offset;
+    uint32_t sample_offset;
+    uint32_t next_timestamp_ms;
+} flo_seek_result;
+/* get_toc (seeking.rs:28-32): every TOC entry exactly as Reader::read returns it (reader.rs:76-100); *entries is malloc'ed
+ * (flo_free; NULL when *n = 0). FLO_ERR_FORMAT with the reader's message in err. No context needed. */
+int flo_get_toc(const uint8_t *flo, size_t len, flo_toc_entry **entries, size_t *n, char *err, size_t err_cap);
+/* seek_to_time (seeking.rs:75-132, 136-159): the rightmost entry with timestamp_ms <= target_ms, clamped to the last frame
+ * read; sample_offset into that frame; next_timestamp_ms (for the last frame: its timestamp + frame_samples * 1000 /
+ * sample_rate). "No TOC available for seeking" for an empty TOC. Where the reference would panic (TOC entries but no
+ * frames read, a zero sample rate) FLO_ERR_FORMAT; u32 differences wrap as in a release build. No context needed. */
+int flo_seek_to_time(const uint8_t *flo, size_t len, uint32_t target_ms, flo_seek_result *out, char *err, size_t err_cap);
+/* decode_frame_at (seeking.rs:43-63, 161-207): the interleaved f32 samples of one frame (*pcm malloc'ed, flo_free).
+ * A lossless frame goes through the device lossless path on its own (frame_samples * channels floats). A transform frame
+ * is the overlap-add of its first half with the second half of the last earlier frame that carries channels - zeros if
+ * there is none - on the device, with flo_decode's kernel: 1024 * channels floats, for i >= 1 of an encoder-made file
+ * bit for bit flo_decode(file)[(i - 1) * 1024 * ch .. i * 1024 * ch]. (The reference gets the same overlap by decoding
+ * every earlier frame.) Errors as the reference's: "Frame index i out of bounds (total frames: n)", "Failed to deserialize
+ * transform frame" - also when the earlier frame it overlaps with cannot be deserialised, where the reference skips it. */
+int flo_decode_frame_at(flo_ctx *ctx, const uint8_t *flo, size_t len, uint32_t frame_index, float **pcm,
+                        size_t *n_interleaved);
+
+/* ---- corpus: many files resident in HBM, many short windows decoded at once -------------------------------------------
+ * flo_corpus_create parses every file on the host once (reader errors come back as FLO_ERR_FORMAT with the reader's
+ * message), uploads all bytes once and builds the per-file frame tables once. All files must share one sample rate and
+ * one channel count (FLO_ERR_ARG otherwise); lossy and lossless files may be mixed. files[i] may be freed afterwards.
+ *
+ * flo_corpus_decode_windows: window w is (file[w], start[w]) in sample-frames of what flo_decode returns for that file;
+ * its window_frames * channels interleaved floats go to dst_device + w * window_frames * channels and equal
+ * flo_decode(file)[start * ch .. (start + window_frames) * ch] bit for bit, zeros past the end of the file. The call only
+ * enqueues: the work runs on the ctx stream, ordered by events after what is queued on `stream` (a hipStream_t: NULL is
+ * the null stream - torch's default stream - and flo_ctx_stream(ctx) orders against nothing else), and later work on
+ * `stream` sees the result. Host work is O(windows + lossless frames touched); scratch grows to the largest call and is
+ * kept. A frame touched by two windows of one call is decoded twice (once per window: no cross-window bookkeeping).
+ * A lossy frame that cannot be deserialised sets an error word: flo_corpus_sync waits for the ctx stream and returns
+ * FLO_ERR_FORMAT with flo_decode's message ("Failed to deserialize transform frame"), then clears the word. */
+typedef struct flo_corpus flo_corpus;
+int flo_corpus_create(flo_ctx *ctx, size_t n_files, const uint8_t *const *files, const size_t *lens, flo_corpus **out);
+void flo_corpus_destroy(flo_corpus *c);
+int flo_corpus_format(const flo_corpus *c, uint32_t *sample_rate, uint8_t *channels);
+/* flo_decode's length of file `file` in sample-frames */
+int flo_corpus_file_frames(const flo_corpus *c, size_t file, uint64_t *decoded_sample_frames);
+int flo_corpus_decode_windows(flo_corpus *c, size_t n_windows, const uint32_t *file, const uint64_t *start,
+                              uint32_t window_frames, float *dst_device, size_t dst_cap_floats, void *stream);
+int flo_corpus_sync(flo_corpus *c);
+
 /* ---- device-resident batch (the throughput path: PCM already in HBM, bitstreams left in HBM) -------- */
 typedef struct flo_batch flo_batch;
 
