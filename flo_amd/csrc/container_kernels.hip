@@ -6,6 +6,7 @@
 // shift-and-xor loops, the per-stripe skip is a table.
 #include <stdlib.h>
 #include "container_kernels.hpp"
+#include "crc_device.hpp"
 
 #include <cstring>
 #include <map>
@@ -14,30 +15,6 @@
 
 namespace flo {
 
-constexpr uint32_t kPoly = 0xEDB88320u;
-
-__host__ __device__ inline uint32_t multmodp(uint32_t a, uint32_t b) {   // a(x) * b(x) mod P, reflected bit order
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ kPoly : b >> 1;
-    }
-    return p;
-}
-__host__ __device__ inline uint32_t x8n_modp(unsigned long long n) {   // x^(8 n) mod P
-    uint32_t sq = 0x00800000u;   // x^8 in the reflected representation (x^0 = 0x80000000)
-    uint32_t p = 0x80000000u;
-    while (n) {
-        if (n & 1ull) p = multmodp(sq, p);
-        sq = multmodp(sq, sq);
-        n >>= 1;
-    }
-    return p;
-}
 // x^(8 n) mod P from the table of x^(8 2^j): one product per set bit of n
 __device__ __forceinline__ uint32_t x8n_tab(const unsigned int (&pow2)[40], unsigned long long n) {
     uint32_t p = 0x80000000u;
@@ -62,97 +39,52 @@ __device__ __forceinline__ void put64(uint8_t *p, unsigned long long v) {
 }
 
 constexpr int kFinThreads = 256;
-constexpr unsigned kBlk = 64;                       // bytes a thread consumes per stripe
-constexpr unsigned kStripe = kFinThreads * kBlk;    // 16 KiB: one coalesced sweep of the workgroup
 
-// The CRC register after a message M from initial value I is (I x^(8n) + M(x) x^32) mod P: linear in I and in M.
-// So a slice of the DATA chunk is cut into 64-byte blocks dealt round-robin to the 256 threads (every load of the
-// workgroup is 16 KiB contiguous); a thread carries one register across its blocks, multiplying by
-// x^(8 (16384 - 64)) to skip the other threads' bytes (a 4 x 256 table, like the byte tables), and at the end each
-// register is moved to the end of the slice by x^(8 tail) and all are xor-ed together. A clip is cut into `parts`
-// slices (one workgroup each, so that a single long clip still fills the chip); finish_files_kernel moves the slice
-// registers to the end of the message and adds the contribution of the initial value.
-__device__ __forceinline__ unsigned long long slice_bytes(unsigned long long n, unsigned parts) {
-    unsigned long long s = (n + parts - 1) / parts;
-    return (s + kStripe - 1) / kStripe * kStripe;
-}
-
+// A clip is cut into `parts` slices (crc_slice_range; one workgroup each, so that a single long clip still fills the
+// chip); finish_files_kernel moves the slice registers to the end of the message and adds the contribution of the
+// initial value. The arithmetic is crc_slice_reg (crc_device.hpp), here with the 256 threads of a workgroup.
 __device__ __forceinline__ void crc_slice_body(const FinishArgs &A, const unsigned clip, const unsigned part) {
     __shared__ uint32_t tab[4][256];    // slicing-by-4 byte tables
-    __shared__ uint32_t skip[4][256];   // multiplication by x^(8 (kStripe - kBlk))
+    __shared__ uint32_t skip[4][256];   // multiplication by x^(8 (16384 - 64))
     __shared__ uint32_t s_red[kFinThreads / 64];
-    __shared__ uint32_t s_pw[2];
     if (clip >= (unsigned)A.n_clips) return;
     const unsigned t = threadIdx.x;
     const unsigned long long total = A.clip_bytes[clip];
-    const unsigned long long S = slice_bytes(total, A.parts);
-    const unsigned long long beg = (unsigned long long)part * S < total ? (unsigned long long)part * S : total;
-    const unsigned long long n = beg + S < total ? S : total - beg;
+    unsigned long long beg, n;
+    crc_slice_range(total, A.parts, part, beg, n);
     if (n == 0) {
         if (t == 0) A.part_reg[(unsigned long long)clip * A.parts + part] = 0;
         return;
     }
-    const uint8_t *data = A.out + A.data_off[clip] + beg;
+    for (int k = 0; k < 4; k++) {   // made once on the host (crc_device_tables)
+        tab[k][t] = A.tables[kCrcTabByte + k * 256 + t];
+        skip[k][t] = A.tables[kCrcTabSkip256 + k * 256 + t];
+    }
+    __syncthreads();
+    const uint32_t r = crc_slice_reg<kFinThreads>(tab, skip, A.blk_pow, A.byte_pow, A.out + A.data_off[clip] + beg, n, t, s_red);
+    if (t == 0) A.part_reg[(unsigned long long)clip * A.parts + part] = r;
+}
 
-    // byte tables (crc32.rs:2-20 builds the first one the same way) and the skip table, made once on the host
+// The slice registers of a clip the chain encode's tail did not reach (crc_ready[clip] != epoch), computed by the
+// finish workgroup itself into LDS (s_part), one slice after the other. Uniform in the workgroup.
+__device__ __forceinline__ void crc_fallback_256(const FinishArgs &A, const unsigned clip, const unsigned long long total,
+                                                 uint32_t *s_part) {
+    __shared__ uint32_t tab[4][256];
+    __shared__ uint32_t skip[4][256];
+    __shared__ uint32_t s_red[kFinThreads / 64];
+    const unsigned t = threadIdx.x;
     for (int k = 0; k < 4; k++) {
-        tab[k][t] = A.tables[k * 256 + t];
-        skip[k][t] = A.tables[1024 + k * 256 + t];
+        tab[k][t] = A.tables[kCrcTabByte + k * 256 + t];
+        skip[k][t] = A.tables[kCrcTabSkip256 + k * 256 + t];
     }
-    const unsigned long long full = n / kStripe;          // complete stripes
-    const unsigned long long rem0 = full * kStripe;       // first byte behind them
-    const unsigned rem = (unsigned)(n - rem0);
-    const unsigned nb = rem / kBlk, last = rem % kBlk;
-    // two per-slice powers from the tables: x^(8 rem) = x^(8 * 64 * nb) * x^(8 last), and x^(8 last)
-    if (t == 0) s_pw[0] = multmodp(A.blk_pow[nb], A.byte_pow[last]);
-    if (t == 64) s_pw[1] = A.byte_pow[last];
     __syncthreads();
-    auto eat = [&](uint32_t reg, const uint8_t *p, unsigned bytes) {   // bytes is a multiple of 4, p 4-byte aligned
-        for (unsigned i = 0; i < bytes; i += 4) {
-            const uint32_t w = *reinterpret_cast<const uint32_t *>(p + i) ^ reg;
-            reg = tab[3][w & 0xFFu] ^ tab[2][(w >> 8) & 0xFFu] ^ tab[1][(w >> 16) & 0xFFu] ^ tab[0][w >> 24];
-        }
-        return reg;
-    };
-    uint32_t acc = 0;
-    if (full) {
-        uint32_t reg = 0;
-        const uint8_t *p = data + (unsigned long long)t * kBlk;
-        for (unsigned long long sidx = 0; sidx < full; sidx++, p += kStripe) {
-            reg = skip[0][reg & 0xFFu] ^ skip[1][(reg >> 8) & 0xFFu] ^ skip[2][(reg >> 16) & 0xFFu] ^ skip[3][reg >> 24];
-            const uint4 a = *reinterpret_cast<const uint4 *>(p), b = *reinterpret_cast<const uint4 *>(p + 16),
-                        c = *reinterpret_cast<const uint4 *>(p + 32), d = *reinterpret_cast<const uint4 *>(p + 48);
-            const uint32_t w[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const uint32_t v = w[i] ^ reg;
-                reg = tab[3][v & 0xFFu] ^ tab[2][(v >> 8) & 0xFFu] ^ tab[1][(v >> 16) & 0xFFu] ^ tab[0][v >> 24];
-            }
-        }
-        // the register now stands behind this thread's block of the last complete stripe
-        // ... and moves to the end of the slice: x^(8 (64 (255 - t) + rem))
-        acc = multmodp(multmodp(A.blk_pow[kFinThreads - 1 - t], s_pw[0]), reg);
+    for (unsigned p = 0; p < A.parts; p++) {
+        unsigned long long beg, n;
+        crc_slice_range(total, A.parts, p, beg, n);
+        const uint32_t r = crc_slice_reg<kFinThreads>(tab, skip, A.blk_pow, A.byte_pow, A.out + A.data_off[clip] + beg, n, t, s_red);
+        if (t == 0) s_part[p] = r;
     }
-    {   // the incomplete stripe: one 64-byte block per thread, then the last < 64 bytes on thread 0
-        if (t < nb) {
-            const uint32_t reg = eat(0, data + rem0 + (unsigned long long)t * kBlk, kBlk);
-            acc ^= multmodp(multmodp(A.blk_pow[nb - 1 - t], s_pw[1]), reg);
-        }
-        if (t == 0) {
-            uint32_t reg = 0;
-            const uint8_t *p = data + rem0 + (unsigned long long)nb * kBlk;
-            for (unsigned i = 0; i < last; i++) reg = tab[0][(reg ^ p[i]) & 0xFFu] ^ (reg >> 8);
-            acc ^= reg;
-        }
-    }
-    for (int d = 32; d > 0; d >>= 1) acc ^= __shfl_down(acc, d);
-    if ((t & 63) == 0) s_red[t >> 6] = acc;
     __syncthreads();
-    if (t == 0) {
-        uint32_t r = 0;
-        for (int k = 0; k < kFinThreads / 64; k++) r ^= s_red[k];
-        A.part_reg[(unsigned long long)clip * A.parts + part] = r;
-    }
 }
 
 __global__ __launch_bounds__(kFinThreads) void crc_slices_kernel(FinishArgs A) {
@@ -208,11 +140,20 @@ __device__ __forceinline__ void finish_body(const FinishArgs &A, const unsigned 
     // slice registers -> end of the message; thread `parts` adds the initial register carried through all n bytes
     uint32_t acc = 0;
     if (first && do_crc) {
-        const unsigned long long S = slice_bytes(n, A.parts);
+        const uint32_t *regs = A.part_reg + (unsigned long long)clip * A.parts;
+        if constexpr (THREADS == kFinThreads) {
+            // a many-clips batch from the stereo chain encode: the slices of a clip its idle tail did not reach are
+            // computed here (crc_ready[clip] carries the launch's epoch for the others; read after the launch boundary)
+            __shared__ uint32_t s_part[128];
+            if (A.crc_ready && A.crc_ready[clip] != A.epoch) {   // (uniform)
+                crc_fallback_256(A, clip, n, s_part);
+                regs = s_part;
+            }
+        }
         if (t < A.parts) {
-            const unsigned long long end = (unsigned long long)(t + 1) * S < n ? (unsigned long long)(t + 1) * S : n;
-            const unsigned long long beg = (unsigned long long)t * S < n ? (unsigned long long)t * S : n;
-            if (end > beg) acc = multmodp(x8n_fast(A, n - end), A.part_reg[(unsigned long long)clip * A.parts + t]);
+            unsigned long long beg, len;
+            crc_slice_range(n, A.parts, t, beg, len);
+            if (len) acc = multmodp(x8n_fast(A, n - beg - len), regs[t]);
         } else if (t == A.parts) {
             acc = multmodp(x8n_fast(A, n), 0xFFFFFFFFu);
         }
@@ -345,52 +286,70 @@ __global__ __launch_bounds__(kFinThreads) void crc_and_toc_kernel(FinishArgs A) 
     else finish_body<kFinThreads>(A, blockIdx.x, blockIdx.y - A.parts);
 }
 
+// host copies of the power rows that travel in FinishArgs, and the device table (crc_device.hpp) per device, made on
+// first use and kept for the process
+static std::mutex crc_mu;
+static unsigned int crc_pow2[40], crc_stripep[256];
+static std::vector<unsigned int> crc_host_tables;
+static std::map<int, unsigned int *> crc_dev_tables;
+
+static void crc_make_host_tables() {   // (crc_mu held)
+    if (!crc_host_tables.empty()) return;
+    uint32_t p = 0x00800000u;   // x^8
+    for (int j = 0; j < 40; j++, p = multmodp(p, p)) crc_pow2[j] = p;
+    for (int i = 0; i < 256; i++) crc_stripep[i] = x8n_modp((unsigned long long)i << 14);
+    std::vector<unsigned int> &h = crc_host_tables;
+    h.resize(kCrcTabWords);
+    for (uint32_t i = 0; i < 256; i++) {
+        uint32_t c = i;
+        for (int j = 0; j < 8; j++) c = (c & 1u) ? (c >> 1) ^ kPoly : c >> 1;
+        h[kCrcTabByte + i] = c;
+    }
+    for (uint32_t i = 0; i < 256; i++) {
+        uint32_t c = h[kCrcTabByte + i];
+        for (int k = 1; k < 4; k++) {
+            c = h[kCrcTabByte + (c & 0xFFu)] ^ (c >> 8);
+            h[kCrcTabByte + k * 256 + i] = c;
+        }
+    }
+    const uint32_t skip256 = x8n_modp(256 * kBlk - kBlk), skip64 = x8n_modp(64 * kBlk - kBlk);
+    for (int k = 0; k < 4; k++)
+        for (uint32_t i = 0; i < 256; i++) {
+            h[kCrcTabSkip256 + k * 256 + i] = multmodp(skip256, i << (8 * k));
+            h[kCrcTabSkip64 + k * 256 + i] = multmodp(skip64, i << (8 * k));
+        }
+    for (int i = 0; i < 256; i++) h[kCrcTabBlkPow + i] = x8n_modp(64ull * i);
+    for (int i = 0; i < 64; i++) h[kCrcTabBytePow + i] = x8n_modp((unsigned long long)i);
+}
+
+const unsigned int *crc_device_tables() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lock(crc_mu);
+    crc_make_host_tables();
+    auto it = crc_dev_tables.find(dev);
+    if (it != crc_dev_tables.end()) return it->second;
+    unsigned int *d = nullptr;
+    if (hipMalloc(&d, crc_host_tables.size() * 4) != hipSuccess) return nullptr;
+    if (hipMemcpy(d, crc_host_tables.data(), crc_host_tables.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return nullptr;
+    }
+    crc_dev_tables[dev] = d;
+    return d;
+}
+
 int launch_finish_files(FinishArgs A, hipStream_t s) {
     if (!A.n_clips) return 0;
     if (A.parts < 1 || A.parts > (A.n_clips < 64 ? 512u : 128u) || !A.part_reg) return -1;
-    static unsigned int pow2[40], blk[256], bytep[64], stripep[256];
-    static std::vector<unsigned int> host_tables;
-    static std::mutex mu;
-    static std::map<int, unsigned int *> dev_tables;   // one copy per device, made on first use, kept for the process
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    if (!(A.tables = crc_device_tables())) return -1;
     {
-        std::lock_guard<std::mutex> lock(mu);
-        if (host_tables.empty()) {
-            uint32_t p = 0x00800000u;   // x^8
-            for (int j = 0; j < 40; j++, p = multmodp(p, p)) pow2[j] = p;
-            for (int i = 0; i < 256; i++) blk[i] = x8n_modp(64ull * i);
-            for (int i = 0; i < 64; i++) bytep[i] = x8n_modp((unsigned long long)i);
-            for (int i = 0; i < 256; i++) stripep[i] = x8n_modp((unsigned long long)i << 14);
-            host_tables.resize(2048);
-            for (uint32_t i = 0; i < 256; i++) {
-                uint32_t c = i;
-                for (int j = 0; j < 8; j++) c = (c & 1u) ? (c >> 1) ^ kPoly : c >> 1;
-                host_tables[i] = c;
-            }
-            for (uint32_t i = 0; i < 256; i++) {
-                uint32_t c = host_tables[i];
-                for (int k = 1; k < 4; k++) {
-                    c = host_tables[c & 0xFFu] ^ (c >> 8);
-                    host_tables[k * 256 + i] = c;
-                }
-            }
-            const uint32_t skipm = x8n_modp(kStripe - kBlk);
-            for (int k = 0; k < 4; k++)
-                for (uint32_t i = 0; i < 256; i++) host_tables[1024 + k * 256 + i] = multmodp(skipm, i << (8 * k));
-        }
-        if (!dev_tables.count(dev)) {
-            unsigned int *d = nullptr;
-            if (hipMalloc(&d, host_tables.size() * 4) != hipSuccess) return -1;
-            if (hipMemcpy(d, host_tables.data(), host_tables.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
-            dev_tables[dev] = d;
-        }
-        A.tables = dev_tables[dev];
+        std::lock_guard<std::mutex> lock(crc_mu);
+        memcpy(A.x8pow2, crc_pow2, sizeof crc_pow2);
+        memcpy(A.blk_pow, crc_host_tables.data() + kCrcTabBlkPow, sizeof A.blk_pow);
+        memcpy(A.byte_pow, crc_host_tables.data() + kCrcTabBytePow, sizeof A.byte_pow);
+        memcpy(A.stripe_pow, crc_stripep, sizeof crc_stripep);
     }
-    memcpy(A.x8pow2, pow2, sizeof pow2);
-    memcpy(A.blk_pow, blk, sizeof blk);
-    memcpy(A.byte_pow, bytep, sizeof bytep);
-    memcpy(A.stripe_pow, stripep, sizeof stripep);
     if (A.n_clips < 64 && A.max_frames && !getenv("FLO_FINISH_TWO_KERNELS")) {
         A.toc_chunk = kFinThreads;
         A.mode = 1;
@@ -402,7 +361,8 @@ int launch_finish_files(FinishArgs A, hipStream_t s) {
         return e2 == hipSuccess ? 0 : (int)e2;
     }
     A.mode = 0;
-    hipLaunchKernelGGL(crc_slices_kernel, dim3((unsigned)A.n_clips, A.parts), dim3(kFinThreads), 0, s, A);
+    if (A.n_clips < 64 || !A.crc_ready)   // (with crc_ready, finish_files_kernel<256> computes what the encode's tail left)
+        hipLaunchKernelGGL(crc_slices_kernel, dim3((unsigned)A.n_clips, A.parts), dim3(kFinThreads), 0, s, A);
     if (A.n_clips < 64) {
         // a few long clips: the TOC in chunks of 1024 frames (one entry per thread)
         A.toc_chunk = 1024;

@@ -23,6 +23,9 @@ struct FinishArgs {
     unsigned int *crc_out;                  // [n_clips] CRC32 of each DATA chunk (also in the header)
     unsigned int parts;                     // slices per clip for the CRC (1..128): few long clips still fill the chip
     unsigned int *part_reg;                 // [n_clips * parts] scratch: CRC register of every slice
+    const unsigned int *crc_ready;          // null, or [n_clips]: == epoch where the encode already left the clip's slice
+                                            // registers in part_reg (many-clips batches; the others are computed here)
+    unsigned int epoch;
     unsigned int max_frames;                // frames of the longest clip (0 = unknown: one workgroup writes a clip's whole TOC)
     unsigned int toc_chunk;                 // set by launch_finish_files: frames per TOC workgroup (0 = all)
     unsigned int mode;                      // set by launch_finish_files: 0 TOC + CRC + header, 1 the TOC (+ total_samples) only, 2 CRC + header only
@@ -31,10 +34,12 @@ struct FinishArgs {
     unsigned int blk_pow[256];              // x^(8 * 64 * i)
     unsigned int byte_pow[64];              // x^(8 * i)
     unsigned int stripe_pow[256];           // x^(8 * 16384 * i)
-    const unsigned int *tables;             // device: tab[4][256] byte tables, then skip[4][256] (times x^(8 * 16320))
+    const unsigned int *tables;             // set by launch_finish_files: crc_device_tables()
 };
 
 int launch_finish_files(FinishArgs A, hipStream_t s);
+// the current device's CRC table (crc_device.hpp layout), made on first use; null on failure
+const unsigned int *crc_device_tables();
 // Location table of a batch's finished files (flo_dist_table_*): row = [0] n | [1 .. max] sizes | [1 + max .. 2 max] offsets
 // | [1 + 2 max .. 3 max] CRC32 of DATA. Sizes and offsets are in the row already; this fills the CRC column from the
 // headers of the files at base + offset (byte 26).

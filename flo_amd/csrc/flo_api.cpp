@@ -282,6 +282,13 @@ struct flo_batch {
     uint32_t *d_frame_size = nullptr;
     uint64_t *d_clip_bytes = nullptr;
     uint32_t *d_crc = nullptr, *d_part = nullptr, *d_next = nullptr;
+    // stereo chain encode of many clips (form 5): the CRC in the launch's idle tail. d_next holds two sets of counters
+    // (claim, done-queue tail and head), used by launches of alternating epoch parity; each launch zeroes the other set
+    uint32_t *d_crc_ready = nullptr;          // [n_clips] epoch of the launch whose tail left the clip's slice registers
+    unsigned long long *d_done_q = nullptr;   // [n_clips] done queue entries (epoch << 32 | clip)
+    uint32_t epoch = 0;                       // of the last form-5 launch; the next is epoch + 1 (never 0)
+    uint64_t *pin_sizes = nullptr;            // pinned [n_clips]: DATA sizes, copied behind finish_files (sizes_queued)
+    bool sizes_queued = false;
     float *d_bmax = nullptr;   // band maxima of every frame (frame-parallel form: pass 1 -> pass 2)
     void *d_coef = nullptr;    // ... and, for a few long stereo clips, every frame's coefficients (8 KB per frame)
     float *d_at = nullptr, *d_sprev = nullptr;
@@ -314,11 +321,13 @@ extern "C" void flo_batch_destroy(flo_batch *b) {
     hipSetDevice(b->ctx->device);
     hipStreamSynchronize(b->ctx->stream);
     void *ptrs[] = {b->d_pcm, b->d_plan, b->d_hops, b->d_out, b->d_frame_size, b->d_clip_bytes, b->d_crc, b->d_part, b->d_at,
-                    b->d_sprev, b->d_slots, b->d_frame_off, b->d_dbg_coeffs, b->d_dbg_q, b->d_dbg_sfw, b->d_pack_plan, b->d_next, b->d_bmax, b->d_coef};
+                    b->d_sprev, b->d_slots, b->d_frame_off, b->d_dbg_coeffs, b->d_dbg_q, b->d_dbg_sfw, b->d_pack_plan, b->d_next, b->d_bmax, b->d_coef,
+                    b->d_crc_ready, b->d_done_q};
     for (void *p : ptrs)
         if (p) pool_free(p);
     if (b->ev_pack_plan) hipEventDestroy(b->ev_pack_plan);
     if (b->pin_plan) stager_pinned_put(b->ctx->stager, b->pin_plan);
+    if (b->pin_sizes) stager_pinned_put(b->ctx->stager, b->pin_sizes);
     if (b->ll) lossless_plan_destroy(b->ll);
     delete b;
 }
@@ -423,7 +432,8 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
         BCHK(pool_alloc(&b->d_frame_size, (b->total_frames + 1) * 4));
         BCHK(pool_alloc(&b->d_clip_bytes, (n_clips + 1) * 8));
         BCHK(pool_alloc(&b->d_crc, (n_clips + 1) * 4));
-        BCHK(pool_alloc(&b->d_next, 16));
+        BCHK(pool_alloc(&b->d_next, 32));
+        BCHK(hipMemsetAsync(b->d_next, 0, 32, c->stream));   // once: every launch then zeroes its successor's counters
         BCHK(pool_alloc(&b->d_part, (n_clips * finish_parts_for(n_clips) + 1) * 4));
         if (n_clips) {
             // from pinned memory on the context's stream, in front of everything that will use them: a synchronous (or
@@ -591,13 +601,40 @@ static int batch_encode_launch(flo_batch *b, int which) {
     int rc;
     if (which == 3 || which == 4) which = 5;   // (earlier rounds' stereo chain forms: retired, the numbers stay valid)
     if (which == 5 && (b->exact || b->ch != 2)) which = 1;   // the exact-threshold yardstick and mono live in the one-wave-per-channel form
+    b->sizes_queued = false;
+    bool tail_crc = false;   // finish_files takes the CRC slices this launch's tail computed
     if (which == 5) {   // stereo: one lock-step transform wave + one quantiser-and-packer wave per clip
 #ifdef FLO_STAMPS
         if (!b->d_stamps) HIPCHK(c, pool_alloc(&b->d_stamps, b->n_clips * b->ch * 16 * 8));
 #endif
         LossyArgs A = make_args(b);
-        HIPCHK(c, hipMemsetAsync(b->d_next, 0, 4, c->stream));   // the batch-wide clip counter of the persistent workgroups
+        // The batch-wide counters of the persistent workgroups live in the set of this launch's epoch parity, zeroed by
+        // the launch before (or at creation). Many clips: the CRC in the launch's idle tail (lossy_kernels.hip,
+        // tail_crc); FLO_TAIL_CRC=0 leaves every CRC to finish_files (the tests compare both).
+        const uint32_t epoch = b->epoch + 1 ? b->epoch + 1 : 2;   // (never 0; the parity alternates)
+        A.next_clip = b->d_next + 4 * (epoch & 1u);
+        A.clear_next = b->d_next + 4 * ((epoch & 1u) ^ 1u);
+        A.epoch = epoch;
+        if (b->n_clips >= 64) {
+            const size_t n = b->n_clips;
+            if (!b->d_crc_ready) {
+                HIPCHK(c, pool_alloc(&b->d_crc_ready, n * 4));
+                HIPCHK(c, hipMemsetAsync(b->d_crc_ready, 0, n * 4, c->stream));
+            }
+            if (!b->d_done_q) {
+                HIPCHK(c, pool_alloc(&b->d_done_q, n * 8));
+                HIPCHK(c, hipMemsetAsync(b->d_done_q, 0, n * 8, c->stream));
+            }
+            if (!(A.crc_tab = crc_device_tables())) return fail(c, FLO_ERR_DEVICE, "CRC tables");
+            const char *tc = getenv("FLO_TAIL_CRC");
+            if (!(tc && tc[0] == '0')) A.crc_ready = b->d_crc_ready;
+            A.done_q = b->d_done_q;
+            A.part_reg = b->d_part;
+            A.parts = finish_parts_for(n);
+            tail_crc = true;
+        }
         rc = timed_launch(c, "lossy_chain2q", [&] { return launch_lossy_chain2q(A, c->stream); });
+        if (rc == FLO_OK) b->epoch = epoch;   // (a launch that did not run zeroed nothing: its epoch is used again)
     } else if (which == 1) {
 #ifdef FLO_STAMPS
         if (!b->d_stamps) HIPCHK(c, pool_alloc(&b->d_stamps, b->n_clips * b->ch * 16 * 8));
@@ -634,9 +671,22 @@ static int batch_encode_launch(flo_batch *b, int which) {
     F.crc_out = b->d_crc;
     F.parts = finish_parts_for(b->n_clips);
     F.part_reg = b->d_part;
+    if (tail_crc) {
+        F.crc_ready = b->d_crc_ready;
+        F.epoch = b->epoch;
+    }
     F.max_frames = 0;
     for (auto h : b->hops) F.max_frames = h > F.max_frames ? h : F.max_frames;
-    return timed_launch(c, "finish_files", [&] { return launch_finish_files(F, c->stream); });
+    if ((rc = timed_launch(c, "finish_files", [&] { return launch_finish_files(F, c->stream); })) != FLO_OK) return rc;
+    if (tail_crc) {   // the sizes come back behind finish_files: flo_batch_sync waits once and copies nothing from the device
+        if (!b->pin_sizes) {
+            std::string perr;
+            if (!(b->pin_sizes = (uint64_t *)stager_pinned_get(c->stager, b->n_clips * 8, perr))) return fail(c, FLO_ERR_NOMEM, perr);
+        }
+        HIPCHK(c, hipMemcpyAsync(b->pin_sizes, b->d_clip_bytes, b->n_clips * 8, hipMemcpyDeviceToHost, c->stream));
+        b->sizes_queued = true;
+    }
+    return FLO_OK;
 }
 
 static int batch_sync_impl(flo_batch *b, hipEvent_t done);
@@ -658,7 +708,9 @@ static int batch_sync_impl(flo_batch *b, hipEvent_t done) {
             // fetched on demand by the few host paths that want them
             b->h_clip_bytes.assign(b->n_clips, 0);
             b->h_frame_size.clear();
-            if (b->n_clips && b->total_frames) {
+            if (b->sizes_queued) {   // (copied behind finish_files, on the stream this call has waited for)
+                memcpy(b->h_clip_bytes.data(), b->pin_sizes, b->n_clips * 8);
+            } else if (b->n_clips && b->total_frames) {
                 if (done && c->down_stream) {   // pipeline: other streams are busy, a synchronous copy would queue behind them
                     HIPCHK(c, hipMemcpyAsync(b->h_clip_bytes.data(), b->d_clip_bytes, b->n_clips * 8, hipMemcpyDeviceToHost, c->down_stream));
                     HIPCHK(c, hipStreamSynchronize(c->down_stream));
@@ -668,6 +720,15 @@ static int batch_sync_impl(flo_batch *b, hipEvent_t done) {
             }
             for (size_t i = 0; i < b->n_clips; i++)
                 if (b->h_clip_bytes[i] > b->out_cap[i]) return fail(c, FLO_ERR_DEVICE, "bitstream overran its buffer");
+#ifdef FLO_TAIL_STATS   // diagnostic builds: how many clips' CRC the chain encode's tail computed, how many finish_files did
+            if (b->sizes_queued) {
+                std::vector<uint32_t> ready(b->n_clips);
+                HIPCHK(c, hipMemcpy(ready.data(), b->d_crc_ready, b->n_clips * 4, hipMemcpyDeviceToHost));
+                size_t tail = 0;
+                for (uint32_t v : ready) tail += v == b->epoch;
+                fprintf(stderr, "[tail] clips %zu: CRC in the encode's tail %zu, in finish_files %zu\n", b->n_clips, tail, b->n_clips - tail);
+            }
+#endif
 #ifdef FLO_STAMPS
             if (b->d_stamps) {
                 std::vector<unsigned long long> st(b->n_clips * b->ch * 16);

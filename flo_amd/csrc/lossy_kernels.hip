@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "crc_device.hpp"
 #include "lossy_device.hpp"
 #include "lossy_kernels.hpp"
 #include "../../include/flo_synth.h"
@@ -491,6 +492,78 @@ constexpr int kPackBytesHotT = kPackRowsHotT * 64 * 16;
 #ifndef FLO_PSLEEP
 #define FLO_PSLEEP 1
 #endif
+static_assert(sizeof(Clip2qLds::u) >= 8 * 256 * sizeof(uint32_t), "the tail's CRC tables fit the exchange buffer");
+
+// ---------------------------------------------------------------------------------------------- CRC in the idle tail
+// Once the batch is exhausted, pairs stop claiming clips one after the other while the rest still encode: the last
+// 0.4-0.5 ms of a launch leave CUs idle while thousands of finished DATA chunks sit in HBM. A packer wave whose claim
+// fails computes the CRC slice registers of its own last clip (its bytes were just written, by this wave), then of
+// finished clips it takes from the done queue, until the queue looks empty. Nothing ever waits: an entry claimed before
+// it is ready, like a clip no worker reached, is left to finish_files_kernel<256>, which computes every clip whose
+// crc_ready is not this launch's epoch. So the files never depend on how far the tail got.
+//
+// Publish a finished clip (its DATA and clip_bytes stores by this wave) to the done queue: agent-scope release
+// (cdna_hip_programming.md §6 Guideline 16; the asm wait behind the fence is its Pitfall 12), then the slot, then the
+// entry, whose epoch tag is its ready word. Once per clip, in front of the next clip's frames.
+__device__ __forceinline__ void tail_publish(const LossyArgs &A, const unsigned clip, const int lane) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned slot = __hip_atomic_fetch_add(A.next_clip + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (slot < (unsigned)A.n_clips)
+            __hip_atomic_store(A.done_q + slot, ((unsigned long long)A.epoch << 32) | clip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// The tail worker (one packer wave, at the lowest priority so that the clips still encoding keep their issue slots).
+// tabs: 8 KB of this pair's LDS that nobody uses any more (the transform wave only reads clip_seq / clip_cur from here
+// on). clip / total: the clip this wave finished last (~0u: none), then each clip taken from the queue.
+__device__ __forceinline__ void tail_crc(const LossyArgs &A, uint32_t *tabs, const int lane, unsigned clip,
+                                         unsigned long long total) {
+    __builtin_amdgcn_s_setprio(0);
+    const unsigned *blk_pow = A.crc_tab + kCrcTabBlkPow, *byte_pow = A.crc_tab + kCrcTabBytePow;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    bool loaded = false;
+    for (;;) {
+        if (clip != ~0u) {
+            if (!loaded) {   // (the byte tables and the one-wave skip table, once)
+                loaded = true;
+                for (int i = lane; i < 1024; i += 64) {
+                    tabs[i] = A.crc_tab[kCrcTabByte + i];
+                    tabs[1024 + i] = A.crc_tab[kCrcTabSkip64 + i];
+                }
+                wave_sync();
+            }
+            const uint32_t(*tab)[256] = reinterpret_cast<const uint32_t(*)[256]>(tabs);
+            const uint32_t(*skip)[256] = reinterpret_cast<const uint32_t(*)[256]>(tabs + 1024);
+            const uint8_t *data = A.out + A.out_off[clip];
+            for (unsigned p = 0; p < A.parts; p++) {
+                unsigned long long beg, len;
+                crc_slice_range(total, A.parts, p, beg, len);
+                const uint32_t r = crc_slice_reg<64>(tab, skip, blk_pow, byte_pow, data + beg, len, (unsigned)lane, nullptr);
+                if (lane == 0) A.part_reg[(unsigned long long)clip * A.parts + p] = r;
+            }
+            if (lane == 0) A.crc_ready[clip] = A.epoch;   // read by finish_files_kernel, behind the launch boundary
+        }
+        unsigned long long e = 0;
+        if (lane == 0) {
+            const unsigned tail = __hip_atomic_load(A.next_clip + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned head = __hip_atomic_load(A.next_clip + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (head < tail) {
+                const unsigned h = __hip_atomic_fetch_add(A.next_clip + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (h < (unsigned)A.n_clips) e = __hip_atomic_load(A.done_q + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        const unsigned tag = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(e >> 32));
+        clip = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)e);
+        if (tag != A.epoch || clip >= (unsigned)A.n_clips) return;   // looks empty, or not ready yet: finish_files does it
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        total = __hip_atomic_load(A.clip_bytes + clip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 template <bool COEFFS, uint32_t DIRTY, bool DBG>
 __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArgs A, int clips_per_wg) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
@@ -506,6 +579,8 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             c0.consumed = 0;
             c0.clip_seq = 0;
         }
+        if (A.clear_next && blockIdx.x == 0 && tid == 0)   // the next launch's counters (the other parity: no one uses them now)
+            A.clear_next[0] = A.clear_next[1] = A.clear_next[2] = 0;
     }
     __syncthreads();
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -546,12 +621,21 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
         const uint32_t tab_a = (uint32_t)(uintptr_t)cs.packtab;
         v4f cf[8];
         bool have = false;   // cf holds the next frame's coefficients (taken before the previous frame's flush)
+        unsigned done_clip = ~0u;          // the clip finished last (tail CRC: published once the next claim succeeds)
+        unsigned long long done_bytes = 0;
         for (;;) {
             unsigned got = 0;
             if (lane == 0) got = atomicAdd(A.next_clip, 1u);
             const unsigned clip = (unsigned)__builtin_amdgcn_readfirstlane((int)got);
             if (lane == 0) cs.clip_cur = clip;
             set_counter(&cs.clip_seq, ++seq);
+            if (A.crc_ready) {   // (the transform wave already has its next clip: the release overlaps its first frame)
+                if (clip >= (unsigned)A.n_clips) {
+                    tail_crc(A, reinterpret_cast<uint32_t *>(&cs.u), lane, done_clip, done_bytes);
+                    return;
+                }
+                if (done_clip != ~0u) tail_publish(A, done_clip, lane);
+            }
             if (clip >= (unsigned)A.n_clips) return;
             const unsigned hops = A.clip_hops[clip];
             const unsigned long long frame0 = A.clip_frame0[clip];
@@ -713,6 +797,8 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             }
             if (lane < (int)pend) gout[written + lane] = (uint8_t)tailb;
             if (lane == 0) A.clip_bytes[clip] = written + pend;
+            done_clip = clip;
+            done_bytes = written + pend;
 #ifdef FLO_STAMPS
             if (A.dbg_stamps && lane == 0) {
                 st_sum[13] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) |

@@ -41,7 +41,18 @@ struct LossyArgs {
     const float *in_coeffs;                  // when set: skip the transform, quantise these spectra
     unsigned long long *dbg_stamps;          // diagnostic builds (FLO_STAMPS): per-wave phase cycle sums [wave][16]
     int exact;                               // re-decide near-threshold coefficients with the reference's dB expression
-    unsigned int *next_clip;                 // lock-step stereo form: batch-wide counter of claimed clips (zero at launch)
+    unsigned int *next_clip;                 // lock-step stereo form: batch-wide counter of claimed clips (zero at launch), then
+                                             // the done queue's tail and head counters (next_clip[1], [2]; zero at launch)
+    // lock-step stereo form, CRC in the launch's idle tail (crc_ready null: none): a packer wave that finds the batch
+    // exhausted computes the CRC slice registers (FinishArgs::part_reg layout) of its last clip and of finished clips
+    // it takes from the done queue, and marks them crc_ready[clip] = epoch
+    unsigned int *clear_next;                // zeroed at launch: the counters of the launch after this one (other parity)
+    unsigned long long *done_q;              // [n_clips] queue entries: epoch << 32 | clip
+    unsigned int *crc_ready;                 // [n_clips]
+    unsigned int *part_reg;                  // [n_clips * parts]
+    unsigned int parts;                      // slices per clip (finish_parts_for)
+    unsigned int epoch;                      // of this launch, never 0
+    const unsigned int *crc_tab;             // crc_device_tables()
     int n_cus;                               // compute units of the device (persistent workgroups)
 };
 
