@@ -67,6 +67,17 @@ struct WaveLds {
     float band_s[CH][32];              // per band: masking level s in dB (exact re-check only)
 };
 
+// One lane's whole 16-byte entry of a pack row, as ONE 16-byte load (in LDS: ds_read_b128, conflict-free, 4 array cycles).
+// Left to itself the compiler narrows a row of which the code uses some dwords into ds_read_b32 / b64 pieces, or splits
+// it into a ds_read2_b64; at a 16-byte lane stride those pieces hit 2- to 4-way bank conflicts and together take up to
+// six times the array cycles of the whole row (diag/lds_model.py).
+__device__ __forceinline__ float4 pack_row(const float4 *p) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    v4f v = *reinterpret_cast<const v4f *>(p);
+    asm("" : "+v"(v));   // (one register quad: all four dwords are "used", so the load stays whole)
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 // The same value behind an optimisation barrier: inside the frame loop every lane-derived address is then
 // recomputed per frame (a few integer ops) instead of being hoisted into dozens of loop-invariant registers.
@@ -624,12 +635,13 @@ __device__ __forceinline__ void load_half_fast_2(const int lane, const float *__
 
 __device__ __forceinline__ void fold_2(const int lane, const v2f (&ae)[8], const v2f (&ao)[8], const v2f (&be)[8], const v2f (&bo)[8],
                                        v2f (&zr)[8], v2f (&zi)[8], const LossyDevTables &T) {
+    float4 t4;   // twiddle row r >> 1: read at r even, its .zw serve r odd
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const float4 ww = T.pack[(kRowWin + r) * 64 + lane];
         const v2f wae = splat2(ww.x), wao = splat2(ww.y), wbe = splat2(ww.z);
         const v2f whi = {ww.z, ww.w};   // (ww.w enters through fma2_na_hi_nc)
-        const float4 t4 = T.pack[(kRowTw + (r >> 1)) * 64 + lane];
+        if (!(r & 1)) t4 = pack_row(&T.pack[(kRowTw + (r >> 1)) * 64 + lane]);
         const v2f wx = splat2((r & 1) ? t4.z : t4.x);
         const v2f thi = {t4.z, t4.w};
         v2f re, im;
@@ -659,9 +671,10 @@ __device__ __forceinline__ void post_rotate_transpose_2(const int lane, const v2
     const int pl = 2 * lane + 2 * (lane >> 3);
     float2 *const w0 = c2 + pl;
     float2 *const w1 = c2 + (1149 - 7 * 144) - pl;
+    float4 t4;   // twiddle row r >> 1: read at r even, its .zw serve r odd (the stores in between would force a re-read)
 #pragma unroll
     for (int r = 0; r < 8; r++) {
-        const float4 t4 = T.pack[(kRowTw + (r >> 1)) * 64 + lane];
+        if (!(r & 1)) t4 = pack_row(&T.pack[(kRowTw + (r >> 1)) * 64 + lane]);
         const v2f wx = splat2((r & 1) ? t4.z : t4.x);
         v2f R, I;
         if (r & 1) {   // (the row's second pair: its .w through the op_sel forms, see fma2_na_hi_nc)
@@ -1107,8 +1120,8 @@ __device__ __forceinline__ void band_stats_2(const int lane, const v2f (&c)[16],
     v4f am = {0.f, 0.f, 0.f, 0.f};   // running (sum left, sum right, max left, max right): one register quad, stored as it is
 #pragma unroll
     for (int g = 0; g < 4; g++) {
-        const float4 keep = T.pack[(kRowKeep + g) * 64 + lane];
-        const float4 dsto = T.pack[(kRowDst + g) * 64 + lane];
+        const float4 keep = pack_row(&T.pack[(kRowKeep + g) * 64 + lane]);
+        const float4 dsto = pack_row(&T.pack[(kRowDst + g) * 64 + lane]);
         const float kp[4] = {keep.x, keep.y, keep.z, keep.w};
         const uint32_t dv[4] = {__float_as_uint(dsto.x), __float_as_uint(dsto.y), __float_as_uint(dsto.z), __float_as_uint(dsto.w)};
 #pragma unroll

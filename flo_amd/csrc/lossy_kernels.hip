@@ -897,7 +897,9 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             const uint32_t consumed_early = peek_counter(&cs.consumed);
             // the masking pass's constants, fetched ahead of the exchange it runs behind (it must not wait for LDS there)
             const float4 sd0 = T.pack[kRowS10 * 64], sd1 = T.pack[kRowS10 * 64 + 1];
-            const float rcount = T.pack[kRowLane * 64 + ln].z;   // (the row holds band (lane & 31)'s value on every lane)
+            // (band (lane & 31)'s 1 / bins, from the copy in row kRowS10: a dword per lane, contiguous; kRowLane's .z has a
+            // 16-byte lane stride, a 4-way bank conflict)
+            const float rcount = reinterpret_cast<const float *>(T.pack + kRowS10 * 64)[64 + ln];
             v2f c[16];
             if (COEFFS) {
 #pragma unroll
@@ -979,7 +981,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
         if (!COEFFS && hops) {   // the last frame's masking pass has no FFT to hide behind
             const int ln = lane_id_opaque();
             const float4 sd0 = T.pack[kRowS10 * 64], sd1 = T.pack[kRowS10 * 64 + 1];
-            mask_publish(ln, fbase + hops - 1u, hops - 1u, pend_e, pend_m, T.pack[kRowLane * 64 + ln].z, sd0, sd1);
+            mask_publish(ln, fbase + hops - 1u, hops - 1u, pend_e, pend_m, reinterpret_cast<const float *>(T.pack + kRowS10 * 64)[64 + ln], sd0, sd1);
         }
 #ifdef FLO_STAMPS
         if (A.dbg_stamps && lane == 0) {   // [13]: where the wave ran (HW_ID, XCC_ID, clip slot): diag/stamps_clips.py groups the records by it

@@ -14,7 +14,8 @@ constexpr int kRowLane = 20;      // 1 row : (lane_bnd, lane_slot0, 1 / bins of 
 constexpr int kRowKeep = 21;      // 4 rows: band-statistics restart multipliers (0.0 behind a band boundary, else 1.0)
 constexpr int kRowDst = 25;       // 4 rows: byte offset of the slot each running (sum, max) is stored to (segment slot or trash)
 constexpr int kRowLst = 29;       // 3 rows: byte offsets of the first 12 slots this band lane adds (zero slot when exhausted)
-constexpr int kRowS10 = 32;       // 1 row : floats 0..23 = s10d[1..24] (spreading level per band distance), read uniformly
+constexpr int kRowS10 = 32;       // 1 row : floats 0..23 = s10d[1..24] (spreading level per band distance), read uniformly;
+                                  //         floats 64..127 = kRowLane .z of lanes 0..63, contiguous (conflict-free dword reads)
 constexpr int kPackRowsHotT = 33;
 constexpr int kRowAth = 33;       // 4 rows: ATH amplitude thresholds of coefficients 16 lane .. 16 lane + 15
 constexpr int kRowBo = 37;        // 4 rows: byte offset (8 x band) of each of the lane's 16 coefficients

@@ -113,7 +113,8 @@ void build_lossy_tables(uint32_t sample_rate, float quality, LossyTablesHost &t)
     t.pack.assign((size_t)kPackRows * 64 * 4, 0.0f);
     t.pack_ext.assign(2 * 64 * 4, 0.0f);
     auto P = [&](int row, int lane, int i) -> float & { return t.pack[((size_t)row * 64 + lane) * 4 + i]; };
-    // row kRowS10 is not per lane: its first 24 floats are s10d[1..24], read uniformly by every lane
+    // row kRowS10 is not per lane: its first 24 floats are s10d[1..24], read uniformly by every lane; floats 64..127 hold
+    // kRowLane's 1 / bins of lane 0..63 (filled below)
     for (int d = 1; d < kNumBands; d++) P(kRowS10, (d - 1) / 4, (d - 1) % 4) = t.s10d[d];
     for (int lane = 0; lane < 64; lane++) {
         for (int r = 0; r < 8; r++) {
@@ -224,6 +225,7 @@ void build_lossy_tables(uint32_t sample_rate, float quality, LossyTablesHost &t)
         PU(kRowLane, lane, 0, t.lane_bnd[lane]);
         PU(kRowLane, lane, 1, t.lane_slot0[lane]);
         PU(kRowLane, lane, 2, rc);
+        PU(kRowS10, 16 + lane / 4, lane % 4, rc);   // the same, as dword 64 + lane of row kRowS10 (one conflict-free ds_read_b32)
         PU(kRowLane, lane, 3, bs0 | (bs1 << 16));
     }
 }
