@@ -7,3 +7,4 @@ from ._native import FloError, MODE_LOSSLESS, MODE_LOSSY  # noqa: F401
 from .api import (Batch, Context, Decoder, EncodedFrame, Encoder, LossyEncoder, QualityPreset, StreamingEncoder,  # noqa: F401
                   TransformEncoder, default_context, decode, encode, encode_lossy, encode_with_bitrate, probe_container)
 from .api import Corpus, SeekResult, TocEntry, decode_frame_at, get_toc, seek_to_time  # noqa: F401
+from .api import DecoderState, StreamingAudioInfo, StreamingDecoder, decode_streams  # noqa: F401

@@ -33,6 +33,9 @@ EXPORTS = [
     "flo_get_toc", "flo_seek_to_time", "flo_decode_frame_at",
     "flo_corpus_create", "flo_corpus_destroy", "flo_corpus_format", "flo_corpus_file_frames", "flo_corpus_decode_windows",
     "flo_corpus_sync",
+    "flo_sdec_create", "flo_sdec_destroy", "flo_sdec_attach", "flo_sdec_last_error", "flo_sdec_feed", "flo_sdec_state",
+    "flo_sdec_info", "flo_sdec_frames_available", "flo_sdec_available_frames", "flo_sdec_current_frame_index",
+    "flo_sdec_buffered_bytes", "flo_sdec_next_frame", "flo_sdec_decode_available", "flo_sdec_reset", "flo_sdec_decode_ready",
 ]
 
 
@@ -60,6 +63,11 @@ class TocEntryC(C.Structure):
 class SeekResultC(C.Structure):
     _fields_ = [("frame_index", C.c_uint32), ("timestamp_ms", C.c_uint32), ("byte_offset", C.c_uint64), ("sample_offset", C.c_uint32),
                 ("next_timestamp_ms", C.c_uint32)]
+
+
+class SdecInfoC(C.Structure):
+    _fields_ = [("sample_rate", C.c_uint32), ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("is_lossy", C.c_uint8),
+                ("pad", C.c_uint8), ("total_samples", C.c_uint64)]
 
 
 class FloError(RuntimeError):
@@ -171,5 +179,22 @@ def lib():
     L.flo_corpus_file_frames.argtypes = [vp, sz, C.POINTER(C.c_uint64)]
     L.flo_corpus_decode_windows.argtypes = [vp, sz, vp, vp, C.c_uint32, vp, sz, vp]
     L.flo_corpus_sync.argtypes = [vp]
+    L.flo_sdec_create.argtypes = [vp, C.POINTER(vp)]
+    L.flo_sdec_destroy.argtypes = [vp]
+    L.flo_sdec_destroy.restype = None
+    L.flo_sdec_attach.argtypes = [vp, vp]
+    L.flo_sdec_last_error.argtypes = [vp]
+    L.flo_sdec_last_error.restype = C.c_char_p
+    L.flo_sdec_feed.argtypes = [vp, C.c_char_p, sz, C.POINTER(C.c_int)]
+    L.flo_sdec_state.argtypes = [vp]
+    L.flo_sdec_info.argtypes = [vp, C.POINTER(SdecInfoC)]
+    for f in ("flo_sdec_frames_available", "flo_sdec_available_frames", "flo_sdec_current_frame_index", "flo_sdec_buffered_bytes"):
+        getattr(L, f).argtypes = [vp]
+        getattr(L, f).restype = sz
+    L.flo_sdec_next_frame.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.flo_sdec_decode_available.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.flo_sdec_reset.argtypes = [vp]
+    L.flo_sdec_reset.restype = None
+    L.flo_sdec_decode_ready.argtypes = [vp, sz, vp, C.c_uint32, vp, sz, vp, vp, vp]
     _LIB = L
     return L

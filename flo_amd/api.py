@@ -710,6 +710,179 @@ class Corpus:
             pass
 
 
+# -- streaming decoder (libflo/src/streaming/decoder.rs, types.rs) ---------------------------------------------------
+class DecoderState(enum.IntEnum):
+    """streaming/types.rs DecoderState"""
+    WaitingForHeader = 0
+    WaitingForToc = 1
+    Ready = 2
+    Finished = 3
+    Error = 4
+
+
+class StreamingAudioInfo(NamedTuple):
+    """streaming/types.rs StreamingAudioInfo"""
+    sample_rate: int
+    channels: int
+    bit_depth: int
+    total_samples: int
+    is_lossy: bool
+
+    def duration_secs(self) -> float:
+        return self.total_samples / self.sample_rate if self.sample_rate else float("inf") if self.total_samples else float("nan")
+
+    def total_samples_per_channel(self) -> int:
+        return self.total_samples
+
+
+class StreamingDecoder:
+    """StreamingDecoder (streaming/decoder.rs) on flo_sdec: feed bytes as they arrive, take each frame once it is complete.
+    With ctx=None the default context is taken at the first decode only: feeding and the counters need no device."""
+
+    def __init__(self, ctx: Context = None):
+        self._L = _native.lib()
+        self._ctx = ctx
+        h = C.c_void_p()
+        if self._L.flo_sdec_create(ctx._h if ctx else None, C.byref(h)) != 0:
+            raise FloError("flo_sdec_create failed")
+        self._h = h
+        if ctx:
+            ctx._batches.add(self)   # its device state goes before its context
+
+    def _err(self):
+        return self._L.flo_sdec_last_error(self._h).decode()
+
+    def _attach(self) -> Context:
+        if self._ctx is None:
+            self._ctx = default_context()
+            if self._L.flo_sdec_attach(self._h, self._ctx._h) != 0:
+                raise FloError("the decoder belongs to another context")
+            self._ctx._batches.add(self)
+        return self._ctx
+
+    def feed(self, data) -> bool:
+        """feed (:70-78): True if new frames are available; FloError on bad magic (the state is then Error)"""
+        data = bytes(data)
+        nf = C.c_int()
+        if self._L.flo_sdec_feed(self._h, data, len(data), C.byref(nf)) != 0:
+            raise FloError(self._err())
+        return bool(nf.value)
+
+    def state(self) -> DecoderState:
+        return DecoderState(self._L.flo_sdec_state(self._h))
+
+    def info(self):
+        """StreamingAudioInfo once the header is parsed, else None"""
+        i = _native.SdecInfoC()
+        if self._L.flo_sdec_info(self._h, C.byref(i)) != 0:
+            return None
+        return StreamingAudioInfo(i.sample_rate, i.channels, i.bit_depth, i.total_samples, bool(i.is_lossy))
+
+    def frames_available(self) -> int:
+        return int(self._L.flo_sdec_frames_available(self._h))
+
+    def available_frames(self) -> int:
+        return int(self._L.flo_sdec_available_frames(self._h))
+
+    def current_frame_index(self) -> int:
+        return int(self._L.flo_sdec_current_frame_index(self._h))
+
+    def buffered_bytes(self) -> int:
+        return int(self._L.flo_sdec_buffered_bytes(self._h))
+
+    def next_frame(self):
+        """next_frame (:81-112): one frame's interleaved f32 samples (possibly empty), or None when no frame is ready"""
+        if self.state() != DecoderState.Ready:
+            return None
+        self._attach()
+        p, n = C.c_void_p(), C.c_size_t()
+        rc = self._L.flo_sdec_next_frame(self._h, C.byref(p), C.byref(n))
+        if rc < 0:
+            raise FloError(self._err())
+        if rc == 0:
+            return None
+        if not n.value:
+            return np.zeros(0, np.float32)
+        arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n.value,)).copy()
+        self._L.flo_free(p)
+        return arr
+
+    def decode_available(self):
+        """decode_available (:114-122): the whole buffer decoded from frame 0; the state becomes Finished"""
+        if self.state() != DecoderState.Ready:
+            return np.zeros(0, np.float32)
+        self._attach()
+        p, n = C.c_void_p(), C.c_size_t()
+        if self._L.flo_sdec_decode_available(self._h, C.byref(p), C.byref(n)) != 0:
+            raise FloError(self._err())
+        if not n.value:
+            if p.value:
+                self._L.flo_free(p)
+            return np.zeros(0, np.float32)
+        arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n.value,)).copy()
+        self._L.flo_free(p)
+        return arr
+
+    def reset(self):
+        self._L.flo_sdec_reset(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.flo_sdec_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class StreamsResult(NamedTuple):
+    out: object          # float32 torch tensor on the context's device
+    offsets: np.ndarray  # [n + 1] uint64: decoder i's samples are out[offsets[i]:offsets[i + 1]]
+    status: np.ndarray   # [n] int32: 0, or the FLO_ERR_* code decoder i's next next_frame reports
+    errors: list         # [n] that error's message ("" for status 0)
+
+
+def decode_streams(decoders, max_frames: int = 0, out=None, ctx: Context = None) -> StreamsResult:
+    """flo_sdec_decode_ready: every complete frame not yet returned of every decoder (at most max_frames each, 0: all),
+    decoded in one set of launches. Decoder i's part equals the concatenation of as many next_frame() results, and its
+    counters advance to match. The decode is enqueued behind torch's current stream and ordered before what is queued on
+    it afterwards. `out`: an optional contiguous float32 tensor on the device, large enough."""
+    import torch
+    decoders = list(decoders)
+    if any(getattr(d, "_h", None) is None for d in decoders):
+        raise FloError("decode_streams: a decoder is closed")
+    if ctx is None:
+        ctx = next((d._ctx for d in decoders if d._ctx is not None), None) or default_context()
+    for d in decoders:
+        if d._ctx is None:
+            d._ctx = ctx
+            if d._L.flo_sdec_attach(d._h, ctx._h) != 0:
+                raise FloError("a decoder belongs to another context")
+            ctx._batches.add(d)
+    L = ctx._L
+    n = len(decoders)
+    hs = C.cast((C.c_void_p * max(n, 1))(*[d._h.value for d in decoders]), C.c_void_p)
+    offs = np.zeros(n + 1, np.uint64)
+    st = np.zeros(max(n, 1), np.int32)
+    dev = torch.device("cuda", ctx.device)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    # sizing first (no destination: offsets only, nothing decoded), then the decode into a buffer of that size
+    ctx._chk(L.flo_sdec_decode_ready(ctx._h, n, hs, int(max_frames), None, 0, offs.ctypes.data, st.ctypes.data, None))
+    need = int(offs[-1])
+    if out is None:
+        out = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or out.numel() < need:
+        raise FloError(f"out must be a contiguous float32 tensor of at least {need} elements on {dev}")
+    ctx._chk(L.flo_sdec_decode_ready(ctx._h, n, hs, int(max_frames), C.c_void_p(out.data_ptr()), out.numel(), offs.ctypes.data,
+                                     st.ctypes.data, C.c_void_p(stream)))
+    st = st[:n].copy()
+    errors = [decoders[i]._err() if st[i] else "" for i in range(n)]
+    return StreamsResult(out[:int(offs[-1])], offs, st, errors)
+
+
 def _encode_analysed(mode, samples, sample_rate, channels, quality_or_level, bit_depth, metadata) -> bytes:
     """what the three free functions share (lib.rs:97-206): `add_analysis_data_if_missing(&metadata.unwrap_or_default(), samples,
     sr, ch, 50)`, then the encoder - on ONE copy of the samples: uploaded once, analysed on the device, encoded from there"""

@@ -5,7 +5,7 @@
 // block into pinned staging, one copy of it, and the launches - all on the ctx stream, ordered against the caller's
 // stream by events. Nothing synchronises the host in steady state: scratch only grows (the blocks it replaces are freed
 // at the next flo_corpus_sync), and a staging slot is reused only once the copy out of it has completed.
-//   lossy files:    lossy_decode_kernel<true> (decode_kernels.hip): runs of blocks per window, trimmed to the window
+//   lossy files:    lossy_decode_kernel<kDecWindow> (decode_kernels.hip): runs of blocks per window, trimmed to the window
 //   lossless files: the frames a window touches (each window its own: a frame two windows share is decoded twice) go
 //                   through the parallel Rice / predictor kernels (lldec_kernels.hip) on a per-call wrapper list, then
 //                   ll_window_finish_kernel writes the window's part of each frame to the window's slot

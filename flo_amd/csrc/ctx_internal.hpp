@@ -46,9 +46,12 @@ struct flo_ctx {
     int reserve_cus = -1;   // compute units the persistent chain kernel leaves free (-1: not set; see flo_ctx_reserve_cus)
     AnalysisSide an_side;   // side streams of the analysis (made on first use)
     bool an_side_ready = false;
+    struct SdecWork *sdec = nullptr;   // flo_sdec_decode_ready's staging slots and scratch (sdec.cpp; made on first use)
 };
 
 int fail(flo_ctx *c, int code, const std::string &msg);
+// releases flo_ctx::sdec (sdec.cpp)
+void sdec_work_free(flo_ctx *c);
 #define HIPCHK(ctx, expr)                                                                               \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \

@@ -43,10 +43,13 @@ constexpr int kBlobStage = 2304;
 #else
 #define DSTAMP(i) do {} while (0)
 #endif
-// WIN = false: whole clips (flo_decode, flo_batch_decode). WIN = true: corpus windows (launch_lossy_window): the unit of work
+// kDecWhole: whole clips (flo_decode, flo_batch_decode). kDecWindow: corpus windows (launch_lossy_window): the unit of work
 // is one run of blocks of one window, the run is trimmed to the window's blocks and its stores to the window's samples.
-template <bool WIN>
+// kDecStream: streaming decoders (launch_lossy_stream): the unit of work is one run of one stream's frames in the call's
+// frame list; the overlap comes from the stream's device state and goes back to it (LossyRunDev::flags).
+template <int MODE>
 __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
+    constexpr bool WIN = MODE == kDecWindow, STRM = MODE == kDecStream;
     const LossyWinArgs &W = D.win;
     // One 8 KiB buffer serves three phases of a channel-frame in turn: the parse table of the record headers, then the
     // integers + the FFT exchange buffer, then the windowed output. Everything that does not change from frame to frame
@@ -83,7 +86,9 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     unsigned clip, run, h0, h1;
     float *out;
     unsigned long long wfirst = 0, wend = 0, frame0 = 0;   // (WIN) the window's samples [wfirst, wend), its file's first frame
-    if constexpr (!WIN) {
+    float *st = nullptr;    // (STRM) the stream's overlap state
+    unsigned sflags = 0;    // (STRM) kRun*
+    if constexpr (MODE == kDecWhole) {
     if (P >= (unsigned long long)D.n_clips * D.n_runs) return;
     clip = (unsigned)(P % (unsigned)D.n_clips);   // (clips fastest)
     const unsigned nframes = D.clip_frames[clip];
@@ -92,7 +97,7 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     if (nframes < 2 || h0 + 1 >= nframes) return;
     h1 = h0 + run < nframes - 1 ? h0 + run : nframes - 1;   // last frame of the run
     out = D.out + D.clip_out[clip];
-    } else {
+    } else if constexpr (MODE == kDecWindow) {
         // window w, run r of its runs (runs fastest): blocks b0 + r run .. of the window's blocks b0 .. b1, which need frames
         // b0 .. b1 + 1 of the file; output past the file's last block is the zero tail, written by window_tail_kernel
         if (P >= (unsigned long long)W.n_windows * W.runs_per_window) return;
@@ -111,6 +116,19 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
         h1 = h0 + run < b1 + 1 ? h0 + run : b1 + 1;
         frame0 = wd.frame0;
         out = D.out + wd.dst;
+    } else {
+        // run P of the call's runs: frames frame0 .. frame0 + n_frames - 1 of the call's frame list
+        if (P >= (unsigned long long)D.strm.n_runs) return;
+        const LossyRunDev rd = D.strm.runs[P];
+        if (rd.n_frames < 1u || rd.n_frames > (unsigned)kDecRunLong + 1u) return;   // (the host never builds such a run)
+        clip = 0;
+        run = rd.n_frames;
+        h0 = 0;
+        h1 = rd.n_frames - 1u;
+        frame0 = rd.frame0;
+        out = D.out + rd.dst;
+        st = rd.state;
+        sflags = rd.flags;
     }
     const float scale = 2.0f / 1024.0f;
     // loop invariants of the run, in registers
@@ -148,7 +166,7 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
         wave_sync();
         if ((unsigned)lane <= h1 - h0) {
             unsigned long long f;
-            if constexpr (WIN) f = frame0 + h0 + (unsigned)lane;
+            if constexpr (MODE != kDecWhole) f = frame0 + h0 + (unsigned)lane;
             else f = D.clip_frame0[clip] + h0 + (unsigned)lane;
             const unsigned long long foff = D.blob_off[f];
             const uint32_t flen = D.blob_len[f];
@@ -495,10 +513,11 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
             // (carried in registers). A channel the frame does not carry gives a silent block and leaves the overlap
             // alone (the reference would fail on such a frame; the oracle behaves like this).
             if constexpr (!WIN) {
-            if (h > h0) {
+            if (h > h0 || (STRM && (sflags & kRunWriteFirst))) {
                 // (a uniform block base and a 32-bit lane offset: the stores take the scalar-base form, no 64-bit address
-                // arithmetic per store)
-                float *ob = out + ((unsigned long long)(h - 1) * 1024) * D.channels + c;
+                // arithmetic per store; a stream run's blocks start at its first frame that writes one)
+                const unsigned blk = STRM ? h - h0 - ((sflags & kRunWriteFirst) ? 0u : 1u) : h - 1;
+                float *ob = out + ((unsigned long long)blk * 1024) * D.channels + c;
                 const uint32_t nchu = (uint32_t)D.channels;
 #pragma unroll
                 for (int k = 0; k < 16; k++) {
@@ -535,6 +554,12 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     {
 #pragma unroll
         for (int k = 0; k < 16; k++) pv[k] = 0.0f;
+        if constexpr (STRM) {
+            if (sflags & kRunLoad) {
+#pragma unroll
+                for (int k = 0; k < 16; k++) pv[k] = st[((sflags & kRunOdd) ? nc * 1024u : 0u) + c * 1024u + (unsigned)lane + 64u * (unsigned)k];
+            }
+        }
         if (!index_run(c)) return;
         fetch(c, h0);
         for (unsigned h = h0; h <= h1; h++) {
@@ -555,6 +580,16 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
             if (h < h1) fetch(c, h + 1);
             DSTAMP(0);
             if (!frame_ch(c, h, present, blen, staged, sfw)) return;
+        }
+        if constexpr (STRM) {
+            if (sflags & kRunStore) {
+                // into the half this call does not read: the stream's first run may load after its last run has stored
+                // (nontemporal: the state is read again by the stream's next call only; plain stores here also cost the
+                // kernel two VGPRs over the whole-file instantiation)
+#pragma unroll
+                for (int k = 0; k < 16; k++)
+                    __builtin_nontemporal_store(pv[k], st + ((sflags & kRunOdd) ? 0u : nc * 1024u) + c * 1024u + (unsigned)lane + 64u * (unsigned)k);
+            }
         }
     }
 #ifdef FLO_DEC_STAMPS
@@ -846,7 +881,7 @@ int launch_lossy_decode(const LossyDecArgs &A0, unsigned max_frames, hipStream_t
     if (hipMalloc(&d_dbg, 80) != hipSuccess || hipMemset(d_dbg, 0, 80) != hipSuccess) return -1;
     A.dbg = d_dbg;
 #endif
-    hipLaunchKernelGGL(lossy_decode_kernel<false>, dim3((unsigned)wgs), dim3(64), 0, s, A);
+    hipLaunchKernelGGL(lossy_decode_kernel<kDecWhole>, dim3((unsigned)wgs), dim3(64), 0, s, A);
     FLO_LAUNCH_CHECK();
 #ifdef FLO_DEC_STAMPS
     {
@@ -874,7 +909,19 @@ int launch_lossy_window(const LossyDecArgs &A0, const LossyWinArgs &W, unsigned 
     const unsigned long long wgs = (units + 7ull) / 8ull * 8ull * (unsigned)A.channels;
     if (wgs > 0x7FFFFFFFull) return -1;
     A.win = W;
-    hipLaunchKernelGGL(lossy_decode_kernel<true>, dim3((unsigned)wgs), dim3(64), 0, s, A);
+    hipLaunchKernelGGL(lossy_decode_kernel<kDecWindow>, dim3((unsigned)wgs), dim3(64), 0, s, A);
+    FLO_LAUNCH_CHECK();
+    return 0;
+}
+int launch_lossy_stream(const LossyDecArgs &A0, const LossyStreamArgs &S, hipStream_t s) {
+    if (!S.n_runs || A0.channels < 1) return 0;
+    LossyDecArgs A = A0;
+    A.run = kDecRunLong;   // (unused by this mode: each run carries its own length)
+    // the grid of lossy_decode_kernel: runs in groups of eight, the channels of a group eight workgroups apart (one XCD)
+    const unsigned long long wgs = ((unsigned long long)S.n_runs + 7ull) / 8ull * 8ull * (unsigned)A.channels;
+    if (wgs > 0x7FFFFFFFull) return -1;
+    A.strm = S;
+    hipLaunchKernelGGL(lossy_decode_kernel<kDecStream>, dim3((unsigned)wgs), dim3(64), 0, s, A);
     FLO_LAUNCH_CHECK();
     return 0;
 }

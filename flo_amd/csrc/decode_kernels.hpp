@@ -7,7 +7,7 @@
 
 namespace flo {
 
-// Corpus windows (lossy_decode_kernel<true>): one descriptor per window, built per call.
+// Corpus windows (lossy_decode_kernel<kDecWindow>): one descriptor per window, built per call.
 struct LossyWinDev {
     unsigned long long frame0;        // the file's first frame in the corpus's compacted frame list (blob_off / blob_len)
     unsigned long long start;         // first sample-frame of the window in the file's decoded signal
@@ -21,6 +21,28 @@ struct LossyWinArgs {
     unsigned int runs_per_window;     // runs of LossyDecArgs::run blocks per window
     unsigned int length;              // window_frames
 };
+// Streaming decoders (lossy_decode_kernel<kDecStream>, flo_sdec_decode_ready): one descriptor per run of a stream's
+// frames, built per call. A stream's overlap (the second half of the last frame it decoded, 1024 floats per channel,
+// channel-major) lives in device memory between calls, in two halves: a call loads from one and stores into the other
+// (kRunOdd: load the second half, store the first), since the runs of one stream are unordered workgroups of one launch.
+constexpr unsigned kRunLoad = 1u;         // start from the stream's overlap state (else: the first frame only primes it)
+constexpr unsigned kRunStore = 2u;        // store the run's final overlap into the other half of the state
+constexpr unsigned kRunWriteFirst = 4u;   // the first frame writes a block (else it is a lead frame or the pre-roll)
+constexpr unsigned kRunOdd = 8u;          // the call's parity: which half of the state is read
+struct LossyRunDev {
+    unsigned long long frame0;        // first frame of the run in the call's frame list (blob_off / blob_len)
+    unsigned long long dst;           // float offset in `out` of the first block the run writes
+    float *state;                     // [2][channels][1024] the stream's overlap, read half and written half (kRunOdd)
+    unsigned int n_frames;            // frames of the run, 1 .. kDecRunLong + 1 (16 at most with kRunWriteFirst)
+    unsigned int flags;               // kRun*
+};
+struct LossyStreamArgs {
+    const LossyRunDev *runs;
+    unsigned int n_runs;
+    unsigned int pad;
+};
+enum DecMode : int { kDecWhole = 0, kDecWindow = 1, kDecStream = 2 };
+
 // One transform frame = one wavefront. Frames of a clip are addressed by (clip, local frame index).
 struct LossyDecArgs {
     LossyDevTables T;                 // pack (rotation + FFT twiddles) and the coefficient -> band map of the file's sample rate
@@ -39,6 +61,7 @@ struct LossyDecArgs {
     unsigned int n_runs;              // runs per clip (set by the launcher)
     unsigned long long *dbg;          // FLO_DEC_STAMPS builds only: phase tick sums (set by the launcher)
     LossyWinArgs win;                 // corpus windows only (set by launch_lossy_window)
+    LossyStreamArgs strm;             // streaming decoders only (set by launch_lossy_stream)
 };
 
 // One ALPC / raw / silent channel wrapper of one frame = one thread.
@@ -126,6 +149,8 @@ int launch_ll_finish(const LlFinishArgs &A, unsigned max_samples, hipStream_t s)
 // corpus windows: runs of `run` blocks (<= 16), runs_per_window of them per window
 int launch_lossy_window(const LossyDecArgs &A, const LossyWinArgs &W, unsigned run, hipStream_t s);
 int launch_ll_window_finish(const LlWinFinishArgs &A, unsigned max_count, hipStream_t s);
+// streaming decoders: one wavefront per run and channel
+int launch_lossy_stream(const LossyDecArgs &A, const LossyStreamArgs &S, hipStream_t s);
 int launch_window_tail(const WinTailDev *tails, unsigned n, float *out, hipStream_t s);
 
 }  // namespace flo

@@ -106,6 +106,7 @@ extern "C" void flo_ctx_destroy(flo_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
+    sdec_work_free(c);
     for (auto *t : c->tables) {
         if (t->blob) hipFree(t->blob);
         delete t;

@@ -158,6 +158,74 @@ int flo_corpus_decode_windows(flo_corpus *c, size_t n_windows, const uint32_t *f
                               uint32_t window_frames, float *dst_device, size_t dst_cap_floats, void *stream);
 int flo_corpus_sync(flo_corpus *c);
 
+/* ---- streaming decoder: StreamingDecoder of libflo/src/streaming/decoder.rs (WasmStreamingDecoder, lib.rs:545-681) -----
+ * Bytes of one .flo file are fed in chunks as they arrive; each frame's samples come out once the frame is complete. The
+ * state machine, the counters and the frame parser are the reference's, quirks included:
+ *   - the header is read from a fixed 70 bytes; bad magic is the only thing that enters FLO_SDEC_ERROR (feed returns
+ *     FLO_ERR_FORMAT then, "Invalid flo file: bad magic"); the TOC starts at 70, the frames at 70 + toc_size
+ *     (header_size is ignored); a TOC shorter than its entry count leaves the entries read pushed, and the next feed
+ *     pushes them again;
+ *   - feed in FLO_SDEC_ERROR or FLO_SDEC_FINISHED drops the data (*new_frames = 0);
+ *   - a frame is complete when its TOC end lies inside the buffer; counting stops at the first incomplete frame;
+ *   - next_frame moves to FLO_SDEC_FINISHED once current_frame >= the TOC's length; a frame that does not parse
+ *     ("Frame too small", "Frame truncated", "Channel data truncated", "Invalid LPC order", "ALPC channel too small",
+ *     "Missing rice parameter") fails without advancing, so it fails again on the next call;
+ *   - lossy: the first transform frame that deserialises is the pre-roll: an empty frame that primes the overlap; a
+ *     frame that does not deserialise is an empty frame, consumed, no pre-roll, the overlap untouched;
+ *   - decode_available decodes the whole buffer from frame 0 like the file reader (its errors leave the state as it was;
+ *     on success the state is FLO_SDEC_FINISHED); it equals flo_decode except that a lossy frame that does not
+ *     deserialise is skipped (flo_decode fails on it).
+ * What the device decoder does not take comes back as FLO_ERR_FORMAT without advancing, like a parse error: transform
+ * blocks other than Long, a transform frame with more channels than the stream, an ALPC wrapper with coefficients and
+ * a non-Rice encoding byte (no encoder writes one), a frame of more than 2 000 000 samples, and a stream that mixes
+ * transform frames with other frames (kind chosen by the header's lossy flag).
+ *
+ * A decoder without a context (ctx NULL) parses and counts; next_frame / decode_available return FLO_ERR_STATE until
+ * flo_sdec_attach gives it one (flo_sdec_decode_ready attaches its context itself).
+ * next_frame returns 1 with one frame in *pcm (malloc'ed, flo_free; NULL and *n = 0 for an empty frame), 0 when no
+ * frame is ready, or a negated FLO_ERR_* code (-FLO_ERR_FORMAT for the errors above). flo_sdec_last_error(d) holds the
+ * decoder's last message.
+ *
+ * flo_sdec_decode_ready: for each decoder, every complete frame that next_frame has not returned yet (at most
+ * max_frames_per_stream of them, 0: all) is decoded into dst_device[offsets[i] .. offsets[i + 1]): bit for bit the
+ * concatenation of what as many next_frame calls return, and the decoder's counters advance to match (a decoder with
+ * nothing left to decode moves to FLO_SDEC_FINISHED, as a next_frame call would). offsets ([n + 1] floats) and status
+ * ([n]: FLO_OK, or the error the decoder's next next_frame reports, message in flo_sdec_last_error) are filled before
+ * the call returns; the decode is enqueued on the ctx stream, ordered after what is queued on `stream` and before its
+ * later work (as flo_corpus_decode_windows). Decoders not yet ready contribute nothing. All decoders that decode in one
+ * call share one sample rate and channel count (FLO_ERR_ARG otherwise); lossy and lossless streams may be mixed. A
+ * lossy stream's overlap stays on the device between calls: each frame is decoded once, except one frame re-decoded
+ * at every 16-frame run boundary inside a call. Per call only the payload bytes of the frames decoded are uploaded.
+ * dst_device NULL: sizing only - offsets and status are filled, nothing is decoded and no decoder changes; the next call
+ * on the same context over the same decoders and cap, none of them changed in between, reuses that plan. */
+#define FLO_SDEC_WAITING_HEADER 0
+#define FLO_SDEC_WAITING_TOC 1
+#define FLO_SDEC_READY 2
+#define FLO_SDEC_FINISHED 3
+#define FLO_SDEC_ERROR 4
+typedef struct flo_sdec flo_sdec;
+typedef struct flo_sdec_audio_info {   /* StreamingAudioInfo, streaming/types.rs */
+    uint32_t sample_rate;
+    uint8_t channels, bit_depth, is_lossy, pad;
+    uint64_t total_samples;
+} flo_sdec_audio_info;
+int flo_sdec_create(flo_ctx *ctx /* may be NULL: parse only */, flo_sdec **out);
+void flo_sdec_destroy(flo_sdec *d);
+int flo_sdec_attach(flo_sdec *d, flo_ctx *ctx);   /* FLO_ERR_STATE if it already has another context */
+const char *flo_sdec_last_error(const flo_sdec *d);
+int flo_sdec_feed(flo_sdec *d, const uint8_t *data, size_t len, int *new_frames);
+int flo_sdec_state(const flo_sdec *d);
+int flo_sdec_info(const flo_sdec *d, flo_sdec_audio_info *out);   /* FLO_ERR_STATE before the header */
+size_t flo_sdec_frames_available(const flo_sdec *d);      /* complete frames, NOT minus the current one (decoder.rs:63-68) */
+size_t flo_sdec_available_frames(const flo_sdec *d);      /* complete frames minus the current one (:143-149) */
+size_t flo_sdec_current_frame_index(const flo_sdec *d);
+size_t flo_sdec_buffered_bytes(const flo_sdec *d);
+int flo_sdec_next_frame(flo_sdec *d, float **pcm, size_t *n);
+int flo_sdec_decode_available(flo_sdec *d, float **pcm, size_t *n);
+void flo_sdec_reset(flo_sdec *d);
+int flo_sdec_decode_ready(flo_ctx *ctx, size_t n, flo_sdec *const *decs, uint32_t max_frames_per_stream, float *dst_device,
+                          size_t dst_cap_floats, uint64_t *offsets, int *status, void *stream);
+
 /* ---- device-resident batch (the throughput path: PCM already in HBM, bitstreams left in HBM) -------- */
 typedef struct flo_batch flo_batch;
 
