@@ -13,18 +13,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "container.hpp"
 #include "ctx_internal.hpp"
 #include "decode_kernels.hpp"
+#include "decode_plan.hpp"
 #include "devpool.hpp"
 
 namespace {
-constexpr int kStageSlots = 8;   // pinned descriptor slots in flight
-
 struct CorpusFile {
     bool lossy = false;
     uint64_t n_out = 0;     // flo_decode's length in sample-frames
@@ -40,14 +38,7 @@ struct LlFrame {
 };
 struct LlWrapper {
     LlChannelDev d;         // off: absolute in the corpus buffer; out_off filled per call
-    uint32_t tiles;         // Rice tiles of the parallel form (0: none, or serial)
-    uint8_t serial, other;
-};
-struct Slot {
-    void *pin = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;
-    bool used = false;
+    LlRoute r;              // routed once, here
 };
 struct Grow {               // device scratch that only grows; replaced blocks wait for the next sync
     void *p = nullptr;
@@ -69,15 +60,11 @@ struct flo_corpus {
     std::vector<LlWrapper> ll_wr;
     Grow desc, scr, tabs, ent;
     std::vector<void *> retired;
-    Slot slots[kStageSlots];
-    unsigned next_slot = 0;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    StageRing ring;
     // per-call host lists (kept: no allocation in steady state)
     std::vector<LossyWinDev> wins;
     std::vector<WinTailDev> tails;
-    std::vector<LlChannelDev> chs;
-    std::vector<unsigned int> tile0, others;
-    std::vector<int> serial;
+    LlWrapperList ll;
     std::vector<LlWinItem> items;
 };
 
@@ -88,12 +75,6 @@ static void corpus_free(flo_corpus *c) {
         if (g->p) pool_free(g->p);
     for (void *p : {(void *)c->d_bytes, (void *)c->d_blob_off, (void *)c->d_blob_len, (void *)c->d_err})
         if (p) pool_free(p);
-    for (Slot &s : c->slots) {
-        if (s.ev) hipEventSynchronize(s.ev), hipEventDestroy(s.ev);
-        if (s.pin) hipHostFree(s.pin);
-    }
-    if (c->ev_in) hipEventDestroy(c->ev_in);
-    if (c->ev_out) hipEventDestroy(c->ev_out);
     delete c;
 }
 
@@ -144,7 +125,7 @@ extern "C" int flo_corpus_create(flo_ctx *ctx, size_t n_files, const uint8_t *co
             }
             cf.n_frames = (uint32_t)(blob_off.size() - cf.frame0);
             cf.n_out = cf.n_frames > 1 ? (uint64_t)(cf.n_frames - 1) * 1024u : 0;
-        } else {   // lossless/decoder.rs:21-72: every frame, its wrappers (as flo_decode's LlWork)
+        } else {   // lossless/decoder.rs:21-72: every frame, its wrappers
             cf.frame0 = c->ll_frames.size();
             cf.n_frames = (uint32_t)f.frames.size();
             uint64_t at = 0;
@@ -153,24 +134,9 @@ extern "C" int flo_corpus_create(flo_ctx *ctx, size_t n_files, const uint8_t *co
                            (f.channels == 2 && (fr.flags & 1)) ? 1u : 0u};
                 for (unsigned k = 0; k < fr.n_channels; k++) {
                     const ChannelDesc &cd = f.channels_desc[fr.first_channel + k];
-                    LlWrapper w{};
-                    w.d.off = base[i] + cd.off;
-                    w.d.len = cd.len;
+                    LlWrapper w{ll_channel(base[i] + cd.off, cd.len, cd.n_coeffs, cd.shift_bits, cd.rice_k, cd.coeffs), {}};
                     w.d.samples = fr.samples;
-                    w.d.n_coeffs = cd.n_coeffs;
-                    w.d.shift_bits = cd.shift_bits;
-                    w.d.rice_k = cd.rice_k;
-                    memcpy(w.d.coeffs, cd.coeffs, sizeof w.d.coeffs);
-                    // which kernels take the wrapper: the same rules as flo_decode (ll_decode_device in flo_api.cpp)
-                    const LlChannelDev &d = w.d;
-                    const bool rice = d.len > 0 && (d.n_coeffs > 0 || d.shift_bits >= 128);
-                    long long csum = 0;
-                    for (unsigned q = 0; q < d.n_coeffs; q++) csum += d.coeffs[q] < 0 ? -(long long)d.coeffs[q] : (long long)d.coeffs[q];
-                    bool ser = (rice && d.rice_k > kRiceMaxK) || csum >= (1ll << 21) || (d.n_coeffs && (d.shift_bits & 63u) > 20u);
-                    if (rice && d.len > 16u * 1024u * (unsigned)kRiceTileBits) ser = true;
-                    w.serial = ser ? 1 : 0;
-                    w.other = !(d.n_coeffs > 0 && d.n_coeffs <= 12 && d.len > 0 && d.samples > d.n_coeffs) ? 1 : 0;
-                    w.tiles = rice && !ser ? (d.len + (unsigned)kRiceTileBits / 8u - 1u) / ((unsigned)kRiceTileBits / 8u) : 0u;
+                    w.r = ll_route(w.d, false);
                     c->ll_wr.push_back(w);
                 }
                 c->ll_frames.push_back(lf);
@@ -204,11 +170,7 @@ extern "C" int flo_corpus_create(flo_ctx *ctx, size_t n_files, const uint8_t *co
     }
     if (pool_alloc(&c->d_err, sizeof(int)) != hipSuccess) return bail(fail(ctx, FLO_ERR_NOMEM, "corpus error word"));
     HIPCHK(ctx, hipMemsetAsync(c->d_err, 0, sizeof(int), ctx->stream));
-    for (Slot &s : c->slots)
-        if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) return bail(fail(ctx, FLO_ERR_DEVICE, "hipEventCreate failed"));
-    if (hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming) != hipSuccess)
-        return bail(fail(ctx, FLO_ERR_DEVICE, "hipEventCreate failed"));
+    if (!c->ring.init()) return bail(fail(ctx, FLO_ERR_DEVICE, "hipEventCreate failed"));
     // the host vectors blob_off / blob_len die with this frame
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail(fail(ctx, FLO_ERR_DEVICE, "corpus upload failed"));
     *out = c;
@@ -251,13 +213,9 @@ extern "C" int flo_corpus_decode_windows(flo_corpus *c, size_t n_windows, const 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     c->wins.clear();
     c->tails.clear();
-    c->chs.clear();
-    c->tile0.assign(1, 0u);
-    c->others.clear();
-    c->serial.clear();
+    c->ll.clear();
     c->items.clear();
-    uint64_t scratch = 0;
-    unsigned max_tiles = 0, max_count = 0;
+    unsigned max_count = 0;
     for (size_t w = 0; w < n_windows; w++) {
         if (file[w] >= c->files.size()) return fail(ctx, FLO_ERR_ARG, "window file index out of range");
         const CorpusFile &F = c->files[file[w]];
@@ -278,7 +236,7 @@ extern "C" int flo_corpus_decode_windows(flo_corpus *c, size_t n_windows, const 
             if (a >= b) continue;
             LlWinItem it{};
             it.dst = dst + (a - s) * ch;
-            it.first_channel = (unsigned)c->chs.size();
+            it.first_channel = (unsigned)c->ll.chs.size();
             it.n_channels = fr->n_channels;
             it.from = (unsigned)(a - fr->start);
             it.count = (unsigned)(b - a);
@@ -286,63 +244,32 @@ extern "C" int flo_corpus_decode_windows(flo_corpus *c, size_t n_windows, const 
             max_count = std::max(max_count, it.count);
             for (unsigned k = 0; k < fr->n_channels; k++) {
                 const LlWrapper &x = c->ll_wr[fr->first_wrapper + k];
-                const unsigned i = (unsigned)c->chs.size();
-                c->chs.push_back(x.d);
-                c->chs.back().out_off = scratch;
-                scratch += fr->samples;
-                c->serial.push_back(x.serial);
-                if (x.other) c->others.push_back(i);
-                c->tile0.push_back(c->tile0.back() + x.tiles);
-                max_tiles = std::max(max_tiles, x.tiles);
+                c->ll.push(x.d, x.r);
             }
             c->items.push_back(it);
         }
     }
-    // one descriptor block: [lossy windows][tails][wrappers][tile0][serial][others][items]
-    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_win = 0, o_tail = o_win + up256(c->wins.size() * sizeof(LossyWinDev)),
-                 o_ch = o_tail + up256(c->tails.size() * sizeof(WinTailDev)), o_t0 = o_ch + up256(c->chs.size() * sizeof(LlChannelDev)),
-                 o_ser = o_t0 + up256(c->tile0.size() * sizeof(unsigned int)), o_oth = o_ser + up256(c->serial.size() * sizeof(int)),
-                 o_it = o_oth + up256(c->others.size() * sizeof(unsigned int)), bytes = o_it + up256(c->items.size() * sizeof(LlWinItem));
-    // the staging slot: reused only after the copy out of it has completed (in steady state long since)
-    Slot &sl = c->slots[c->next_slot++ % kStageSlots];
-    if (sl.used) HIPCHK(ctx, hipEventSynchronize(sl.ev));
-    if (sl.cap < bytes) {
-        if (sl.pin) hipHostFree(sl.pin);
-        sl.pin = nullptr;
-        sl.cap = 0;
-        const size_t want = bytes + bytes / 4;
-        HIPCHK(ctx, hipHostMalloc(&sl.pin, want, hipHostMallocDefault));
-        sl.cap = want;
-    }
-    uint8_t *pin = (uint8_t *)sl.pin;
-    memcpy(pin + o_win, c->wins.data(), c->wins.size() * sizeof(LossyWinDev));
-    memcpy(pin + o_tail, c->tails.data(), c->tails.size() * sizeof(WinTailDev));
-    memcpy(pin + o_ch, c->chs.data(), c->chs.size() * sizeof(LlChannelDev));
-    memcpy(pin + o_t0, c->tile0.data(), c->tile0.size() * sizeof(unsigned int));
-    memcpy(pin + o_ser, c->serial.data(), c->serial.size() * sizeof(int));
-    memcpy(pin + o_oth, c->others.data(), c->others.size() * sizeof(unsigned int));
-    memcpy(pin + o_it, c->items.data(), c->items.size() * sizeof(LlWinItem));
+    // one descriptor block
+    enum { kWin, kTail, kCh, kT0, kSer, kOth, kItem };
+    const LlWrapperList &ll = c->ll;
+    const DescBlock blk{desc_part(c->wins), desc_part(c->tails), desc_part(ll.chs), desc_part(ll.tile0),
+                        desc_part(ll.serial), desc_part(ll.others), desc_part(c->items)};
+    uint8_t *pin;
     int rc;
-    if ((rc = grow(c, c->desc, bytes)) != FLO_OK) return rc;
-    if (!c->chs.empty()) {
-        const size_t tiles = c->tile0.back();
-        if ((rc = grow(c, c->scr, scratch * sizeof(int))) != FLO_OK || (rc = grow(c, c->tabs, (tiles ? tiles : 1) * kRiceStates * sizeof(unsigned int))) != FLO_OK ||
+    if ((rc = c->ring.acquire(ctx, blk.bytes, &pin)) != FLO_OK) return rc;
+    blk.fill(pin);
+    if ((rc = grow(c, c->desc, blk.bytes)) != FLO_OK) return rc;
+    if (!ll.chs.empty()) {
+        const size_t tiles = ll.tiles();
+        if ((rc = grow(c, c->scr, ll.scratch * sizeof(int))) != FLO_OK || (rc = grow(c, c->tabs, (tiles ? tiles : 1) * kRiceStates * sizeof(unsigned int))) != FLO_OK ||
             (rc = grow(c, c->ent, (tiles ? tiles : 1) * sizeof(uint2))) != FLO_OK)
             return rc;
     }
-    // order: after what the caller queued on `stream`; the caller's later work after ours
     hipStream_t us = (hipStream_t)stream, cs = ctx->stream;
-    if (us != cs) {
-        HIPCHK(ctx, hipEventRecord(c->ev_in, us));
-        HIPCHK(ctx, hipStreamWaitEvent(cs, c->ev_in, 0));
-    }
-    uint8_t *d = (uint8_t *)c->desc.p;
-    HIPCHK(ctx, hipMemcpyAsync(d, pin, bytes, hipMemcpyHostToDevice, cs));
-    HIPCHK(ctx, hipEventRecord(sl.ev, cs));
-    sl.used = true;
+    if ((rc = c->ring.fence_in(ctx, us)) != FLO_OK || (rc = c->ring.upload(ctx, c->desc.p, blk.bytes)) != FLO_OK) return rc;
+    void *d = c->desc.p;
     if (!c->tails.empty()) {
-        const WinTailDev *t = reinterpret_cast<const WinTailDev *>(d + o_tail);
+        const WinTailDev *t = blk.at<const WinTailDev>(d, kTail);
         if ((rc = timed_launch(ctx, "window_tail", [&] { return launch_window_tail(t, (unsigned)c->tails.size(), dst_device, cs); })) != FLO_OK) return rc;
     }
     if (!c->wins.empty()) {
@@ -357,27 +284,19 @@ extern "C" int flo_corpus_decode_windows(flo_corpus *c, size_t n_windows, const 
         A.channels = c->channels;
         A.out = dst_device;
         A.error = c->d_err;
-        LossyWinArgs W{reinterpret_cast<const LossyWinDev *>(d + o_win), (unsigned)c->wins.size(), rpw, window_frames};
+        LossyWinArgs W{blk.at<const LossyWinDev>(d, kWin), (unsigned)c->wins.size(), rpw, window_frames};
         if ((rc = timed_launch(ctx, "lossy_window", [&] { return launch_lossy_window(A, W, run, cs); })) != FLO_OK) return rc;
     }
-    if (!c->chs.empty()) {
-        const LlChannelDev *d_ch = reinterpret_cast<const LlChannelDev *>(d + o_ch);
-        int *d_ser = reinterpret_cast<int *>(d + o_ser);
-        LlParArgs P{c->d_bytes, d_ch, (unsigned)c->chs.size(), (int *)c->scr.p, reinterpret_cast<const unsigned int *>(d + o_t0),
-                    (unsigned int *)c->tabs.p, (uint2 *)c->ent.p, d_ser, reinterpret_cast<const unsigned int *>(d + o_oth),
-                    (unsigned)c->others.size()};
-        if ((rc = timed_launch(ctx, "window_ll_decode_parallel", [&] { return launch_ll_decode_parallel(P, max_tiles, cs); })) != FLO_OK) return rc;
-        LlDecArgs S{c->d_bytes, d_ch, (unsigned)c->chs.size(), (int *)c->scr.p, d_ser};
-        if ((rc = timed_launch(ctx, "window_ll_decode", [&] { return launch_ll_decode(S, cs); })) != FLO_OK) return rc;
-        LlWinFinishArgs F{reinterpret_cast<const LlWinItem *>(d + o_it), d_ch, (unsigned)c->items.size(), (int)c->channels,
-                          (const int *)c->scr.p, dst_device};
+    if (!ll.chs.empty()) {
+        const LlChannelDev *d_ch = blk.at<const LlChannelDev>(d, kCh);
+        if ((rc = launch_ll_wrappers(ctx, ll, c->d_bytes, d_ch, blk.at<const unsigned int>(d, kT0), blk.at<int>(d, kSer),
+                                     blk.at<const unsigned int>(d, kOth), (int *)c->scr.p, (unsigned int *)c->tabs.p, (uint2 *)c->ent.p,
+                                     "window_ll_decode_parallel", "window_ll_decode")) != FLO_OK)
+            return rc;
+        LlWinFinishArgs F{blk.at<const LlWinItem>(d, kItem), d_ch, (unsigned)c->items.size(), (int)c->channels, (const int *)c->scr.p, dst_device};
         if ((rc = timed_launch(ctx, "window_ll_finish", [&] { return launch_ll_window_finish(F, max_count, cs); })) != FLO_OK) return rc;
     }
-    if (us != cs) {
-        HIPCHK(ctx, hipEventRecord(c->ev_out, cs));
-        HIPCHK(ctx, hipStreamWaitEvent(us, c->ev_out, 0));
-    }
-    return FLO_OK;
+    return c->ring.fence_out(ctx, us);
 }
 
 extern "C" int flo_corpus_sync(flo_corpus *c) {

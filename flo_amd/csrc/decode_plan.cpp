@@ -1,0 +1,134 @@
+// decode_plan.cpp — see decode_plan.hpp.
+#include "decode_plan.hpp"
+
+#include <cassert>
+#include <cstring>
+
+LlRoute ll_route(const LlChannelDev &d, bool force_serial) {
+    LlRoute r;
+    const bool rice = d.len > 0 && (d.n_coeffs > 0 || d.shift_bits >= 128);
+    long long csum = 0;
+    for (unsigned q = 0; q < d.n_coeffs; q++) csum += d.coeffs[q] < 0 ? -(long long)d.coeffs[q] : (long long)d.coeffs[q];
+    bool ser = force_serial || (rice && d.rice_k > kRiceMaxK) || csum >= (1ll << 21) || (d.n_coeffs && (d.shift_bits & 63u) > 20u);
+    if (rice && d.len > 16u * 1024u * (unsigned)kRiceTileBits) ser = true;
+    r.serial = ser ? 1 : 0;
+    r.other = !(d.n_coeffs > 0 && d.n_coeffs <= 12 && d.len > 0 && d.samples > d.n_coeffs) ? 1 : 0;
+    r.tiles = rice && !ser ? (d.len + (unsigned)kRiceTileBits / 8u - 1u) / ((unsigned)kRiceTileBits / 8u) : 0u;
+    return r;
+}
+
+LlChannelDev ll_channel(uint64_t off, uint32_t len, uint8_t n_coeffs, uint8_t shift_bits, uint8_t rice_k, const int32_t *coeffs) {
+    LlChannelDev d{};
+    d.off = off;
+    d.len = len;
+    d.n_coeffs = n_coeffs;
+    d.shift_bits = shift_bits;
+    d.rice_k = rice_k;
+    memcpy(d.coeffs, coeffs, sizeof d.coeffs);
+    return d;
+}
+
+void LlWrapperList::clear() {
+    chs.clear();
+    tile0.assign(1, 0u);
+    serial.clear();
+    others.clear();
+    frs.clear();
+    scratch = 0;
+    max_tiles = max_samples = 0;
+}
+
+unsigned LlWrapperList::push(const LlChannelDev &d, const LlRoute &r) {
+    const unsigned i = (unsigned)chs.size();
+    chs.push_back(d);
+    chs.back().out_off = scratch;
+    scratch += d.samples;
+    serial.push_back(r.serial);
+    if (r.other) others.push_back(i);
+    tile0.push_back(tile0.back() + r.tiles);
+    if (r.tiles > max_tiles) max_tiles = r.tiles;
+    return i;
+}
+
+DescBlock::DescBlock(std::initializer_list<DescPart> parts) {
+    assert(parts.size() <= (size_t)kMaxParts);
+    for (const DescPart &p : parts) {
+        part[n] = p;
+        off[n++] = bytes;
+        bytes += (p.bytes + 255) & ~(size_t)255;
+    }
+}
+
+void DescBlock::fill(uint8_t *pin) const {
+    for (int i = 0; i < n; i++)
+        if (part[i].src && part[i].bytes) memcpy(pin + off[i], part[i].src, part[i].bytes);
+}
+
+StageRing::~StageRing() {
+    for (Slot &s : slots_) {
+        if (s.ev) hipEventSynchronize(s.ev), hipEventDestroy(s.ev);
+        if (s.pin) hipHostFree(s.pin);
+    }
+    if (ev_in_) hipEventDestroy(ev_in_);
+    if (ev_out_) hipEventDestroy(ev_out_);
+}
+
+bool StageRing::init() {
+    bool ok = true;
+    for (Slot &s : slots_)
+        if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) s.ev = nullptr, ok = false;
+    if (hipEventCreateWithFlags(&ev_in_, hipEventDisableTiming) != hipSuccess) ev_in_ = nullptr, ok = false;
+    if (hipEventCreateWithFlags(&ev_out_, hipEventDisableTiming) != hipSuccess) ev_out_ = nullptr, ok = false;
+    return ok;
+}
+
+int StageRing::acquire(flo_ctx *c, size_t bytes, uint8_t **pin) {
+    Slot &sl = slots_[next_++ % kSlots];
+    cur_ = &sl;
+    if (!sl.ev) return fail(c, FLO_ERR_DEVICE, "hipEventCreate failed");
+    if (sl.used) HIPCHK(c, hipEventSynchronize(sl.ev));
+    if (sl.cap < bytes) {
+        if (sl.pin) hipHostFree(sl.pin);
+        sl.pin = nullptr;
+        sl.cap = 0;
+        const size_t want = bytes + bytes / 4;
+        HIPCHK(c, hipHostMalloc(&sl.pin, want, hipHostMallocDefault));
+        sl.cap = want;
+    }
+    *pin = (uint8_t *)sl.pin;
+    return FLO_OK;
+}
+
+int StageRing::upload(flo_ctx *c, void *dst, size_t bytes) {
+    HIPCHK(c, hipMemcpyAsync(dst, cur_->pin, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(cur_->ev, c->stream));
+    cur_->used = true;
+    return FLO_OK;
+}
+
+int StageRing::fence_in(flo_ctx *c, hipStream_t caller) {
+    if (caller != c->stream) {
+        HIPCHK(c, hipEventRecord(ev_in_, caller));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, ev_in_, 0));
+    }
+    return FLO_OK;
+}
+
+int StageRing::fence_out(flo_ctx *c, hipStream_t caller) {
+    if (caller != c->stream) {
+        HIPCHK(c, hipEventRecord(ev_out_, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(caller, ev_out_, 0));
+    }
+    return FLO_OK;
+}
+
+int launch_ll_wrappers(flo_ctx *c, const LlWrapperList &w, const uint8_t *bytes, const LlChannelDev *d_ch, const unsigned int *d_tile0,
+                       int *d_serial, const unsigned int *d_others, int *scratch, unsigned int *tabs, uint2 *ent,
+                       const char *name_parallel, const char *name_serial) {
+    const unsigned n = (unsigned)w.chs.size();
+    LlParArgs P{bytes, d_ch, n, scratch, d_tile0, tabs, ent, d_serial, d_others, (unsigned)w.others.size()};
+    int rc = timed_launch(c, name_parallel, [&] { return launch_ll_decode_parallel(P, w.max_tiles, c->stream); });
+    if (rc != FLO_OK) return rc;
+    LlDecArgs S{bytes, d_ch, n, scratch, d_serial};
+    return timed_launch(c, name_serial, [&] { return launch_ll_decode(S, c->stream); });
+}

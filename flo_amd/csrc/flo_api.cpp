@@ -20,6 +20,7 @@
 #include "analysis_kernels.hpp"
 #include "container_kernels.hpp"
 #include "decode_kernels.hpp"
+#include "decode_plan.hpp"
 #include "devpool.hpp"
 #include "dist_engine.hpp"
 #include "stager.hpp"
@@ -1402,78 +1403,33 @@ static int download(flo_ctx *c, void *dst, const void *d_src, size_t bytes) {
     return done(FLO_OK);
 }
 
-// The channel wrappers and frames of one or more parsed lossless files whose bytes sit in one device buffer
-// (lossless/decoder.rs:21-72 per file). Output sample-frames follow each other file after file.
-struct LlWork {
-    std::vector<LlChannelDev> chs;
-    std::vector<LlFrameDev> frs;
-    unsigned long long scratch = 0, out_sf = 0;
-    unsigned max_samples = 0;
-    void add(const ParsedFile &f, uint64_t base, int nch) {
-        for (const FrameDesc &fr : f.frames) {
-            LlFrameDev fd{};
-            fd.out_off = out_sf;
-            fd.first_channel = (unsigned)chs.size();
-            fd.n_channels = fr.n_channels;
-            fd.samples = fr.samples;
-            fd.mid_side = (nch == 2 && (fr.flags & 1)) ? 1u : 0u;
-            for (unsigned k = 0; k < fr.n_channels; k++) {
-                const ChannelDesc &cd = f.channels_desc[fr.first_channel + k];
-                LlChannelDev d{};
-                d.off = base + cd.off;
-                d.out_off = scratch;
-                d.len = cd.len;
-                d.samples = fr.samples;
-                d.n_coeffs = cd.n_coeffs;
-                d.shift_bits = cd.shift_bits;
-                d.rice_k = cd.rice_k;
-                memcpy(d.coeffs, cd.coeffs, sizeof d.coeffs);
-                if (k < 2) fd.scratch_off[k] = scratch;
-                scratch += fr.samples;
-                chs.push_back(d);
-            }
-            out_sf += fr.samples;
-            if (fr.samples > max_samples) max_samples = fr.samples;
-            frs.push_back(fd);
-        }
-    }
-};
+// FLO_LL_DECODE_SERIAL: every wrapper to the serial kernel (read once per decode call)
+static bool ll_force_serial() { return getenv("FLO_LL_DECODE_SERIAL") != nullptr; }
 
-// Enqueue the decode of `w` on the ctx stream: integers per wrapper into a scratch, then mid/side, interleave and the
-// 1/32767 scale into d_out (f32, nullable) / d_out_i32 (nullable), both out_sf * nch elements. Returns when the
-// kernels have run.
-static int ll_decode_device(flo_ctx *c, const LlWork &w, const uint8_t *d_bytes, int nch, float *d_out, int *d_out_i32) {
-    const size_t n_out = (size_t)w.out_sf * (size_t)nch;
+// Frame `fr` of a parsed lossless file whose bytes start the device buffer, to sample-frame `out_off` of the output
+// (lossless/decoder.rs:21-72).
+static void add_parsed_frame(LlWrapperList &w, const ParsedFile &f, const FrameDesc &fr, uint64_t out_off, bool force_serial) {
+    w.add_frame(out_off, fr.samples, f.channels == 2 && (fr.flags & 1), fr.n_channels, force_serial, [&](unsigned k) {
+        const ChannelDesc &cd = f.channels_desc[fr.first_channel + k];
+        return ll_channel(cd.off, cd.len, cd.n_coeffs, cd.shift_bits, cd.rice_k, cd.coeffs);
+    });
+}
+
+// Enqueue the decode of `w` (out_sf sample-frames) on the ctx stream: integers per wrapper into a scratch, then
+// mid/side, interleave and the 1/32767 scale into d_out (f32, nullable) / d_out_i32 (nullable), both out_sf * nch
+// elements. Returns when the kernels have run.
+static int ll_decode_device(flo_ctx *c, const LlWrapperList &w, uint64_t out_sf, const uint8_t *d_bytes, int nch, float *d_out, int *d_out_i32) {
+    const size_t n_out = (size_t)out_sf * (size_t)nch;
     if (!n_out) return FLO_OK;
     const auto t_enter = std::chrono::steady_clock::now();
     DevMem d_desc, d_scr, d_tabs, d_ent;
     QuiesceOnExit quiesce_d_desc(c);
     int rc;
-    // Rice tiles per wrapper; wrappers the parallel form does not take (rice.rs k > 14; coefficient sums or shifts
-    // that would leave the exact range of the f64 recurrence: it holds r * 2^shift + sum c * s, |r|, |s| < 2^31, in
-    // 53 bits) go to the serial kernel
-    std::vector<unsigned int> tile0(w.chs.size() + 1, 0);
-    std::vector<int> serial(w.chs.size(), 0);
-    std::vector<unsigned int> others;
-    unsigned max_tiles = 0;
-    const bool force_serial = getenv("FLO_LL_DECODE_SERIAL") != nullptr;
-    for (size_t i = 0; i < w.chs.size(); i++) {
-        const LlChannelDev &d = w.chs[i];
-        const bool rice = d.len > 0 && (d.n_coeffs > 0 || d.shift_bits >= 128);
-        long long csum = 0;
-        for (unsigned q = 0; q < d.n_coeffs; q++) csum += d.coeffs[q] < 0 ? -(long long)d.coeffs[q] : (long long)d.coeffs[q];
-        if (force_serial || (rice && d.rice_k > kRiceMaxK) || csum >= (1ll << 21) || (d.n_coeffs && (d.shift_bits & 63u) > 20u)) serial[i] = 1;
-        if (rice && d.len > 16u * 1024u * (unsigned)kRiceTileBits) serial[i] = 1;   // the tile stages put a wrapper's tiles (four per workgroup at least) in gridDim.y (<= 65535)
-        if (!(d.n_coeffs > 0 && d.n_coeffs <= 12 && d.len > 0 && d.samples > d.n_coeffs)) others.push_back((unsigned)i);   // (what ll_predict's row form does not take)
-        const unsigned nt = rice && !serial[i] ? (d.len + (unsigned)kRiceTileBits / 8u - 1u) / ((unsigned)kRiceTileBits / 8u) : 0u;
-        tile0[i + 1] = tile0[i] + nt;
-        if (nt > max_tiles) max_tiles = nt;
-    }
     if (getenv("FLO_TRACE")) {
         size_t lpc = 0, lpc8 = 0, fixed = 0, other = 0, ser = 0;
         for (size_t i = 0; i < w.chs.size(); i++) {
             const LlChannelDev &d = w.chs[i];
-            if (serial[i]) ser++;
+            if (w.serial[i]) ser++;
             else if (d.n_coeffs && d.len) (d.n_coeffs <= 8 ? lpc8 : lpc)++;
             else if (d.len && d.shift_bits >= 128) fixed++;
             else other++;
@@ -1481,31 +1437,21 @@ static int ll_decode_device(flo_ctx *c, const LlWork &w, const uint8_t *d_bytes,
         fprintf(stderr, "[flo] ll decode: %zu wrappers: LPC order <= 8 %zu, order 9..12 %zu, fixed %zu, raw/silent/empty %zu, serial %zu\n", w.chs.size(), lpc8,
                 lpc, fixed, other, ser);
     }
-    // the four descriptor arrays go up as ONE copy out of pinned memory, queued in front of the kernels (four copies out
+    // the descriptor arrays go up as ONE copy out of pinned memory, queued in front of the kernels (a copy per array out
     // of pageable vectors each held the host until the driver had staged them: 0.15 ms of an idle device per call)
-    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_ch = 0, o_fr = up256(w.chs.size() * sizeof(LlChannelDev)), o_t0 = o_fr + up256(w.frs.size() * sizeof(LlFrameDev)),
-                 o_ser = o_t0 + up256(tile0.size() * sizeof(unsigned int)), o_oth = o_ser + up256(serial.size() * sizeof(int)),
-                 desc_bytes = o_oth + up256(others.size() * sizeof(unsigned int));
+    enum { kCh, kFr, kT0, kSer, kOth };
+    const DescBlock blk{desc_part(w.chs), desc_part(w.frs), desc_part(w.tile0), desc_part(w.serial), desc_part(w.others)};
     if ((rc = ctx_stager(c)) != FLO_OK) return rc;
     {
         std::string perr;
-        uint8_t *pin = (uint8_t *)stager_pinned(c->stager, desc_bytes, perr);
+        uint8_t *pin = (uint8_t *)stager_pinned(c->stager, blk.bytes, perr);
         if (!pin) return fail(c, FLO_ERR_NOMEM, perr);
-        memcpy(pin + o_ch, w.chs.data(), w.chs.size() * sizeof(LlChannelDev));
-        memcpy(pin + o_fr, w.frs.data(), w.frs.size() * sizeof(LlFrameDev));
-        memcpy(pin + o_t0, tile0.data(), tile0.size() * sizeof(unsigned int));
-        memcpy(pin + o_ser, serial.data(), serial.size() * sizeof(int));
-        memcpy(pin + o_oth, others.data(), others.size() * sizeof(unsigned int));
-        HIPCHK(c, pool_alloc(&d_desc.p, desc_bytes));
-        HIPCHK(c, hipMemcpyAsync(d_desc.p, pin, desc_bytes, hipMemcpyHostToDevice, c->stream));   // (read before this function's final synchronise)
+        blk.fill(pin);
+        HIPCHK(c, pool_alloc(&d_desc.p, blk.bytes));
+        HIPCHK(c, hipMemcpyAsync(d_desc.p, pin, blk.bytes, hipMemcpyHostToDevice, c->stream));   // (read before this function's final synchronise)
     }
-    LlChannelDev *const d_ch = reinterpret_cast<LlChannelDev *>(d_desc.as<uint8_t>() + o_ch);
-    LlFrameDev *const d_fr = reinterpret_cast<LlFrameDev *>(d_desc.as<uint8_t>() + o_fr);
-    unsigned int *const d_t0 = reinterpret_cast<unsigned int *>(d_desc.as<uint8_t>() + o_t0);
-    int *const d_ser = reinterpret_cast<int *>(d_desc.as<uint8_t>() + o_ser);
-    const unsigned int *const d_oth = reinterpret_cast<const unsigned int *>(d_desc.as<uint8_t>() + o_oth);
-    const size_t tiles = tile0.back();
+    const LlChannelDev *const d_ch = blk.at<const LlChannelDev>(d_desc.p, kCh);
+    const size_t tiles = w.tiles();
     hipError_t e = pool_alloc(&d_scr.p, w.scratch ? w.scratch * sizeof(int) : 16);
     if (e == hipSuccess) e = pool_alloc(&d_tabs.p, tiles ? tiles * kRiceStates * sizeof(unsigned int) : 16);
     if (e == hipSuccess) e = pool_alloc(&d_ent.p, tiles ? tiles * sizeof(uint2) : 16);
@@ -1517,20 +1463,53 @@ static int ll_decode_device(flo_ctx *c, const LlWork &w, const uint8_t *d_bytes,
     if (e == hipSuccess && d_out && partial) e = hipMemsetAsync(d_out, 0, n_out * sizeof(float), c->stream);
     if (e == hipSuccess && d_out_i32 && partial) e = hipMemsetAsync(d_out_i32, 0, n_out * sizeof(int), c->stream);
     if (e != hipSuccess) return fail(c, FLO_ERR_NOMEM, std::string("decode buffers: ") + hipGetErrorString(e));
-    LlParArgs P{d_bytes, d_ch, (unsigned)w.chs.size(), d_scr.as<int>(), d_t0, d_tabs.as<unsigned int>(), d_ent.as<uint2>(), d_ser, d_oth, (unsigned)others.size()};
-    rc = timed_launch(c, "ll_decode_parallel", [&] { return launch_ll_decode_parallel(P, max_tiles, c->stream); });
+    rc = launch_ll_wrappers(c, w, d_bytes, d_ch, blk.at<const unsigned int>(d_desc.p, kT0), blk.at<int>(d_desc.p, kSer),
+                            blk.at<const unsigned int>(d_desc.p, kOth), d_scr.as<int>(), d_tabs.as<unsigned int>(), d_ent.as<uint2>(),
+                            "ll_decode_parallel", "ll_decode");
     if (rc != FLO_OK) return rc;
-    LlDecArgs A{d_bytes, d_ch, (unsigned)w.chs.size(), d_scr.as<int>(), d_ser};
-    rc = timed_launch(c, "ll_decode", [&] { return launch_ll_decode(A, c->stream); });
-    if (rc != FLO_OK) return rc;
-    LlFinishArgs F{d_fr, d_ch, (unsigned)w.frs.size(), nch, d_scr.as<int>(), d_out, d_out_i32};
+    LlFinishArgs F{blk.at<const LlFrameDev>(d_desc.p, kFr), d_ch, (unsigned)w.frs.size(), nch, d_scr.as<int>(), d_out, d_out_i32};
     rc = timed_launch(c, "ll_finish", [&] { return launch_ll_finish(F, w.max_samples, c->stream); });
     if (rc != FLO_OK) return rc;
     if (getenv("FLO_TRACE"))
         fprintf(stderr, "[flo] ll decode: host time until the last launch %.0f us\n",
                 (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_enter).count() / 1e3);
-    // the descriptor uploads read pageable vectors that die with this frame, and the temporaries go back to the pool
+    // the temporaries go back to the pool
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FLO_OK;
+}
+
+// lossy_decode_kernel<kDecWhole> over the clips whose bytes sit at `bytes`: the frame and clip tables and a cleared
+// error word go up, the kernel runs, the error word comes back (the ctx stream is idle on return). FLO_ERR_FORMAT when a
+// frame does not deserialise.
+static int lossy_decode_whole(flo_ctx *c, const TableSet *ts, const uint8_t *bytes, int channels, const std::vector<unsigned long long> &blob_off,
+                              const std::vector<unsigned int> &blob_len, const std::vector<unsigned long long> &clip_frame0,
+                              const std::vector<unsigned int> &clip_frames, const std::vector<unsigned long long> &clip_out,
+                              unsigned max_frames, float *out) {
+    DevMem d_off, d_len, d_c0, d_cn, d_co, d_err;
+    QuiesceOnExit quiesce_d_off(c);
+    const std::vector<int> zero{0};
+    int rc;
+    if ((rc = upload(c, d_off, blob_off)) || (rc = upload(c, d_len, blob_len)) || (rc = upload(c, d_c0, clip_frame0)) ||
+        (rc = upload(c, d_cn, clip_frames)) || (rc = upload(c, d_co, clip_out)) || (rc = upload(c, d_err, zero)))
+        return rc;
+    LossyDecArgs A{};
+    A.T = ts->dev;
+    A.window = ts->dev_window;
+    A.bytes = bytes;
+    A.blob_off = d_off.as<unsigned long long>();
+    A.blob_len = d_len.as<unsigned int>();
+    A.clip_frame0 = d_c0.as<unsigned long long>();
+    A.clip_frames = d_cn.as<unsigned int>();
+    A.clip_out = d_co.as<unsigned long long>();
+    A.n_clips = (int)clip_frame0.size();
+    A.channels = channels;
+    A.out = out;
+    A.error = d_err.as<int>();
+    if ((rc = timed_launch(c, "lossy_decode", [&] { return launch_lossy_decode(A, max_frames, c->stream); })) != FLO_OK) return rc;
+    int herr = 0;
+    HIPCHK(c, hipMemcpyAsync(&herr, d_err.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (herr) return fail(c, FLO_ERR_FORMAT, "Failed to deserialize transform frame");
     return FLO_OK;
 }
 
@@ -1584,44 +1563,16 @@ static int decode_impl(flo_ctx *c, const uint8_t *flo, size_t len, float **pcm, 
                 free(host);
                 return rc;
             }
-            DevMem d_off, d_len, d_c0, d_cn, d_co, d_out, d_err;
-            QuiesceOnExit quiesce_d_off(c);
-            std::vector<unsigned long long> c0{0}, co{0};
-            std::vector<unsigned int> cn{(unsigned int)nf};
-            std::vector<int> zero{0};
-            if ((rc = upload(c, d_off, blob_off)) || (rc = upload(c, d_len, blob_len)) || (rc = upload(c, d_c0, c0)) ||
-                (rc = upload(c, d_cn, cn)) || (rc = upload(c, d_co, co)) || (rc = upload(c, d_err, zero))) {
-                free(host);
-                return rc;
-            }
+            DevMem d_out;
+            QuiesceOnExit quiesce_d_out(c);
             hipError_t e = pool_alloc(&d_out.p, n_out ? n_out * sizeof(float) : 16);
             // (no clearing: the decode kernel writes every sample of every output block exactly once)
             if (e != hipSuccess) {
                 free(host);
                 return fail(c, FLO_ERR_NOMEM, std::string("decode output: ") + hipGetErrorString(e));
             }
-            LossyDecArgs A{};
-            A.T = ts->dev;
-            A.window = ts->dev_window;
-            A.bytes = d_bytes.as<uint8_t>();
-            A.blob_off = d_off.as<unsigned long long>();
-            A.blob_len = d_len.as<unsigned int>();
-            A.clip_frame0 = d_c0.as<unsigned long long>();
-            A.clip_frames = d_cn.as<unsigned int>();
-            A.clip_out = d_co.as<unsigned long long>();
-            A.n_clips = 1;
-            A.channels = nch;
-            A.out = d_out.as<float>();
-            A.error = d_err.as<int>();
-            rc = timed_launch(c, "lossy_decode", [&] { return launch_lossy_decode(A, (unsigned)nf, c->stream); });
-            int herr = 0;
-            if (rc == FLO_OK) {
-                e = hipMemcpyAsync(&herr, d_err.p, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) rc = fail(c, FLO_ERR_DEVICE, std::string("lossy decode: ") + hipGetErrorString(e));
-                if (rc == FLO_OK && n_out && !herr) rc = download(c, host, d_out.p, n_out * sizeof(float));
-            }
-            if (rc == FLO_OK && herr) rc = fail(c, FLO_ERR_FORMAT, "Failed to deserialize transform frame");
+            rc = lossy_decode_whole(c, ts, d_bytes.as<uint8_t>(), nch, blob_off, blob_len, {0}, {(unsigned int)nf}, {0}, (unsigned)nf, d_out.as<float>());
+            if (rc == FLO_OK && n_out) rc = download(c, host, d_out.p, n_out * sizeof(float));
             if (rc != FLO_OK) {
                 free(host);
                 return rc;
@@ -1633,9 +1584,14 @@ static int decode_impl(flo_ctx *c, const uint8_t *flo, size_t len, float **pcm, 
     }
 
     // lossless (lossless/decoder.rs:21-72)
-    LlWork w;
-    w.add(f, 0, nch);
-    const size_t n_out = nch ? (size_t)w.out_sf * (size_t)nch : 0;
+    LlWrapperList w;
+    uint64_t out_sf = 0;
+    const bool force_serial = ll_force_serial();
+    for (const FrameDesc &fr : f.frames) {
+        add_parsed_frame(w, f, fr, out_sf, force_serial);
+        out_sf += fr.samples;
+    }
+    const size_t n_out = nch ? (size_t)out_sf * (size_t)nch : 0;
     float *host = pcm ? (float *)alloc_result(n_out * sizeof(float)) : nullptr;
     int32_t *host_i = pcm_i32 ? (int32_t *)alloc_result(n_out * sizeof(int32_t)) : nullptr;
     auto bail = [&](int rc) {
@@ -1652,7 +1608,7 @@ static int decode_impl(flo_ctx *c, const uint8_t *flo, size_t len, float **pcm, 
         if (host) e = pool_alloc(&d_out.p, n_out * sizeof(float));
         if (e == hipSuccess && host_i) e = pool_alloc(&d_outi.p, n_out * sizeof(int));
         if (e != hipSuccess) return bail(fail(c, FLO_ERR_NOMEM, std::string("decode buffers: ") + hipGetErrorString(e)));
-        if ((rc = ll_decode_device(c, w, d_bytes.as<uint8_t>(), nch, d_out.as<float>(), d_outi.as<int>())) != FLO_OK) return bail(rc);
+        if ((rc = ll_decode_device(c, w, out_sf, d_bytes.as<uint8_t>(), nch, d_out.as<float>(), d_outi.as<int>())) != FLO_OK) return bail(rc);
         if (host && (rc = download(c, host, d_out.p, n_out * sizeof(float))) != FLO_OK) return bail(rc);
         if (host_i && (rc = download(c, host_i, d_outi.p, n_out * sizeof(int))) != FLO_OK) return bail(rc);
         e = hipStreamSynchronize(c->stream);
@@ -1677,44 +1633,27 @@ static int batch_decode_lossless(flo_batch *b, float *dst, size_t dst_cap, uint6
     const auto t_0 = std::chrono::steady_clock::now();
     if (lossless_describe(b->ll, fr, wr, &base, err) != 0) return fail(c, FLO_ERR_STATE, err);
     const auto t_1 = std::chrono::steady_clock::now();
-    LlWork w;
+    LlWrapperList w;
     w.chs.reserve(wr.size());
     w.frs.reserve(fr.size());
+    uint64_t out_sf = 0;
+    const bool force_serial = ll_force_serial();
     for (size_t i = 0; i < b->n_clips; i++) offsets[i] = 0;
     uint32_t cur = 0xFFFFFFFFu;
     for (const LosslessFrameInfo &f : fr) {
         if (f.clip != cur) {   // frames are in clip order: a clip's PCM starts where its first frame's does
             cur = f.clip;
-            if (cur < b->n_clips) offsets[cur] = w.out_sf * b->ch;
+            if (cur < b->n_clips) offsets[cur] = out_sf * b->ch;
         }
-        LlFrameDev fd{};
-        fd.out_off = w.out_sf;
-        fd.first_channel = (unsigned)w.chs.size();
-        fd.n_channels = f.n_wrappers;
-        fd.samples = f.samples;
-        fd.mid_side = (b->ch == 2 && (f.flags & 1)) ? 1u : 0u;
-        for (uint32_t k = 0; k < f.n_wrappers; k++) {
+        w.add_frame(out_sf, f.samples, b->ch == 2 && (f.flags & 1), f.n_wrappers, force_serial, [&](unsigned k) {
             const LosslessWrapperInfo &x = wr[f.first_wrapper + k];
-            LlChannelDev d{};
-            d.off = x.off;
-            d.out_off = w.scratch;
-            d.len = x.len;
-            d.samples = f.samples;
-            d.n_coeffs = x.n_coeffs;
-            d.shift_bits = x.shift_bits;
-            d.rice_k = x.rice_k;
-            memcpy(d.coeffs, x.coeffs, sizeof d.coeffs);
-            if (k < 2) fd.scratch_off[k] = w.scratch;
-            w.scratch += f.samples;
-            w.chs.push_back(d);
-        }
-        w.out_sf += f.samples;
-        if (f.samples > w.max_samples) w.max_samples = f.samples;
-        w.frs.push_back(fd);
+            return ll_channel(x.off, x.len, x.n_coeffs, x.shift_bits, x.rice_k, x.coeffs);
+        });
+        out_sf += f.samples;
     }
     // clips without frames (empty input) keep the offset of whatever follows them
     {
-        uint64_t next = w.out_sf * b->ch;
+        uint64_t next = out_sf * b->ch;
         std::vector<char> has(b->n_clips, 0);
         for (const LosslessFrameInfo &f : fr)
             if (f.clip < b->n_clips) has[f.clip] = 1;
@@ -1723,10 +1662,10 @@ static int batch_decode_lossless(flo_batch *b, float *dst, size_t dst_cap, uint6
             else offsets[i] = next;
         }
     }
-    const uint64_t total = w.out_sf * b->ch;
+    const uint64_t total = out_sf * b->ch;
     if (total > dst_cap) return fail(c, FLO_ERR_ARG, "destination too small for the decoded batch");
     const auto t_2 = std::chrono::steady_clock::now();
-    const int rc = ll_decode_device(c, w, base, b->ch, dst, nullptr);
+    const int rc = ll_decode_device(c, w, out_sf, base, b->ch, dst, nullptr);
     if (trace) {
         const auto t_3 = std::chrono::steady_clock::now();
         auto us = [](auto a, auto b2) { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(b2 - a).count() / 1e3; };
@@ -1769,34 +1708,8 @@ extern "C" int flo_batch_decode(flo_batch *b, float *dst, size_t dst_cap, uint64
     }
     if (total > dst_cap) return fail(c, FLO_ERR_ARG, "destination too small for the decoded batch");
     if (!total) return FLO_OK;
-    DevMem d_off, d_len, d_c0, d_cn, d_co, d_err;
-    QuiesceOnExit quiesce_d_off(c);
-    std::vector<int> zero{0};
-    int rc;
-    if ((rc = upload(c, d_off, blob_off)) || (rc = upload(c, d_len, blob_len)) || (rc = upload(c, d_c0, c0)) ||
-        (rc = upload(c, d_cn, cn)) || (rc = upload(c, d_co, co)) || (rc = upload(c, d_err, zero)))
-        return rc;
     // (dst needs no clearing: the decode kernel writes every sample of every output block exactly once)
-    LossyDecArgs A{};
-    A.T = b->ts->dev;
-    A.window = b->ts->dev_window;
-    A.bytes = b->d_out;
-    A.blob_off = d_off.as<unsigned long long>();
-    A.blob_len = d_len.as<unsigned int>();
-    A.clip_frame0 = d_c0.as<unsigned long long>();
-    A.clip_frames = d_cn.as<unsigned int>();
-    A.clip_out = d_co.as<unsigned long long>();
-    A.n_clips = (int)b->n_clips;
-    A.channels = b->ch;
-    A.out = dst;
-    A.error = d_err.as<int>();
-    rc = timed_launch(c, "lossy_decode", [&] { return launch_lossy_decode(A, max_hops, c->stream); });
-    if (rc != FLO_OK) return rc;
-    int herr = 0;
-    HIPCHK(c, hipMemcpyAsync(&herr, d_err.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (herr) return fail(c, FLO_ERR_FORMAT, "Failed to deserialize transform frame");
-    return FLO_OK;
+    return lossy_decode_whole(c, b->ts, b->d_out, b->ch, blob_off, blob_len, c0, cn, co, max_hops, dst);
 }
 
 extern "C" int flo_decode(flo_ctx *c, const uint8_t *flo, size_t len, float **pcm, size_t *n_interleaved,
@@ -1832,14 +1745,9 @@ extern "C" int flo_decode_frame_at(flo_ctx *c, const uint8_t *flo, size_t len, u
     HIPCHK(c, pool_alloc(&d_bytes.p, len + 32));
     HIPCHK(c, hipMemcpyAsync(d_bytes.p, flo, len, hipMemcpyHostToDevice, c->stream));
     if (fr.type != 253) {
-        ParsedFile one;
-        one.channels = f.channels;
-        one.frames.push_back(fr);
-        one.frames[0].first_channel = 0;
-        for (unsigned k = 0; k < fr.n_channels; k++) one.channels_desc.push_back(f.channels_desc[fr.first_channel + k]);
-        LlWork w;
-        w.add(one, 0, nch);
-        const size_t n_out = nch ? (size_t)w.out_sf * (size_t)nch : 0;
+        LlWrapperList w;
+        add_parsed_frame(w, f, fr, 0, ll_force_serial());
+        const size_t n_out = nch ? (size_t)fr.samples * (size_t)nch : 0;
         float *host = (float *)malloc(n_out ? n_out * sizeof(float) : 1);
         if (!host) return fail(c, FLO_ERR_NOMEM, "out of host memory");
         if (n_out) {
@@ -1850,7 +1758,7 @@ extern "C" int flo_decode_frame_at(flo_ctx *c, const uint8_t *flo, size_t len, u
                 free(host);
                 return fail(c, FLO_ERR_NOMEM, "decode buffers");
             }
-            if ((rc = ll_decode_device(c, w, d_bytes.as<uint8_t>(), nch, d_out.as<float>(), nullptr)) != FLO_OK ||
+            if ((rc = ll_decode_device(c, w, fr.samples, d_bytes.as<uint8_t>(), nch, d_out.as<float>(), nullptr)) != FLO_OK ||
                 (rc = download(c, host, d_out.p, n_out * sizeof(float))) != FLO_OK) {
                 free(host);
                 return rc;
@@ -1882,39 +1790,15 @@ extern "C" int flo_decode_frame_at(flo_ctx *c, const uint8_t *flo, size_t len, u
     int rc = get_tables(c, f.sample_rate, 0.5f, &ts);
     if (rc != FLO_OK) return rc;
     const size_t n_out = 1024 * (size_t)nch;
-    DevMem d_off, d_len, d_c0, d_cn, d_co, d_out, d_err;
-    QuiesceOnExit quiesce_d_off(c);
-    std::vector<unsigned long long> c0{0}, co{0};
-    std::vector<unsigned int> cn{2u};
-    std::vector<int> zero{0};
-    if ((rc = upload(c, d_off, blob_off)) || (rc = upload(c, d_len, blob_len)) || (rc = upload(c, d_c0, c0)) ||
-        (rc = upload(c, d_cn, cn)) || (rc = upload(c, d_co, co)) || (rc = upload(c, d_err, zero)))
-        return rc;
+    DevMem d_out;
+    QuiesceOnExit quiesce_d_out(c);
     HIPCHK(c, pool_alloc(&d_out.p, n_out * sizeof(float)));
-    LossyDecArgs A{};
-    A.T = ts->dev;
-    A.window = ts->dev_window;
-    A.bytes = d_bytes.as<uint8_t>();
-    A.blob_off = d_off.as<unsigned long long>();
-    A.blob_len = d_len.as<unsigned int>();
-    A.clip_frame0 = d_c0.as<unsigned long long>();
-    A.clip_frames = d_cn.as<unsigned int>();
-    A.clip_out = d_co.as<unsigned long long>();
-    A.n_clips = 1;
-    A.channels = nch;
-    A.out = d_out.as<float>();
-    A.error = d_err.as<int>();
-    if ((rc = timed_launch(c, "lossy_decode", [&] { return launch_lossy_decode(A, 2u, c->stream); })) != FLO_OK) return rc;
+    if ((rc = lossy_decode_whole(c, ts, d_bytes.as<uint8_t>(), nch, blob_off, blob_len, {0}, {2u}, {0}, 2u, d_out.as<float>())) != FLO_OK) return rc;
     float *host = (float *)malloc(n_out * sizeof(float));
     if (!host) return fail(c, FLO_ERR_NOMEM, "out of host memory");
-    int herr = 0;
-    hipError_t e = hipMemcpyAsync(&herr, d_err.p, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(host, d_out.p, n_out * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || herr) {
+    if ((rc = download(c, host, d_out.p, n_out * sizeof(float))) != FLO_OK) {
         free(host);
-        return e != hipSuccess ? fail(c, FLO_ERR_DEVICE, std::string("decode_frame_at: ") + hipGetErrorString(e))
-                               : fail(c, FLO_ERR_FORMAT, "Failed to deserialize transform frame");
+        return rc;
     }
     *pcm = host;
     *n_interleaved = n_out;

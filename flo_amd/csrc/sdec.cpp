@@ -21,12 +21,12 @@
 #include "container.hpp"
 #include "ctx_internal.hpp"
 #include "decode_kernels.hpp"
+#include "decode_plan.hpp"
 #include "devpool.hpp"
 
 namespace {
 constexpr size_t kHeaderBytes = 70;           // try_parse_header reads a fixed 70 bytes (:177-180)
 constexpr uint32_t kMaxFrameSamples = 2000000;   // the container reader's limit (reader.rs); the device path keeps it
-constexpr int kStageSlots = 8;                // pinned descriptor slots in flight
 
 uint16_t rd16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -145,13 +145,6 @@ struct SdPlan {
     std::string err;
     bool finish = false;   // a next_frame call would find current_frame >= toc.len() (:93-96)
 };
-
-struct Slot {
-    void *pin = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;
-    bool used = false;
-};
 }  // namespace
 
 struct flo_sdec {
@@ -180,11 +173,9 @@ struct flo_sdec {
 
 // The per-context workspace of flo_sdec_decode_ready: staging slots, device blocks that only grow, host lists.
 struct SdecWork {
-    Slot slots[kStageSlots];
-    unsigned next_slot = 0;
+    StageRing ring;
     void *desc = nullptr, *scr = nullptr, *tabs = nullptr, *ent = nullptr;
     size_t desc_cap = 0, scr_cap = 0, tabs_cap = 0, ent_cap = 0;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
     std::vector<SdPlan> plans;
     // the plans of the last sizing call (NULL destination), reused by a call with the same decoders, cap and versions
     bool sized = false;
@@ -194,10 +185,7 @@ struct SdecWork {
     std::vector<LossyRunDev> runs;
     std::vector<unsigned long long> blob_off;
     std::vector<unsigned int> blob_len;
-    std::vector<LlChannelDev> chs;
-    std::vector<LlFrameDev> frs;
-    std::vector<unsigned int> tile0, others;
-    std::vector<int> serial;
+    LlWrapperList ll;
     std::vector<std::pair<const uint8_t *, uint32_t>> segs;   // payload bytes to gather, in upload order
 };
 
@@ -207,12 +195,6 @@ void sdec_work_free(flo_ctx *c) {
     hipStreamSynchronize(c->stream);
     for (void *p : {w->desc, w->scr, w->tabs, w->ent})
         if (p) pool_free(p);
-    for (Slot &s : w->slots) {
-        if (s.ev) hipEventSynchronize(s.ev), hipEventDestroy(s.ev);
-        if (s.pin) hipHostFree(s.pin);
-    }
-    if (w->ev_in) hipEventDestroy(w->ev_in);
-    if (w->ev_out) hipEventDestroy(w->ev_out);
     delete w;
     c->sdec = nullptr;
 }
@@ -414,10 +396,7 @@ int grow(flo_ctx *ctx, void *&p, size_t &cap, size_t bytes) {
 SdecWork *work(flo_ctx *ctx) {
     if (ctx->sdec) return ctx->sdec;
     SdecWork *w = new SdecWork();
-    for (Slot &s : w->slots)
-        if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) s.ev = nullptr;
-    hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming);
-    hipEventCreateWithFlags(&w->ev_out, hipEventDisableTiming);
+    w->ring.init();   // (a slot without its event fails when it is taken)
     ctx->sdec = w;
     return w;
 }
@@ -431,14 +410,9 @@ int launch_plans(flo_ctx *ctx, SdecWork *w, size_t n, flo_sdec *const *decs, con
     w->runs.clear();
     w->blob_off.clear();
     w->blob_len.clear();
-    w->chs.clear();
-    w->frs.clear();
-    w->tile0.assign(1, 0u);
-    w->others.clear();
-    w->serial.clear();
+    w->ll.clear();
     w->segs.clear();
-    uint64_t bytes_up = 0, scratch = 0;
-    unsigned max_tiles = 0, max_samples = 0;
+    uint64_t bytes_up = 0;
     auto add_seg = [&](const uint8_t *p, uint32_t len) -> uint64_t {   // -> the payload's offset in the uploaded bytes
         const uint64_t at = bytes_up;
         w->segs.push_back({p, len});
@@ -527,131 +501,70 @@ int launch_plans(flo_ctx *ctx, SdecWork *w, size_t n, flo_sdec *const *decs, con
             frame_span(d, it.frame, s, e);
             const uint8_t *fb = d->buffer.data() + s;
             parse_frame(fb, (uint32_t)(e - s), d->info.channels, f, &perr);
-            LlFrameDev fd{};
-            fd.out_off = at / ch;
-            fd.first_channel = (unsigned)w->chs.size();
-            fd.n_channels = (unsigned)f.ch.size();
-            fd.samples = f.samples;
-            fd.mid_side = (ch == 2 && (f.flags & 1)) ? 1u : 0u;
-            for (size_t k = 0; k < f.ch.size(); k++) {
+            w->ll.add_frame(at / ch, f.samples, ch == 2 && (f.flags & 1), (unsigned)f.ch.size(), false, [&](unsigned k) {
                 const SdChannel &sc = f.ch[k];
-                LlChannelDev c{};
-                c.off = sc.len ? add_seg(fb + sc.off, sc.len) : 0;
-                c.out_off = scratch;
-                c.len = sc.len;
-                c.samples = f.samples;
-                c.n_coeffs = sc.n_coeffs;
-                c.shift_bits = sc.shift;
-                c.rice_k = sc.rice_k;
-                memcpy(c.coeffs, sc.coeffs, sizeof c.coeffs);
-                if (k < 2) fd.scratch_off[k] = scratch;
-                scratch += f.samples;
-                // which kernels take the wrapper: the same rules as flo_decode (ll_decode_device in flo_api.cpp)
-                const bool rice = c.len > 0 && (c.n_coeffs > 0 || c.shift_bits >= 128);
-                long long csum = 0;
-                for (unsigned q = 0; q < c.n_coeffs; q++) csum += c.coeffs[q] < 0 ? -(long long)c.coeffs[q] : (long long)c.coeffs[q];
-                bool ser = (rice && c.rice_k > kRiceMaxK) || csum >= (1ll << 21) || (c.n_coeffs && (c.shift_bits & 63u) > 20u);
-                if (rice && c.len > 16u * 1024u * (unsigned)kRiceTileBits) ser = true;
-                const unsigned idx = (unsigned)w->chs.size();
-                w->serial.push_back(ser ? 1 : 0);
-                if (!(c.n_coeffs > 0 && c.n_coeffs <= 12 && c.len > 0 && c.samples > c.n_coeffs)) w->others.push_back(idx);
-                const unsigned nt = rice && !ser ? (c.len + (unsigned)kRiceTileBits / 8u - 1u) / ((unsigned)kRiceTileBits / 8u) : 0u;
-                w->tile0.push_back(w->tile0.back() + nt);
-                max_tiles = std::max(max_tiles, nt);
-                w->chs.push_back(c);
-            }
-            max_samples = std::max(max_samples, f.samples);
-            w->frs.push_back(fd);
+                return ll_channel(sc.len ? add_seg(fb + sc.off, sc.len) : 0, sc.len, sc.n_coeffs, sc.shift, sc.rice_k, sc.coeffs);
+            });
             at += it.floats;
         }
     }
-    if (w->runs.empty() && w->chs.empty()) return FLO_OK;
+    const LlWrapperList &ll = w->ll;
+    if (w->runs.empty() && ll.chs.empty()) return FLO_OK;
     TableSet *ts = nullptr;
     int rc;
     if (!w->runs.empty() && (rc = get_tables(ctx, sr, 0.5f, &ts)) != FLO_OK) return rc;
-    // one block: [runs][blob_off][blob_len][wrappers][tile0][serial][others][frames][error word][payload bytes + slack]
-    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_run = 0, o_bo = up256(w->runs.size() * sizeof(LossyRunDev)), o_bl = o_bo + up256(w->blob_off.size() * sizeof(unsigned long long)),
-                 o_ch = o_bl + up256(w->blob_len.size() * sizeof(unsigned int)), o_t0 = o_ch + up256(w->chs.size() * sizeof(LlChannelDev)),
-                 o_ser = o_t0 + up256(w->tile0.size() * sizeof(unsigned int)), o_oth = o_ser + up256(w->serial.size() * sizeof(int)),
-                 o_fr = o_oth + up256(w->others.size() * sizeof(unsigned int)), o_err = o_fr + up256(w->frs.size() * sizeof(LlFrameDev)),
-                 o_by = o_err + 256, bytes = o_by + up256(bytes_up + 32);   // (the lossy kernel reads up to three bytes past a blob)
-    Slot &sl = w->slots[w->next_slot++ % kStageSlots];
-    if (!sl.ev) return fail(ctx, FLO_ERR_DEVICE, "hipEventCreate failed");
-    if (sl.used) HIPCHK(ctx, hipEventSynchronize(sl.ev));   // reused only after the copy out of it has completed
-    if (sl.cap < bytes) {
-        if (sl.pin) hipHostFree(sl.pin);
-        sl.pin = nullptr;
-        sl.cap = 0;
-        const size_t want = bytes + bytes / 4;
-        HIPCHK(ctx, hipHostMalloc(&sl.pin, want, hipHostMallocDefault));
-        sl.cap = want;
-    }
-    uint8_t *pin = (uint8_t *)sl.pin;
-    memcpy(pin + o_run, w->runs.data(), w->runs.size() * sizeof(LossyRunDev));
-    memcpy(pin + o_bo, w->blob_off.data(), w->blob_off.size() * sizeof(unsigned long long));
-    memcpy(pin + o_bl, w->blob_len.data(), w->blob_len.size() * sizeof(unsigned int));
-    memcpy(pin + o_ch, w->chs.data(), w->chs.size() * sizeof(LlChannelDev));
-    memcpy(pin + o_t0, w->tile0.data(), w->tile0.size() * sizeof(unsigned int));
-    memcpy(pin + o_ser, w->serial.data(), w->serial.size() * sizeof(int));
-    memcpy(pin + o_oth, w->others.data(), w->others.size() * sizeof(unsigned int));
-    memcpy(pin + o_fr, w->frs.data(), w->frs.size() * sizeof(LlFrameDev));
-    memset(pin + o_err, 0, 256);
+    // one block, the payload bytes last (the lossy kernel reads up to three bytes past a blob)
+    enum { kRun, kBlobOff, kBlobLen, kCh, kT0, kSer, kOth, kFr, kErr, kBytes };
+    const DescBlock blk{desc_part(w->runs), desc_part(w->blob_off), desc_part(w->blob_len), desc_part(ll.chs), desc_part(ll.tile0),
+                        desc_part(ll.serial), desc_part(ll.others), desc_part(ll.frs), {nullptr, 256}, {nullptr, bytes_up + 32}};
+    uint8_t *pin;
+    if ((rc = w->ring.acquire(ctx, blk.bytes, &pin)) != FLO_OK) return rc;
+    blk.fill(pin);
+    memset(pin + blk.off[kErr], 0, 256);
     {
+        uint8_t *by = pin + blk.off[kBytes];
         uint64_t at = 0;
         for (const auto &sg : w->segs) {
-            memcpy(pin + o_by + at, sg.first, sg.second);
+            memcpy(by + at, sg.first, sg.second);
             at += ((uint64_t)sg.second + 15) & ~(uint64_t)15;
         }
-        memset(pin + o_by + at, 0, 32);
+        memset(by + at, 0, 32);
     }
-    if ((rc = grow(ctx, w->desc, w->desc_cap, bytes)) != FLO_OK) return rc;
-    if (!w->chs.empty()) {
-        const size_t tiles = w->tile0.back();
-        if ((rc = grow(ctx, w->scr, w->scr_cap, (scratch ? scratch : 1) * sizeof(int))) != FLO_OK ||
+    if ((rc = grow(ctx, w->desc, w->desc_cap, blk.bytes)) != FLO_OK) return rc;
+    if (!ll.chs.empty()) {
+        const size_t tiles = ll.tiles();
+        if ((rc = grow(ctx, w->scr, w->scr_cap, (ll.scratch ? ll.scratch : 1) * sizeof(int))) != FLO_OK ||
             (rc = grow(ctx, w->tabs, w->tabs_cap, (tiles ? tiles : 1) * kRiceStates * sizeof(unsigned int))) != FLO_OK ||
             (rc = grow(ctx, w->ent, w->ent_cap, (tiles ? tiles : 1) * sizeof(uint2))) != FLO_OK)
             return rc;
     }
     hipStream_t cs = ctx->stream;
-    if (us != cs) {
-        HIPCHK(ctx, hipEventRecord(w->ev_in, us));
-        HIPCHK(ctx, hipStreamWaitEvent(cs, w->ev_in, 0));
-    }
-    uint8_t *dd = (uint8_t *)w->desc;
-    HIPCHK(ctx, hipMemcpyAsync(dd, pin, bytes, hipMemcpyHostToDevice, cs));
-    HIPCHK(ctx, hipEventRecord(sl.ev, cs));
-    sl.used = true;
-    const uint8_t *d_bytes = dd + o_by;
+    if ((rc = w->ring.fence_in(ctx, us)) != FLO_OK || (rc = w->ring.upload(ctx, w->desc, blk.bytes)) != FLO_OK) return rc;
+    void *dd = w->desc;
+    const uint8_t *d_bytes = blk.at<const uint8_t>(dd, kBytes);
     if (!w->runs.empty()) {
         LossyDecArgs A{};
         A.T = ts->dev;
         A.window = ts->dev_window;
         A.bytes = d_bytes;
-        A.blob_off = reinterpret_cast<const unsigned long long *>(dd + o_bo);
-        A.blob_len = reinterpret_cast<const unsigned int *>(dd + o_bl);
+        A.blob_off = blk.at<const unsigned long long>(dd, kBlobOff);
+        A.blob_len = blk.at<const unsigned int>(dd, kBlobLen);
         A.channels = nch;
         A.out = dst;
-        A.error = reinterpret_cast<int *>(dd + o_err);   // (never set: the host has checked every frame)
-        LossyStreamArgs S{reinterpret_cast<const LossyRunDev *>(dd + o_run), (unsigned)w->runs.size(), 0u};
+        A.error = blk.at<int>(dd, kErr);   // (never set: the host has checked every frame)
+        LossyStreamArgs S{blk.at<const LossyRunDev>(dd, kRun), (unsigned)w->runs.size(), 0u};
         if ((rc = timed_launch(ctx, "sdec_lossy", [&] { return launch_lossy_stream(A, S, cs); })) != FLO_OK) return rc;
     }
-    if (!w->chs.empty()) {
-        const LlChannelDev *d_ch = reinterpret_cast<const LlChannelDev *>(dd + o_ch);
-        int *d_ser = reinterpret_cast<int *>(dd + o_ser);
-        LlParArgs P{d_bytes, d_ch, (unsigned)w->chs.size(), (int *)w->scr, reinterpret_cast<const unsigned int *>(dd + o_t0),
-                    (unsigned int *)w->tabs, (uint2 *)w->ent, d_ser, reinterpret_cast<const unsigned int *>(dd + o_oth), (unsigned)w->others.size()};
-        if ((rc = timed_launch(ctx, "sdec_ll_decode_parallel", [&] { return launch_ll_decode_parallel(P, max_tiles, cs); })) != FLO_OK) return rc;
-        LlDecArgs S{d_bytes, d_ch, (unsigned)w->chs.size(), (int *)w->scr, d_ser};
-        if ((rc = timed_launch(ctx, "sdec_ll_decode", [&] { return launch_ll_decode(S, cs); })) != FLO_OK) return rc;
-        LlFinishArgs F{reinterpret_cast<const LlFrameDev *>(dd + o_fr), d_ch, (unsigned)w->frs.size(), nch, (const int *)w->scr, dst, nullptr};
-        if ((rc = timed_launch(ctx, "sdec_ll_finish", [&] { return launch_ll_finish(F, max_samples, cs); })) != FLO_OK) return rc;
+    if (!ll.chs.empty()) {
+        const LlChannelDev *d_ch = blk.at<const LlChannelDev>(dd, kCh);
+        if ((rc = launch_ll_wrappers(ctx, ll, d_bytes, d_ch, blk.at<const unsigned int>(dd, kT0), blk.at<int>(dd, kSer),
+                                     blk.at<const unsigned int>(dd, kOth), (int *)w->scr, (unsigned int *)w->tabs, (uint2 *)w->ent,
+                                     "sdec_ll_decode_parallel", "sdec_ll_decode")) != FLO_OK)
+            return rc;
+        LlFinishArgs F{blk.at<const LlFrameDev>(dd, kFr), d_ch, (unsigned)ll.frs.size(), nch, (const int *)w->scr, dst, nullptr};
+        if ((rc = timed_launch(ctx, "sdec_ll_finish", [&] { return launch_ll_finish(F, ll.max_samples, cs); })) != FLO_OK) return rc;
     }
-    if (us != cs) {
-        HIPCHK(ctx, hipEventRecord(w->ev_out, cs));
-        HIPCHK(ctx, hipStreamWaitEvent(us, w->ev_out, 0));
-    }
-    return FLO_OK;
+    return w->ring.fence_out(ctx, us);
 }
 
 // decode_with_standard_decoder for transform files (:741-767) skips a frame that does not deserialise; flo_decode fails on

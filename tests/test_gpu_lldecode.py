@@ -5,6 +5,7 @@ ABI. Needs an MI355X."""
 import numpy as np
 import pytest
 
+import flo_amd
 import flofile
 from gpu_util import ctx  # noqa: F401
 from oracle import oracle as O
@@ -31,6 +32,27 @@ def same(ctx, flo):
     assert di.shape == oi.shape
     bad = np.nonzero(di != oi)[0]
     assert bad.size == 0, (bad[:8], di[bad[:8]], oi[bad[:8]])
+    return oi
+
+
+def same_on_every_path(ctx, flo):
+    """same(), then the corpus window and the streaming decoder, which build their own wrapper lists: a window over the
+    whole file and the whole file fed to a StreamingDecoder equal ctx.decode bit for bit"""
+    oi = same(ctx, flo)
+    want = ctx.decode(flo).view(np.uint32)
+    corpus = flo_amd.Corpus([flo], ctx)
+    n = int(corpus.lengths[0])
+    win = corpus.decode_windows(np.zeros(1, np.uint32), np.zeros(1, np.uint64), n).cpu().numpy().reshape(-1)
+    corpus.sync()
+    corpus.close()
+    assert np.array_equal(win.view(np.uint32), want), "corpus window differs from decode"
+    d = flo_amd.StreamingDecoder(ctx)
+    d.feed(flo)
+    r = flo_amd.decode_streams([d])
+    assert int(r.status[0]) == 0, r.errors
+    got = r.out.cpu().numpy()
+    d.close()
+    assert np.array_equal(got.view(np.uint32), want), "streaming decoder differs from decode"
     return oi
 
 
@@ -91,23 +113,23 @@ def test_lpc_cases_left_to_the_serial_kernel(ctx):
     n = 6000
     r = residuals(rng, n, 7)
     # coefficient sum just under and at 2^21, shift at and over 20 (the f64 recurrence is exact below those)
-    same(ctx, one_frame(n, [wrapper(r, 7, [(1 << 21) - 5, 4], 20)]))
-    same(ctx, one_frame(n, [wrapper(r, 7, [(1 << 21) - 4, 4], 20)]))
-    same(ctx, one_frame(n, [wrapper(r, 7, [(1 << 21) - 5, 4], 21)]))
+    same_on_every_path(ctx, one_frame(n, [wrapper(r, 7, [(1 << 21) - 5, 4], 20)]))
+    same_on_every_path(ctx, one_frame(n, [wrapper(r, 7, [(1 << 21) - 4, 4], 20)]))
+    same_on_every_path(ctx, one_frame(n, [wrapper(r, 7, [(1 << 21) - 5, 4], 21)]))
     # the largest numbers the parallel form takes: an integrator climbing to just under 2^31 (it stays in i32, so this
     # one is not handed over), then the same ramp a little longer (it wraps, so it is)
-    same(ctx, one_frame(2040, [wrapper(np.full(2040, 1 << 20, np.int32), 14, [1 << 20], 20)]))
-    same(ctx, one_frame(2060, [wrapper(np.full(2060, 1 << 20, np.int32), 14, [1 << 20], 20)]))
-    same(ctx, one_frame(2040, [wrapper(np.full(2040, -(1 << 20), np.int32), 14, [(1 << 20), -5, 5], 20)]))
-    same(ctx, one_frame(n, [wrapper(r, 7, [1 << 30, -(1 << 29), 12345], 30)]))
-    same(ctx, one_frame(n, [wrapper(r, 7, [-(1 << 31), (1 << 31) - 1], 31)]))
+    same_on_every_path(ctx, one_frame(2040, [wrapper(np.full(2040, 1 << 20, np.int32), 14, [1 << 20], 20)]))
+    same_on_every_path(ctx, one_frame(2060, [wrapper(np.full(2060, 1 << 20, np.int32), 14, [1 << 20], 20)]))
+    same_on_every_path(ctx, one_frame(2040, [wrapper(np.full(2040, -(1 << 20), np.int32), 14, [(1 << 20), -5, 5], 20)]))
+    same_on_every_path(ctx, one_frame(n, [wrapper(r, 7, [1 << 30, -(1 << 29), 12345], 30)]))
+    same_on_every_path(ctx, one_frame(n, [wrapper(r, 7, [-(1 << 31), (1 << 31) - 1], 31)]))
     # an unstable predictor: samples grow past i32 and wrap (decoder.rs:179 `as i32` + wrapping add)
-    same(ctx, one_frame(n, [wrapper(r, 7, [2 << 10, 1 << 8], 10)]))
-    same(ctx, one_frame(n, [wrapper(np.full(n, 1000, np.int32), 11, [1 << 12], 12)]))   # a ramp that reaches 2^31 late
+    same_on_every_path(ctx, one_frame(n, [wrapper(r, 7, [2 << 10, 1 << 8], 10)]))
+    same_on_every_path(ctx, one_frame(n, [wrapper(np.full(n, 1000, np.int32), 11, [1 << 12], 12)]))   # a ramp that reaches 2^31 late
     # Rice parameters the tile tables have no room for
     for k in (15, 16, 20, 31):
         rr = rng.integers(-(1 << 14), 1 << 14, 500).astype(np.int32)
-        same(ctx, one_frame(500, [wrapper(rr, k, [1000, -300], 11)]))
+        same_on_every_path(ctx, one_frame(500, [wrapper(rr, k, [1000, -300], 11)]))
 
 
 def test_sample_at_the_edge_of_i32(ctx):
@@ -161,10 +183,10 @@ def test_the_256_ones_escape_anywhere_in_the_stream(ctx):
         bad = bytearray(enc)
         bad[at:at + 33] = b"\xff" * 33   # at least 256 ones in a row
         flo = one_frame(r.size, [dict(coeffs=[900, -100], shift=10, k=k, residuals=bytes(bad))])
-        same(ctx, flo)
+        same_on_every_path(ctx, flo)
     bad = bytearray(enc)
     bad[1000:1031] = b"\xff" * 31        # 248 ones plus whatever surrounds them: may or may not reach 256
-    same(ctx, one_frame(r.size, [dict(coeffs=[900, -100], shift=10, k=k, residuals=bytes(bad))]))
+    same_on_every_path(ctx, one_frame(r.size, [dict(coeffs=[900, -100], shift=10, k=k, residuals=bytes(bad))]))
 
 
 def test_random_bytes_as_a_rice_stream(ctx):
@@ -233,4 +255,4 @@ def test_long_wrappers_of_unequal_length_share_a_wavefront(ctx, orders):
                 else:
                     chans.append(wrapper(residuals(rng, n, k), k, shift=128 + int(rng.integers(1, 5))))
             frames.append((8, n, 0, chans))
-    same(ctx, flofile.build_lossless(SR, 2, frames))
+    same_on_every_path(ctx, flofile.build_lossless(SR, 2, frames))
