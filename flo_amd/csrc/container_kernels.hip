@@ -339,10 +339,11 @@ const unsigned int *crc_device_tables() {
     return d;
 }
 
-int launch_finish_files(FinishArgs A, hipStream_t s) {
+int launch_finish_files(FinishArgs A, const FinishPlan &P, hipStream_t s) {
     if (!A.n_clips) return 0;
-    if (A.parts < 1 || A.parts > (A.n_clips < 64 ? 512u : 128u) || !A.part_reg) return -1;
+    if (!A.part_reg) return -1;
     if (!(A.tables = crc_device_tables())) return -1;
+    A.parts = P.parts;
     {
         std::lock_guard<std::mutex> lock(crc_mu);
         memcpy(A.x8pow2, crc_pow2, sizeof crc_pow2);
@@ -350,7 +351,7 @@ int launch_finish_files(FinishArgs A, hipStream_t s) {
         memcpy(A.byte_pow, crc_host_tables.data() + kCrcTabBytePow, sizeof A.byte_pow);
         memcpy(A.stripe_pow, crc_stripep, sizeof crc_stripep);
     }
-    if (A.n_clips < 64 && A.max_frames && !getenv("FLO_FINISH_TWO_KERNELS")) {
+    if (P.fused) {
         A.toc_chunk = kFinThreads;
         A.mode = 1;
         const unsigned chunks = (A.max_frames + kFinThreads - 1u) / kFinThreads;
@@ -361,9 +362,8 @@ int launch_finish_files(FinishArgs A, hipStream_t s) {
         return e2 == hipSuccess ? 0 : (int)e2;
     }
     A.mode = 0;
-    if (A.n_clips < 64 || !A.crc_ready)   // (with crc_ready, finish_files_kernel<256> computes what the encode's tail left)
-        hipLaunchKernelGGL(crc_slices_kernel, dim3((unsigned)A.n_clips, A.parts), dim3(kFinThreads), 0, s, A);
-    if (A.n_clips < 64) {
+    if (P.crc_slices) hipLaunchKernelGGL(crc_slices_kernel, dim3((unsigned)A.n_clips, A.parts), dim3(kFinThreads), 0, s, A);
+    if (P.threads == 1024) {
         // a few long clips: the TOC in chunks of 1024 frames (one entry per thread)
         A.toc_chunk = 1024;
         const unsigned chunks = A.max_frames ? (A.max_frames + 1023u) / 1024u : 1u;

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "encode_plan.hpp"
+
 namespace flo {
 
 struct FinishArgs {
@@ -21,7 +23,7 @@ struct FinishArgs {
     unsigned char channels, bit_depth, level;
     int n_clips;
     unsigned int *crc_out;                  // [n_clips] CRC32 of each DATA chunk (also in the header)
-    unsigned int parts;                     // slices per clip for the CRC (1..128): few long clips still fill the chip
+    unsigned int parts;                     // set by launch_finish_files: CRC slices per clip (FinishPlan::parts)
     unsigned int *part_reg;                 // [n_clips * parts] scratch: CRC register of every slice
     const unsigned int *crc_ready;          // null, or [n_clips]: == epoch where the encode already left the clip's slice
                                             // registers in part_reg (many-clips batches; the others are computed here)
@@ -37,20 +39,12 @@ struct FinishArgs {
     const unsigned int *tables;             // set by launch_finish_files: crc_device_tables()
 };
 
-int launch_finish_files(FinishArgs A, hipStream_t s);
+int launch_finish_files(FinishArgs A, const FinishPlan &P, hipStream_t s);
 // the current device's CRC table (crc_device.hpp layout), made on first use; null on failure
 const unsigned int *crc_device_tables();
 // Location table of a batch's finished files (flo_dist_table_*): row = [0] n | [1 .. max] sizes | [1 + max .. 2 max] offsets
 // | [1 + 2 max .. 3 max] CRC32 of DATA. Sizes and offsets are in the row already; this fills the CRC column from the
 // headers of the files at base + offset (byte 26).
 int launch_table_crcs(const uint8_t *base, unsigned long long *row, unsigned long long n, unsigned long long max_clips, hipStream_t s);
-// slices per clip so that about two thousand workgroups run; at most 128, or 512 for the few-long-clips case whose
-// finish_files_kernel runs 1024 threads (one per slice register)
-inline unsigned finish_parts_for(size_t n_clips) {
-    if (n_clips >= 1024) return 1;
-    size_t p = (2048 + n_clips - 1) / (n_clips ? n_clips : 1);
-    const size_t cap = n_clips < 64 ? 512 : 128;
-    return (unsigned)(p > cap ? cap : p);
-}
 
 }  // namespace flo

@@ -22,6 +22,7 @@
 #include "decode_kernels.hpp"
 #include "decode_plan.hpp"
 #include "devpool.hpp"
+#include "encode_plan.hpp"
 #include "dist_engine.hpp"
 #include "stager.hpp"
 #include "lossless_kernels.hpp"
@@ -306,6 +307,7 @@ struct flo_batch {
     hipEvent_t ev_pack_plan = nullptr;
     unsigned long long *d_stamps = nullptr;
     int exact = 0;
+    LossyPlan plan;   // of the last lossy flo_batch_encode
     // results (host, valid after sync)
     bool encoded = false, synced = false, encode_failed = false;
     std::vector<uint64_t> h_clip_bytes;
@@ -314,8 +316,8 @@ struct flo_batch {
     LosslessPlan *ll = nullptr;
 };
 
-static int auto_form(const flo_batch *b);
-static int alloc_frame_scratch(flo_batch *b);
+static LossyPlan lossy_plan(const flo_batch *b, int which, int force_path);
+static int alloc_frame_scratch(flo_batch *b, const LossyPlan &p);
 static size_t lossy_max_frame_bytes(int ch) { return 12 + 50 * (size_t)ch + (size_t)ch * (4 + 2064); }
 
 extern "C" void flo_batch_destroy(flo_batch *b) {
@@ -436,7 +438,7 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
         BCHK(pool_alloc(&b->d_crc, (n_clips + 1) * 4));
         BCHK(pool_alloc(&b->d_next, 32));
         BCHK(hipMemsetAsync(b->d_next, 0, 32, c->stream));   // once: every launch then zeroes its successor's counters
-        BCHK(pool_alloc(&b->d_part, (n_clips * finish_parts_for(n_clips) + 1) * 4));
+        BCHK(pool_alloc(&b->d_part, (n_clips * finish_parts(n_clips) + 1) * 4));
         if (n_clips) {
             // from pinned memory on the context's stream, in front of everything that will use them: a synchronous (or
             // pageable "asynchronous") copy would wait for whatever this context's other batches have in flight
@@ -451,7 +453,8 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
             BCHK(hipMemcpyAsync(b->d_plan, b->pin_plan, plan.size() * 8, hipMemcpyHostToDevice, c->stream));
             BCHK(hipMemcpyAsync(b->d_hops, b->pin_plan + 4 * n_clips, n_clips * 4, hipMemcpyHostToDevice, c->stream));
         }
-        if (auto_form(b) == 2 && (rc = alloc_frame_scratch(b)) != FLO_OK) return bail(rc);
+        // the frame-parallel scratch up front when auto picks that form (a forced form allocates at its first encode)
+        if ((rc = alloc_frame_scratch(b, lossy_plan(b, 0, 0))) != FLO_OK) return bail(rc);
     } else {
         uint8_t level = qol < 0 ? 0 : (qol > 9 ? 9 : (uint8_t)qol);  // with_compression: level.min(9)
         b->qol = level;
@@ -508,22 +511,23 @@ extern "C" int flo_batch_fill_synthetic(flo_batch *b, uint32_t seed, uint64_t cl
     return FLO_OK;
 }
 
-// auto selection of the lossy kernel form (flo_batch_encode with which = 0 and nothing forced)
-static int auto_form(const flo_batch *b) {
-    if (b->ch > 2) return 2;
-    return (b->n_clips * b->ch >= 512) ? (b->ch == 2 ? 5 : 1) : 2;
+// the batch's lossy plan for flo_batch_encode's `which` (encode_plan.hpp); the diagnostic switches are read here, once
+// (FLO_TAIL_CRC=0: every CRC from finish_files, the tests compare both; FLO_CHAIN2X_CLIPS: clips per workgroup)
+static LossyPlan lossy_plan(const flo_batch *b, int which, int force_path) {
+    const char *tc = getenv("FLO_TAIL_CRC"), *clips = getenv("FLO_CHAIN2X_CLIPS");
+    return plan_lossy({.which = which, .force_path = force_path, .ch = b->ch, .n_clips = b->n_clips, .total_frames = b->total_frames,
+                       .exact = b->exact != 0, .in_coeffs = b->d_in_coeffs != nullptr, .debug = b->d_dbg_coeffs || b->d_dbg_q || b->d_dbg_sfw,
+                       .dirty = b->ts->dev.dirty, .tail_crc = !(tc && tc[0] == '0'), .chain2q_clips = clips ? atoi(clips) : 0});
 }
 // scratch of the frame-parallel form: per-frame masking levels, fixed-size frame slots, frame offsets
-static int alloc_frame_scratch(flo_batch *b) {
+static int alloc_frame_scratch(flo_batch *b, const LossyPlan &p) {
     flo_ctx *c = b->ctx;
-    if (b->d_at || !b->total_frames) return FLO_OK;
+    if (p.form != LossyForm::Frames || b->d_at || !b->total_frames) return FLO_OK;
     const size_t n = (size_t)b->total_frames * b->ch * 32 * sizeof(float);
     HIPCHK(c, pool_alloc(&b->d_at, n));
     HIPCHK(c, pool_alloc(&b->d_sprev, n));
     HIPCHK(c, pool_alloc(&b->d_bmax, n));
-    // one 3-minute clip: 63 MB that never leave the memory-side cache; a batch of thousands of clips forced into this form
-    // transforms twice instead
-    if (b->ch == 2 && (size_t)b->total_frames * 8192 <= ((size_t)256 << 20) && !getenv("FLO_NO_COEF_HANDOVER")) HIPCHK(c, pool_alloc(&b->d_coef, (size_t)b->total_frames * 8192));
+    if (p.coef_handover) HIPCHK(c, pool_alloc(&b->d_coef, (size_t)b->total_frames * 8192));
     HIPCHK(c, pool_alloc(&b->d_slots, (size_t)b->total_frames * lossy_slot_bytes(b->ch)));
     HIPCHK(c, pool_alloc(&b->d_frame_off, (size_t)(b->total_frames + 1) * 8));
     return FLO_OK;
@@ -566,7 +570,7 @@ static LossyArgs make_args(flo_batch *b) {
     return A;
 }
 
-static int batch_encode_launch(flo_batch *b, int which);
+static int batch_encode_launch(flo_batch *b);
 extern "C" int flo_batch_encode(flo_batch *b, int which) {
     if (!b) return FLO_ERR_ARG;
     flo_ctx *c = b->ctx;
@@ -576,13 +580,14 @@ extern "C" int flo_batch_encode(flo_batch *b, int which) {
     // pack refuse with FLO_ERR_STATE instead of handing out stale or partial bytes
     b->encoded = false;
     b->synced = false;
-    int erc = batch_encode_launch(b, which);
+    if (b->mode == FLO_MODE_LOSSY) b->plan = lossy_plan(b, which, c->force_path);
+    int erc = batch_encode_launch(b);
     b->encoded = erc == FLO_OK;
     b->encode_failed = erc != FLO_OK;
     return erc;
 }
 
-static int batch_encode_launch(flo_batch *b, int which) {
+static int batch_encode_launch(flo_batch *b) {
     flo_ctx *c = b->ctx;
     if (!b->n_clips) return FLO_OK;
     if (b->mode == FLO_MODE_LOSSLESS) {
@@ -597,27 +602,25 @@ static int batch_encode_launch(flo_batch *b, int which) {
         const uint64_t part = b->n_il[i] % b->ch;
         if (part) HIPCHK(c, hipMemsetAsync(b->d_pcm + b->clip_off[i] + b->clip_nsf[i] * b->ch, 0, part * sizeof(float), c->stream));
     }
-    if (which == 0) which = c->force_path;
-    if (which == 0) which = auto_form(b);
-    if (b->ch > 2) which = 2;   // more than two channels: the generic frame-parallel kernels
+    const LossyPlan &P = b->plan;
+    unsigned max_frames = 0;
+    for (auto h : b->hops) max_frames = h > max_frames ? h : max_frames;
+    const FinishPlan fin = plan_finish(b->n_clips, max_frames, P.crc_ready);
     int rc;
-    if (which == 3 || which == 4) which = 5;   // (earlier rounds' stereo chain forms: retired, the numbers stay valid)
-    if (which == 5 && (b->exact || b->ch != 2)) which = 1;   // the exact-threshold yardstick and mono live in the one-wave-per-channel form
     b->sizes_queued = false;
-    bool tail_crc = false;   // finish_files takes the CRC slices this launch's tail computed
-    if (which == 5) {   // stereo: one lock-step transform wave + one quantiser-and-packer wave per clip
+    if (P.form == LossyForm::Chain2q) {   // stereo: one lock-step transform wave + one quantiser-and-packer wave per clip
 #ifdef FLO_STAMPS
         if (!b->d_stamps) HIPCHK(c, pool_alloc(&b->d_stamps, b->n_clips * b->ch * 16 * 8));
 #endif
         LossyArgs A = make_args(b);
         // The batch-wide counters of the persistent workgroups live in the set of this launch's epoch parity, zeroed by
         // the launch before (or at creation). Many clips: the CRC in the launch's idle tail (lossy_kernels.hip,
-        // tail_crc); FLO_TAIL_CRC=0 leaves every CRC to finish_files (the tests compare both).
+        // tail_crc), which finish_files then takes.
         const uint32_t epoch = b->epoch + 1 ? b->epoch + 1 : 2;   // (never 0; the parity alternates)
         A.next_clip = b->d_next + 4 * (epoch & 1u);
         A.clear_next = b->d_next + 4 * ((epoch & 1u) ^ 1u);
         A.epoch = epoch;
-        if (b->n_clips >= 64) {
+        if (P.crc_ready) {
             const size_t n = b->n_clips;
             if (!b->d_crc_ready) {
                 HIPCHK(c, pool_alloc(&b->d_crc_ready, n * 4));
@@ -628,30 +631,28 @@ static int batch_encode_launch(flo_batch *b, int which) {
                 HIPCHK(c, hipMemsetAsync(b->d_done_q, 0, n * 8, c->stream));
             }
             if (!(A.crc_tab = crc_device_tables())) return fail(c, FLO_ERR_DEVICE, "CRC tables");
-            const char *tc = getenv("FLO_TAIL_CRC");
-            if (!(tc && tc[0] == '0')) A.crc_ready = b->d_crc_ready;
+            if (P.tail_crc) A.crc_ready = b->d_crc_ready;
             A.done_q = b->d_done_q;
             A.part_reg = b->d_part;
-            A.parts = finish_parts_for(n);
-            tail_crc = true;
+            A.parts = fin.parts;
         }
-        rc = timed_launch(c, "lossy_chain2q", [&] { return launch_lossy_chain2q(A, c->stream); });
+        rc = timed_launch(c, "lossy_chain2q", [&] { return launch_lossy_chain2q(A, P, c->stream); });
         if (rc == FLO_OK) b->epoch = epoch;   // (a launch that did not run zeroed nothing: its epoch is used again)
-    } else if (which == 1) {
+    } else if (P.form == LossyForm::Chain) {
 #ifdef FLO_STAMPS
         if (!b->d_stamps) HIPCHK(c, pool_alloc(&b->d_stamps, b->n_clips * b->ch * 16 * 8));
 #endif
         LossyArgs A = make_args(b);
-        rc = timed_launch(c, "lossy_chain", [&] { return launch_lossy_chain(A, c->stream); });
+        rc = timed_launch(c, "lossy_chain", [&] { return launch_lossy_chain(A, P, c->stream); });
     } else {   // frame-parallel form
         // allocated by flo_batch_create when this form is what auto selects; only a forced form allocates here
-        int arc = alloc_frame_scratch(b);
+        int arc = alloc_frame_scratch(b, P);
         if (arc != FLO_OK) return arc;
         LossyArgs A = make_args(b);
-        if ((rc = timed_launch(c, "lossy_bands", [&] { return launch_lossy_frames_pass(A, 1, c->stream); })) != FLO_OK) return rc;
-        if ((rc = timed_launch(c, "lossy_scan", [&] { return launch_lossy_scan(A, c->stream); })) != FLO_OK) return rc;
-        if ((rc = timed_launch(c, "lossy_frames", [&] { return launch_lossy_frames_pass(A, 2, c->stream); })) != FLO_OK) return rc;
-        rc = timed_launch(c, "lossy_compact", [&] { return launch_lossy_compact(A, c->stream); });
+        if ((rc = timed_launch(c, "lossy_bands", [&] { return launch_lossy_frames_pass(A, P.pass1, c->stream); })) != FLO_OK) return rc;
+        if (P.scan() && (rc = timed_launch(c, "lossy_scan", [&] { return launch_lossy_scan(A, c->stream); })) != FLO_OK) return rc;
+        if ((rc = timed_launch(c, "lossy_frames", [&] { return launch_lossy_frames_pass(A, P.pass2, c->stream); })) != FLO_OK) return rc;
+        rc = timed_launch(c, "lossy_compact", [&] { return launch_lossy_compact(A, P.compact, c->stream); });
     }
     if (rc != FLO_OK) return rc;
     // header, TOC and CRC32 of every clip, in front of its DATA chunk (writer.rs:132-224; encoder.rs:229-238 parameters)
@@ -671,16 +672,14 @@ static int batch_encode_launch(flo_batch *b, int which) {
     F.level = 5;
     F.n_clips = (int)b->n_clips;
     F.crc_out = b->d_crc;
-    F.parts = finish_parts_for(b->n_clips);
     F.part_reg = b->d_part;
-    if (tail_crc) {
+    if (P.crc_ready) {
         F.crc_ready = b->d_crc_ready;
         F.epoch = b->epoch;
     }
-    F.max_frames = 0;
-    for (auto h : b->hops) F.max_frames = h > F.max_frames ? h : F.max_frames;
-    if ((rc = timed_launch(c, "finish_files", [&] { return launch_finish_files(F, c->stream); })) != FLO_OK) return rc;
-    if (tail_crc) {   // the sizes come back behind finish_files: flo_batch_sync waits once and copies nothing from the device
+    F.max_frames = max_frames;
+    if ((rc = timed_launch(c, "finish_files", [&] { return launch_finish_files(F, fin, c->stream); })) != FLO_OK) return rc;
+    if (P.crc_ready) {   // the sizes come back behind finish_files: flo_batch_sync waits once and copies nothing from the device
         if (!b->pin_sizes) {
             std::string perr;
             if (!(b->pin_sizes = (uint64_t *)stager_pinned_get(c->stager, b->n_clips * 8, perr))) return fail(c, FLO_ERR_NOMEM, perr);
@@ -739,7 +738,7 @@ static int batch_sync_impl(flo_batch *b, hipEvent_t done) {
                 for (size_t w = 0; w < b->n_clips * b->ch; w++)
                     for (int i = 0; i < 14; i++) sum[i] += (double)st[w * 16 + i];
                 double frames = (double)b->total_frames * b->ch;
-                if (b->ch == 2 && (c->force_path >= 3 || c->force_path == 0)) {   // lock-step form: wave 0 = transform, wave 1 = packer
+                if (b->plan.form == LossyForm::Chain2q) {   // lock-step form: wave 0 = transform, wave 1 = packer
                     double t[14] = {0}, p[14] = {0};
                     for (size_t k = 0; k < b->n_clips; k++)
                         for (int i = 0; i < 14; i++) { t[i] += (double)st[(2 * k) * 16 + i]; p[i] += (double)st[(2 * k + 1) * 16 + i]; }
@@ -1216,7 +1215,7 @@ static int analyze_common(flo_ctx *c, const float *pcm, size_t n, const float *i
         rc = flo_batch_upload(b, 0, pcm);
         if (rc != FLO_OK) return done(rc);
     }
-    rc = flo_batch_encode(b, c->force_path ? c->force_path : 1);
+    rc = flo_batch_encode(b, 0);   // the plan's analysis default: the forced form, else 1
     if (rc == FLO_OK) rc = flo_batch_sync(b);
     if (rc != FLO_OK) return done(rc);
     hipError_t e = hipSuccess;

@@ -1154,7 +1154,7 @@ LosslessPlan *lossless_plan_create(const std::vector<uint64_t> &n_il, const std:
         LCHK(pool_alloc(&p->d_fsamp, fsamp.size() * 4));
         LCHK(pool_alloc(&p->d_fsize, (nf + 1) * 4));
         LCHK(pool_alloc(&p->d_crc, (p->n_clips + 1) * 4));
-        LCHK(pool_alloc(&p->d_part, (p->n_clips * finish_parts_for(p->n_clips) + 1) * 4));
+        LCHK(pool_alloc(&p->d_part, (p->n_clips * finish_parts(p->n_clips) + 1) * 4));
         LCHK(hipMemcpy(p->d_cf0, cf0.data(), cf0.size() * 8, hipMemcpyHostToDevice));
         LCHK(hipMemcpy(p->d_cfn, cfn.data(), cfn.size() * 4, hipMemcpyHostToDevice));
         LCHK(hipMemcpy(p->d_fsamp, fsamp.data(), fsamp.size() * 4, hipMemcpyHostToDevice));
@@ -1227,14 +1227,13 @@ int lossless_encode_launch(LosslessPlan *p, hipStream_t s, int profile, std::str
     F.level = p->level;
     F.n_clips = (int)p->n_clips;
     F.crc_out = p->d_crc;
-    F.parts = finish_parts_for(p->n_clips);
     F.part_reg = p->d_part;
     F.max_frames = 0;
     for (size_t i = 0; i < p->n_clips; i++) {
         const unsigned nfc = (unsigned)(p->clip_first_frame[i + 1] - p->clip_first_frame[i]);
         F.max_frames = nfc > F.max_frames ? nfc : F.max_frames;
     }
-    if (launch_finish_files(F, s) != 0) {
+    if (launch_finish_files(F, plan_finish(p->n_clips, F.max_frames, false), s) != 0) {
         err = "finish_files launch failed";
         return -1;
     }

@@ -15,6 +15,7 @@
 //                            packs the slots. lossy_frame2x_kernel is its stereo form built from the lock-step device
 //                            functions, lossy_frame_n_kernel<P> the same for 3 to 8 channels.
 //   All forms produce identical bytes (tests compare them file by file).
+#include <assert.h>
 #include <stdlib.h>
 
 #include <mutex>
@@ -438,10 +439,7 @@ __device__ __forceinline__ void set_counter(uint32_t *p, uint32_t v) {
 #ifndef FLO_C2X_THREADS
 #define FLO_C2X_THREADS 768
 #endif
-// DIRTY (template parameter of the lock-step chain kernel): the element positions (bit e of 16) at which some lane of the band
-// table closes a segment; the other positions skip the slot store and the restart multiplication of band_stats_2. 0xFFFF
-// serves every table; the launcher picks the instantiation made for 44.1 kHz when the table agrees.
-constexpr uint32_t kDirty44k = 0xBDBEu;
+// DIRTY (template parameter of the lock-step chain kernel): see kDirty44k in encode_plan.hpp
 #ifdef FLO_MARKS   // diagnostic builds: section markers in the assembly listing (they pin the schedule: never shipped)
 #define FLO_MARK(x) asm volatile("; MARK " x ::: "memory")
 #else
@@ -1742,12 +1740,9 @@ int chain2q_clips_per_wg(int n_clips) {
     return g < 1 ? 1 : g;
 }
 template <bool COEFFS, uint32_t DIRTY, bool DBG>
-static int launch_chain2q_t(const LossyArgs &A, hipStream_t s) {
+static int launch_chain2q_t(const LossyArgs &A, int clips, hipStream_t s) {
     int g = chain2q_clips_per_wg(A.n_clips);
-    if (const char *e = getenv("FLO_CHAIN2X_CLIPS")) {   // diagnostic: clips per workgroup
-        const int v = atoi(e);
-        if (v >= 1 && v <= FLO_C2X_THREADS / 128) g = v;
-    }
+    if (clips >= 1 && clips <= FLO_C2X_THREADS / 128) g = clips;   // diagnostic: FLO_CHAIN2X_CLIPS
     const size_t lds = kPackBytesHotT + (size_t)g * sizeof(Clip2qLds);
     if (int rc = allow_big_lds(reinterpret_cast<const void *>(&lossy_chain2q_kernel<COEFFS, DIRTY, DBG>))) return rc;
     unsigned wgs = (unsigned)((A.n_clips + g - 1) / g);
@@ -1756,58 +1751,62 @@ static int launch_chain2q_t(const LossyArgs &A, hipStream_t s) {
     FLO_LAUNCH_CHECK();
     return 0;
 }
-int launch_lossy_chain2q(const LossyArgs &A, hipStream_t s) {
-    if (A.nch != 2 || A.exact) return -1;   // the exact-threshold test yardstick lives in the other forms
-    if (A.in_coeffs) return launch_chain2q_t<true, 0xFFFFu, true>(A, s);
-    if (A.dbg_coeffs || A.dbg_q || A.dbg_sfw) return launch_chain2q_t<false, 0xFFFFu, true>(A, s);
-    return (A.T.dirty | 0x8000u) == kDirty44k ? launch_chain2q_t<false, kDirty44k, false>(A, s) : launch_chain2q_t<false, 0xFFFFu, false>(A, s);
+int launch_lossy_chain2q(const LossyArgs &A, const LossyPlan &P, hipStream_t s) {
+    assert(P.form == LossyForm::Chain2q && A.nch == 2 && !A.exact);
+    switch (P.chain2q) {
+    case Chain2qKernel::InCoeffs: return launch_chain2q_t<true, 0xFFFFu, true>(A, P.chain2q_clips, s);
+    case Chain2qKernel::Debug: return launch_chain2q_t<false, 0xFFFFu, true>(A, P.chain2q_clips, s);
+    case Chain2qKernel::Dirty44k: return launch_chain2q_t<false, kDirty44k, false>(A, P.chain2q_clips, s);
+    case Chain2qKernel::Generic: return launch_chain2q_t<false, 0xFFFFu, false>(A, P.chain2q_clips, s);
+    default: return -1;
+    }
 }
-int launch_lossy_chain(const LossyArgs &A, hipStream_t s) {
-    if (A.nch == 1) return A.exact ? launch_chain_t<1, true>(A, s) : launch_chain_t<1, false>(A, s);
-    if (A.nch == 2) return A.exact ? launch_chain_t<2, true>(A, s) : launch_chain_t<2, false>(A, s);
-    return -1;
+int launch_lossy_chain(const LossyArgs &A, const LossyPlan &P, hipStream_t s) {
+    switch (P.chain) {
+    case ChainKernel::Mono: return launch_chain_t<1, false>(A, s);
+    case ChainKernel::MonoExact: return launch_chain_t<1, true>(A, s);
+    case ChainKernel::Stereo: return launch_chain_t<2, false>(A, s);
+    case ChainKernel::StereoExact: return launch_chain_t<2, true>(A, s);
+    default: return -1;
+    }
 }
-int launch_lossy_frames_pass(const LossyArgs &A, int pass, hipStream_t s) {
+int launch_lossy_frames_pass(const LossyArgs &A, FrameKernel k, hipStream_t s) {
     dim3 g((unsigned)A.total_frames), b(64);
-    if (A.nch == 1) {
-        if (pass == 1) hipLaunchKernelGGL((lossy_frame_kernel<1, 1, false>), g, b, 0, s, A);
-        else if (A.exact) hipLaunchKernelGGL((lossy_frame_kernel<1, 2, true>), g, b, 0, s, A);
-        else hipLaunchKernelGGL((lossy_frame_kernel<1, 2, false>), g, b, 0, s, A);
-    } else if (A.nch == 2 && !A.exact && !A.in_coeffs && !getenv("FLO_FRAME_OLD")) {
-        if (pass == 1) hipLaunchKernelGGL((lossy_frame2x_kernel<1>), g, b, 0, s, A);
-        else if (A.coef_t) hipLaunchKernelGGL((lossy_frame2x_kernel<2, true>), g, b, 0, s, A);
-        else hipLaunchKernelGGL((lossy_frame2x_kernel<2>), g, b, 0, s, A);
-    } else if (A.nch == 2) {
-        if (pass == 1) hipLaunchKernelGGL((lossy_frame_kernel<2, 1, false>), g, b, 0, s, A);
-        else if (A.exact) hipLaunchKernelGGL((lossy_frame_kernel<2, 2, true>), g, b, 0, s, A);
-        else hipLaunchKernelGGL((lossy_frame_kernel<2, 2, false>), g, b, 0, s, A);
-    } else if (A.nch <= kMaxLossyChannels) {
-        const size_t dynb = (size_t)A.slot_bytes + 256 + (size_t)A.nch * 2048;
-        if (pass == 1) hipLaunchKernelGGL((lossy_frame_n_kernel<1, false>), g, b, dynb, s, A);
-        else if (A.exact) hipLaunchKernelGGL((lossy_frame_n_kernel<2, true>), g, b, dynb, s, A);
-        else hipLaunchKernelGGL((lossy_frame_n_kernel<2, false>), g, b, dynb, s, A);
-    } else return -1;
+    const size_t dynb = (size_t)A.slot_bytes + 256 + (size_t)A.nch * 2048;   // lossy_frame_n_kernel
+    switch (k) {
+    case FrameKernel::Mono1: hipLaunchKernelGGL((lossy_frame_kernel<1, 1, false>), g, b, 0, s, A); break;
+    case FrameKernel::Mono2: hipLaunchKernelGGL((lossy_frame_kernel<1, 2, false>), g, b, 0, s, A); break;
+    case FrameKernel::Mono2Exact: hipLaunchKernelGGL((lossy_frame_kernel<1, 2, true>), g, b, 0, s, A); break;
+    case FrameKernel::Stereo1: hipLaunchKernelGGL((lossy_frame_kernel<2, 1, false>), g, b, 0, s, A); break;
+    case FrameKernel::Stereo2: hipLaunchKernelGGL((lossy_frame_kernel<2, 2, false>), g, b, 0, s, A); break;
+    case FrameKernel::Stereo2Exact: hipLaunchKernelGGL((lossy_frame_kernel<2, 2, true>), g, b, 0, s, A); break;
+    case FrameKernel::Pair1: hipLaunchKernelGGL((lossy_frame2x_kernel<1>), g, b, 0, s, A); break;
+    case FrameKernel::Pair2: hipLaunchKernelGGL((lossy_frame2x_kernel<2>), g, b, 0, s, A); break;
+    case FrameKernel::Pair2FromCoef: hipLaunchKernelGGL((lossy_frame2x_kernel<2, true>), g, b, 0, s, A); break;
+    case FrameKernel::Multi1: hipLaunchKernelGGL((lossy_frame_n_kernel<1, false>), g, b, dynb, s, A); break;
+    case FrameKernel::Multi2: hipLaunchKernelGGL((lossy_frame_n_kernel<2, false>), g, b, dynb, s, A); break;
+    case FrameKernel::Multi2Exact: hipLaunchKernelGGL((lossy_frame_n_kernel<2, true>), g, b, dynb, s, A); break;
+    default: return -1;
+    }
     FLO_LAUNCH_CHECK();
     return 0;
 }
-// the stereo frame-parallel form with handed-over coefficients walks the temporal chain inside pass 2: no scan launch
-bool lossy_pass2_scans_itself(const LossyArgs &A) { return A.nch == 2 && !A.exact && !A.in_coeffs && A.coef_t && !getenv("FLO_FRAME_OLD"); }
 int launch_lossy_scan(const LossyArgs &A, hipStream_t s) {
-    if (lossy_pass2_scans_itself(A)) return 0;
     unsigned max_hops = (unsigned)A.max_hops;
     hipLaunchKernelGGL(lossy_scan_kernel, dim3(A.n_clips, (max_hops + kScanBlock - 1) / kScanBlock), dim3(32 * A.nch), 0, s, A);
     FLO_LAUNCH_CHECK();
     return 0;
 }
-int launch_lossy_compact(const LossyArgs &A, hipStream_t s) {
-    if (A.n_clips <= 16 && !getenv("FLO_COMPACT_TWO_KERNELS")) {   // few clips: the fused form (a chunk's workgroup sums the sizes in front of it itself)
+int launch_lossy_compact(const LossyArgs &A, CompactKernel k, hipStream_t s) {
+    if (k == CompactKernel::Fused) {   // few clips: a chunk's workgroup sums the sizes in front of it itself
         const unsigned chunks = ((unsigned)A.max_hops + kCompactChunk - 1) / kCompactChunk;
         hipLaunchKernelGGL(lossy_offsets_compact_kernel, dim3(chunks ? chunks : 1u, (unsigned)A.n_clips), dim3(256), 0, s, A);
         FLO_LAUNCH_CHECK();
         return 0;
     }
-    if (A.n_clips < 64) hipLaunchKernelGGL((lossy_frame_offsets_kernel<1024>), dim3(A.n_clips), dim3(1024), 0, s, A);
-    else hipLaunchKernelGGL((lossy_frame_offsets_kernel<256>), dim3(A.n_clips), dim3(256), 0, s, A);
+    if (k == CompactKernel::Offsets1024) hipLaunchKernelGGL((lossy_frame_offsets_kernel<1024>), dim3(A.n_clips), dim3(1024), 0, s, A);
+    else if (k == CompactKernel::Offsets256) hipLaunchKernelGGL((lossy_frame_offsets_kernel<256>), dim3(A.n_clips), dim3(256), 0, s, A);
+    else return -1;
     FLO_LAUNCH_CHECK();
     hipLaunchKernelGGL(lossy_compact_kernel, dim3((unsigned)A.total_frames), dim3(256), 0, s, A);
     FLO_LAUNCH_CHECK();

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "encode_plan.hpp"
 #include "lossy_device.hpp"
 
 namespace flo {
@@ -50,15 +51,16 @@ struct LossyArgs {
     unsigned long long *done_q;              // [n_clips] queue entries: epoch << 32 | clip
     unsigned int *crc_ready;                 // [n_clips]
     unsigned int *part_reg;                  // [n_clips * parts]
-    unsigned int parts;                      // slices per clip (finish_parts_for)
+    unsigned int parts;                      // slices per clip (finish_parts)
     unsigned int epoch;                      // of this launch, never 0
     const unsigned int *crc_tab;             // crc_device_tables()
     int n_cus;                               // compute units of the device (persistent workgroups)
 };
 
-int launch_lossy_chain(const LossyArgs &A, hipStream_t s);
-int launch_lossy_chain2q(const LossyArgs &A, hipStream_t s);  // stereo only: one lock-step transform wave + one quantiser-and-packer wave per clip
-int launch_lossy_frames_pass(const LossyArgs &A, int pass, hipStream_t s);
+// the launchers launch the kernels the plan names (encode_plan.hpp); they choose only the launch geometry
+int launch_lossy_chain(const LossyArgs &A, const LossyPlan &P, hipStream_t s);
+int launch_lossy_chain2q(const LossyArgs &A, const LossyPlan &P, hipStream_t s);  // stereo only: one lock-step transform wave + one quantiser-and-packer wave per clip
+int launch_lossy_frames_pass(const LossyArgs &A, FrameKernel k, hipStream_t s);
 // bytes reserved per frame in the frame-parallel form: header + scale words + every channel's largest sparse blob
 inline unsigned int lossy_slot_bytes(int nch) {
     unsigned int need = 12u + 50u * (unsigned)nch + (unsigned)nch * (4u + 2064u) + 16u;
@@ -67,7 +69,7 @@ inline unsigned int lossy_slot_bytes(int nch) {
 }
 constexpr int kMaxLossyChannels = 8;      // more channels than two take the generic frame-parallel kernel
 int launch_lossy_scan(const LossyArgs &A, hipStream_t s);
-int launch_lossy_compact(const LossyArgs &A, hipStream_t s);
+int launch_lossy_compact(const LossyArgs &A, CompactKernel k, hipStream_t s);
 int launch_mdct_only(const LossyDevTables &T, const float *frames, unsigned long long n, float *out, hipStream_t s);
 int launch_quantise_smr(const LossyDevTables &T, const float *coeffs, const float *smr, unsigned long long n, short *q, float *sf,
                         hipStream_t s);
