@@ -30,6 +30,7 @@ EXPORTS = [
     "flo_stream_create", "flo_stream_destroy", "flo_stream_push", "flo_stream_pending_samples", "flo_stream_pending_frames",
     "flo_stream_next_frame", "flo_stream_flush", "flo_stream_finalize",
     "flo_analyze", "flo_analysis_metadata", "flo_batch_analysis_metadata", "flo_batch_set_bit_depth",
+    "flo_batch_analyze_all", "flo_batch_analysis_metadata_all", "flo_batch_clip_device_data",
     "flo_get_toc", "flo_seek_to_time", "flo_decode_frame_at",
     "flo_corpus_create", "flo_corpus_destroy", "flo_corpus_format", "flo_corpus_file_frames", "flo_corpus_decode_windows",
     "flo_corpus_sync",
@@ -145,6 +146,10 @@ def lib():
     L.flo_ctx_reserve_cus.argtypes = [vp, C.c_int]
     L.flo_ctx_reserve_cus.restype = C.c_int
     L.flo_batch_analysis_metadata.argtypes = [vp, sz, C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
+    L.flo_batch_clip_device_data.argtypes = [vp, sz]
+    L.flo_batch_clip_device_data.restype = vp
+    L.flo_batch_analyze_all.argtypes = [vp, C.c_uint32, vp, vp, sz, C.POINTER(C.c_uint64)]
+    L.flo_batch_analysis_metadata_all.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.flo_batch_set_bit_depth.argtypes = [vp, C.c_uint8]
     L.flo_ctx_upload_path.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.flo_ctx_reserved_cus.argtypes = [vp]

@@ -81,6 +81,14 @@ class _CBuffer:
             self._ptr = C.c_void_p()
 
 
+def _analysis_dict(a, peaks):
+    return dict(peaks=peaks, hash=bytes(a.hash), duration_ms=a.duration_ms, sample_rate=a.sample_rate,
+                channels=a.channels, frequency_peaks=list(a.frequency_peaks), energy_profile=list(a.energy_profile),
+                avg_loudness=a.avg_loudness, integrated_lufs=a.integrated_lufs, length_ms=a.length_ms,
+                loudness_range_lu=a.loudness_range_lu, true_peak_dbtp=a.true_peak_dbtp, sample_peak_dbfs=a.sample_peak_dbfs,
+                sum_squares=np.float32(a.sum_squares))
+
+
 class Context:
     """One per host thread / GPU (flo_ctx)."""
 
@@ -217,11 +225,7 @@ class Context:
         a = _native.Analysis()
         self._chk(self._L.flo_analyze(self._h, p.ctypes.data, p.size, sample_rate, channels, peaks_per_second,
                                       peaks.ctypes.data, peaks.size, C.byref(a)))
-        return dict(peaks=peaks[: a.n_peaks].copy(), hash=bytes(a.hash), duration_ms=a.duration_ms, sample_rate=a.sample_rate,
-                    channels=a.channels, frequency_peaks=list(a.frequency_peaks), energy_profile=list(a.energy_profile),
-                    avg_loudness=a.avg_loudness, integrated_lufs=a.integrated_lufs, length_ms=a.length_ms,
-                    loudness_range_lu=a.loudness_range_lu, true_peak_dbtp=a.true_peak_dbtp, sample_peak_dbfs=a.sample_peak_dbfs,
-                    sum_squares=np.float32(a.sum_squares))
+        return _analysis_dict(a, peaks[: a.n_peaks].copy())
 
     def analysis_metadata(self, samples, sample_rate, channels, peaks_per_second=50) -> bytes:
         """add_analysis_data_if_missing(&[], ...): the MessagePack META libflo::encode* build for an empty input META"""
@@ -348,7 +352,7 @@ class Batch:
         if n:
             hip = C.CDLL("libamdhip64.so")
             hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-            rc = hip.hipMemcpy(out.ctypes.data, self.clip_device_ptr(clip), n * 4, 2)
+            rc = hip.hipMemcpy(out.ctypes.data, self._L.flo_batch_clip_device_data(self._h, clip), n * 4, 2)
             if rc != 0:
                 raise FloError(f"hipMemcpy (device to host) failed with {rc}")
         return out
@@ -369,6 +373,22 @@ class Batch:
         out, n = C.c_void_p(), C.c_size_t()
         self.ctx._chk(self._L.flo_batch_analysis_metadata(self._h, clip, peaks_per_second, C.byref(out), C.byref(n)))
         return self.ctx._take(out, n)
+
+    def analyze_all(self, peaks_per_second=50):
+        """the analysis of every clip (one device pass over the whole batch): a list of dicts shaped like Context.analyze"""
+        off = (C.c_uint64 * (self.n_clips + 1))()
+        self.ctx._chk(self._L.flo_batch_analyze_all(self._h, peaks_per_second, None, None, 0, off))
+        peaks = np.zeros(max(off[self.n_clips], 1), np.float32)
+        an = (_native.Analysis * max(self.n_clips, 1))()
+        self.ctx._chk(self._L.flo_batch_analyze_all(self._h, peaks_per_second, an, peaks.ctypes.data, peaks.size, off))
+        return [_analysis_dict(an[i], peaks[off[i]:off[i + 1]].copy()) for i in range(self.n_clips)]
+
+    def analysis_metadata_all(self, peaks_per_second=50):
+        """the analysis META of every clip (one device pass over the whole batch), as a list of bytes"""
+        out, off = C.c_void_p(), (C.c_uint64 * (self.n_clips + 1))()
+        self.ctx._chk(self._L.flo_batch_analysis_metadata_all(self._h, peaks_per_second, C.byref(out), off))
+        blob = self.ctx._take(out, C.c_size_t(off[self.n_clips]))
+        return [blob[off[i]:off[i + 1]] for i in range(self.n_clips)]
 
     def set_bit_depth(self, bit_depth: int):
         self.ctx._chk(self._L.flo_batch_set_bit_depth(self._h, bit_depth))
@@ -908,9 +928,14 @@ def encode(samples, sample_rate, channels, bit_depth, metadata=None) -> bytes:
     return _encode_analysed(MODE_LOSSLESS, samples, sample_rate, channels, 5, bit_depth, metadata)
 
 
+def _lossy_quality(quality: int) -> float:
+    """libflo::encode_lossy's quality level 0-4 -> 0.0/0.35/0.55/0.75/1.0 (lib.rs:135-166)"""
+    return {0: 0.0, 1: 0.35, 2: 0.55, 3: 0.75}.get(int(quality), 1.0)
+
+
 def encode_lossy(samples, sample_rate, channels, _bit_depth, quality: int, metadata=None) -> bytes:
     """libflo::encode_lossy (lib.rs:135-166): quality level 0-4 -> 0.0/0.35/0.55/0.75/1.0"""
-    q = {0: 0.0, 1: 0.35, 2: 0.55, 3: 0.75}.get(int(quality), 1.0)
+    q = _lossy_quality(quality)
     return _encode_analysed(MODE_LOSSY, samples, sample_rate, channels, q, 16, metadata)
 
 
@@ -918,3 +943,51 @@ def encode_with_bitrate(samples, sample_rate, channels, _bit_depth, target_bitra
     """libflo::encode_with_bitrate (lib.rs:181-206)"""
     q = QualityPreset.from_bitrate(target_bitrate_kbps, sample_rate, channels).as_f32()
     return _encode_analysed(MODE_LOSSY, samples, sample_rate, channels, q, 16, metadata)
+
+
+def _encode_analysed_many(mode, clips, sample_rate, channels, quality_or_level, bit_depth, metadata):
+    """_encode_analysed for many clips: every clip uploaded into one batch (one flo_batch_upload each, one sync), ONE
+    batched analysis (Batch.analysis_metadata_all), one encode, then each file with its META. metadata: None, one bytes
+    for every clip, or one entry per clip"""
+    from . import meta as _meta
+    ps = [_f32(x) for x in clips]
+    if metadata is None or isinstance(metadata, (bytes, bytearray)):
+        user = [bytes(metadata or b"")] * len(ps)
+    else:
+        user = [bytes(m or b"") for m in metadata]
+        if len(user) != len(ps):
+            raise ValueError(f"metadata has {len(user)} entries for {len(ps)} clips")
+    if not ps:
+        return []
+    ctx = default_context()
+    b = Batch(ctx, mode, [p.size for p in ps], sample_rate, channels, quality_or_level)
+    try:
+        for i, p in enumerate(ps):
+            ctx._chk(b._L.flo_batch_upload(b._h, i, p.ctypes.data))
+        b.sync()   # (the copies have read ps)
+        metas = b.analysis_metadata_all(50)
+        if mode == MODE_LOSSLESS:
+            b.set_bit_depth(bit_depth)
+        b.encode(0)
+        b.sync()
+        return [b.fetch(i, _meta.merge_analysis(user[i], metas[i])) for i in range(len(ps))]
+    finally:
+        b.close()
+
+
+def encode_many(clips, sample_rate, channels, bit_depth, metadata=None):
+    """encode (libflo::encode) of every clip, the analysis of all of them in one device pass: a list of files"""
+    return _encode_analysed_many(MODE_LOSSLESS, clips, sample_rate, channels, 5, bit_depth, metadata)
+
+
+def encode_lossy_many(clips, sample_rate, channels, _bit_depth, quality: int, metadata=None):
+    """encode_lossy (libflo::encode_lossy) of every clip, the analysis of all of them in one device pass. A clip whose
+    length is not a whole number of sample-frames is analysed over all of its samples, as the reference does"""
+    q = _lossy_quality(quality)
+    return _encode_analysed_many(MODE_LOSSY, clips, sample_rate, channels, q, 16, metadata)
+
+
+def encode_with_bitrate_many(clips, sample_rate, channels, _bit_depth, target_bitrate_kbps, metadata=None):
+    """encode_with_bitrate (libflo::encode_with_bitrate) of every clip, the analysis of all of them in one device pass"""
+    q = QualityPreset.from_bitrate(target_bitrate_kbps, sample_rate, channels).as_f32()
+    return _encode_analysed_many(MODE_LOSSY, clips, sample_rate, channels, q, 16, metadata)

@@ -50,6 +50,10 @@ struct AnalysisArgs {
     unsigned int point_ok[3];
     float *band_sqrt;            // [3][16]
     unsigned int *peak_bin;      // [3][8]
+    // batched analysis only (analysis_batch_kernels.hip): the 400 ms block energies, summed over the channels and divided
+    // by the block lengths as the host does it (an_block_energy), and the BLAKE3 root, next to the clip's other results
+    double *block_energy;        // [n_blocks]
+    unsigned int *root;          // [8]
 };
 
 // The analysis is four independent chains of kernels - K-weighting, sum of squares, BLAKE3, peaks - each ending in a step
@@ -60,5 +64,64 @@ struct AnalysisSide {
     hipEvent_t fork = nullptr, join[3] = {nullptr, nullptr, nullptr};
 };
 int launch_analysis(const AnalysisArgs &A, hipStream_t s, const AnalysisSide *side = nullptr);
+
+// ------------------------------------------------------------------------------------------------ batched analysis
+// Every clip of a group in one launch per kernel (analysis_batch_kernels.hip). The descriptors ARE the clips'
+// AnalysisArgs, made by the same host code as for one clip. A launch's grid is a flat work list of (clip, item): for list
+// L, pre[L * (n_clips + 1) + i] is the number of workgroups of the clips in front of clip i (a workgroup takes
+// an_batch_per_wg(L) items of one clip in turn), and a workgroup finds its clip by binary search. The steps one workgroup walks alone for one clip (the hash tree, the sum-of-squares prefix and chain,
+// the K-weighting scan, the peak reduce) become one workgroup per clip.
+constexpr int kAnTile = 2048;   // frames per tile (an_loud, an_peak)
+enum AnList : int {
+    kAnlPeaks,     // n_peaks: one wave per peak window
+    kAnlLoud,      // clips of at most one exact segment: n_seg x channels
+    kAnlKw,        // longer clips: ceil(n_kseg / 64) x channels (K-weighting passes 1 and 2)
+    kAnlKScan,     // longer clips: channels
+    kAnlTile,      // longer clips: true / sample peak tiles x channels
+    kAnlFast1,     // longer clips: 1 (peak reduce)
+    kAnlSqChunk,   // sum of squares beyond one segment: n_sq_chunks
+    kAnlSq1,       // sum of squares beyond one segment: 1 (prefix, chain)
+    kAnlSumsq,     // sum of squares within one segment: n_sq_seg
+    kAnlB3,        // BLAKE3 chunks: ceil(n_chunks / 128)
+    kAnlClip,      // every clip with samples: 1 (hash tree, block energies)
+    kAnlFft,       // every clip with samples: 3
+    kAnlCount
+};
+// items of every list for one clip (host and device agree on the geometry through this one function)
+__host__ __device__ inline void an_batch_items(const AnalysisArgs &A, unsigned long long (&it)[kAnlCount]) {
+    for (int k = 0; k < kAnlCount; k++) it[k] = 0;
+    if (!A.n) return;
+    const unsigned long long ch = A.channels, longest = (A.n + ch - 1) / ch;
+    it[kAnlPeaks] = A.n_peaks;
+    if (A.fast) {
+        it[kAnlKw] = (A.n_kseg + 63ull) / 64ull * ch;
+        it[kAnlKScan] = ch;
+        it[kAnlTile] = (longest + kAnTile - 1) / kAnTile * ch;
+        it[kAnlFast1] = 1;
+    } else {
+        it[kAnlLoud] = (unsigned long long)A.n_seg * ch;
+    }
+    if (A.sq_exact) {
+        it[kAnlSqChunk] = A.n_sq_chunks;
+        it[kAnlSq1] = 1;
+    } else {
+        it[kAnlSumsq] = A.n_sq_seg;
+    }
+    it[kAnlB3] = (A.n_chunks + 127ull) / 128ull;
+    it[kAnlClip] = 1;
+    it[kAnlFft] = 3;
+}
+// items one workgroup takes in turn (one clip lookup for all of them); a list's prefix counts these workgroups
+__host__ __device__ constexpr unsigned an_batch_per_wg(int L) {
+    return L == kAnlPeaks ? 8u : L == kAnlTile ? 4u : L == kAnlSqChunk ? 16u : L == kAnlB3 ? 4u : 1u;
+}
+struct AnBatchArgs {
+    const AnalysisArgs *clips;   // [n_clips] the group's descriptors (device)
+    const unsigned int *pre;     // [kAnlCount][n_clips + 1]: workgroups of the clips in front (device)
+    unsigned int n_clips;
+};
+// one group: launches on `s` and, given `side`, the three side streams (fork behind what `s` holds, join before return);
+// total[L]: the workgroups of list L over the group (the grid sizes)
+int launch_analysis_batch(const AnBatchArgs &G, const unsigned long long (&total)[kAnlCount], hipStream_t s, const AnalysisSide *side);
 
 }  // namespace flo

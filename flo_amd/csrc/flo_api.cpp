@@ -314,6 +314,15 @@ struct flo_batch {
     std::vector<uint32_t> h_frame_size;
     // lossless
     LosslessPlan *ll = nullptr;
+    // lossy clips of n_interleaved % ch != 0 uploaded from the host: the trailing partial sample-frame, which the encoder
+    // drops (so it stays out of the device copy) but the analysis covers (flo_batch_analyze_all)
+    std::vector<std::vector<float>> tail;
+    void keep_tail(size_t clip, const float *pcm) {
+        if (tail.size() != n_clips) tail.resize(n_clips);
+        const uint64_t whole = clip_nsf[clip] * ch;
+        if (mode == FLO_MODE_LOSSY && n_il[clip] > whole) tail[clip].assign(pcm + whole, pcm + n_il[clip]);
+        else tail[clip].clear();
+    }
 };
 
 static LossyPlan lossy_plan(const flo_batch *b, int which, int force_path);
@@ -472,6 +481,13 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
 
 extern "C" float *flo_batch_clip_device_ptr(flo_batch *b, size_t clip) {
     if (!b || clip >= b->n_clips) return nullptr;
+    if (clip < b->tail.size()) b->tail[clip].clear();   // (the caller writes the clip: it is analysed as the device holds it)
+    return b->d_pcm + b->clip_off[clip];
+}
+
+// the same address for reading only: the clip's kept tail (flo_batch_analyze_all) stays
+extern "C" const float *flo_batch_clip_device_data(const flo_batch *b, size_t clip) {
+    if (!b || clip >= b->n_clips) return nullptr;
     return b->d_pcm + b->clip_off[clip];
 }
 
@@ -483,6 +499,7 @@ extern "C" int flo_batch_upload(flo_batch *b, size_t clip, const float *pcm) {
     const uint64_t n_copy = b->mode == FLO_MODE_LOSSY ? b->clip_nsf[clip] * b->ch : b->n_il[clip];
     if (n_copy)
         HIPCHK(c, hipMemcpyAsync(b->d_pcm + b->clip_off[clip], pcm, n_copy * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    b->keep_tail(clip, pcm);
     b->encoded = b->synced = b->encode_failed = false;
     return FLO_OK;
 }
@@ -506,6 +523,7 @@ extern "C" int flo_batch_fill_synthetic(flo_batch *b, uint32_t seed, uint64_t cl
         rc = launch_synth_fill(b->d_pcm, (const unsigned long long *)d_off, (const unsigned long long *)d_off + b->n_clips, (int)b->n_clips, b->ch, seed, clip_id0, c->stream);
     hipStreamSynchronize(c->stream);
     hipFree(d_off);
+    b->tail.clear();
     if (e != hipSuccess || rc != 0) return fail(c, FLO_ERR_DEVICE, "synthetic fill failed");
     b->encoded = b->synced = b->encode_failed = false;
     return FLO_OK;
@@ -940,6 +958,7 @@ static int batch_upload_all(flo_batch *b, const float *const *pcm, hipStream_t s
         // a trailing partial sample-frame is not part of the clip (encoder.rs:174): it must not land in the zero padding
         const uint64_t n_copy = b->mode == FLO_MODE_LOSSY ? b->clip_nsf[i] * b->ch : b->n_il[i];
         if (n_copy) segs.push_back({b->d_pcm + b->clip_off[i], pcm[i], n_copy * sizeof(float)});
+        b->keep_tail(i, pcm[i]);
     }
     std::string err;
     if (stager_upload(c->stager, segs, stream ? stream : c->stream, err) != 0) return fail(c, FLO_ERR_DEVICE, err);
@@ -2406,20 +2425,17 @@ float max_rust(float a, float b) {
 }
 }  // namespace
 
-// pcm_dev: the samples are already on the device (a batch's clip): nothing is staged
-static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size_t n, uint32_t sr, uint8_t ch, uint32_t pps, float *peaks,
-                        size_t peaks_cap, flo_analysis *out) {
-    if (!c || !out || (n && !pcm && !pcm_dev) || !ch || !sr || !pps) return c ? fail(c, FLO_ERR_ARG, "flo_analyze: bad argument") : FLO_ERR_ARG;
-    memset(out, 0, sizeof *out);
-    out->sample_rate = sr;
-    out->channels = ch;
-    out->integrated_lufs = -23.0;
-    out->loudness_range_lu = 0.0;
-    out->true_peak_dbtp = -150.0;
-    out->sample_peak_dbfs = -150.0;
-    out->length_ms = (uint64_t)((double)(n / ch) / (double)sr * 1000.0);
-    HIPCHK(c, hipSetDevice(c->device));
-    AnalysisArgs A{};
+// K-weighting of a clip beyond one exact segment: two passes over short segments with the filter state handed over
+// exactly (analysis_kernels.hip, "K-weighting, long clips"); FLO_ANALYSIS_EXACT=1 keeps the one-lane walk (diagnostic)
+static bool analysis_fast_path(uint64_t frames, unsigned hop, unsigned ch) {
+    return frames > 65536 && hop && ch <= 64 && !getenv("FLO_ANALYSIS_EXACT");
+}
+// a clip's geometry: everything launch_analysis needs but its buffers, for the per-clip and the batched path alike
+// (block_len: the lengths of the 400 ms blocks, when asked for). Nothing but n_peaks for an empty clip, or when
+// peaks_only. `like`: a clip of the same rate whose geometry is made - its filter coefficients (and its M^L, for the same
+// segment length) are copied rather than computed again (the same values: the batched path's clips share one rate).
+static void analysis_geometry(AnalysisArgs &A, size_t n, uint32_t sr, uint8_t ch, uint32_t pps, std::vector<uint64_t> *block_len_out,
+                              bool peaks_only = false, const AnalysisArgs *like = nullptr) {
     A.n = n;
     A.sample_rate = sr;
     A.channels = ch;
@@ -2432,11 +2448,14 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
         while (np < cap && (uint64_t)((double)np * A.samples_per_peak) * ch < n) np++;
         A.n_peaks = np;
     }
-    out->n_peaks = A.n_peaks;
-    if (!n) return FLO_OK;
-    if (peaks_cap < A.n_peaks) return fail(c, FLO_ERR_ARG, "flo_analyze: peak buffer too small");
+    if (!n || peaks_only) return;
+    if (like && (!like->n || like->sample_rate != sr)) like = nullptr;
     // K-weighting (ebu_r128.rs:51-103) and block geometry (:190-192, :236-262)
-    {
+    if (like) {
+        memcpy(A.shelf, like->shelf, sizeof A.shelf);
+        memcpy(A.hp, like->hp, sizeof A.hp);
+        A.hop = like->hop;
+    } else {
         const double rate = (double)sr;
         const double f0 = 1681.974450955533, g_db = 3.999843853973347, q = 0.7071752369554196;
         const double k = std::tan(M_PI * f0 / rate), vh = std::pow(10.0, g_db / 20.0), vb = std::pow(vh, 0.4996667741545416);
@@ -2456,7 +2475,7 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
         A.hop = (unsigned)std::llround(rate * 0.1);
     }
     const uint64_t frames = n / ch;
-    std::vector<uint64_t> block_len;
+    std::vector<uint64_t> block_len;   // (ebu_r128.rs:236-262)
     if (A.hop) {
         uint64_t start = 0;
         const uint64_t block = (uint64_t)A.hop * 4;
@@ -2478,16 +2497,16 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
         A.n_seg = (unsigned)((longest + A.seg_frames - 1) / A.seg_frames);
         if (A.n_seg == 0) A.n_seg = 1;
     }
-    // clips beyond one exact segment: two passes over short segments with the filter state handed over exactly
-    // (analysis_kernels.hip, "K-weighting, long clips"); FLO_ANALYSIS_EXACT=1 keeps the one-lane walk (diagnostic)
-    A.fast = (frames > 65536 && A.hop && ch <= 64 && !getenv("FLO_ANALYSIS_EXACT")) ? 1u : 0u;
+    A.fast = analysis_fast_path(frames, A.hop, ch) ? 1u : 0u;
     // segment length: two walks of L frames (150 ns per frame) against a scan over frames / L segments (35 ns each):
     // the power of two next to sqrt(frames / 8), between 256 and 2048
     A.kseg_frames = 256;
     while (A.kseg_frames < 2048 && (uint64_t)A.kseg_frames * A.kseg_frames * 8 < frames) A.kseg_frames *= 2;
     A.n_kseg = (unsigned)((frames + A.kseg_frames - 1) / A.kseg_frames);
     A.kq = A.hop ? A.kseg_frames / A.hop + 2 : 1;
-    if (A.fast) {
+    if (A.fast && like && like->fast && like->kseg_frames == A.kseg_frames) {
+        memcpy(A.kpow, like->kpow, sizeof A.kpow);
+    } else if (A.fast) {
         // M^L: the homogeneous system (x = 0) walked L steps from each unit state, in the kernels' own arithmetic
         for (int col = 0; col < 4; col++) {
             double v[4] = {0, 0, 0, 0};
@@ -2508,7 +2527,9 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
     A.sq_exact = n > A.sq_seg ? 1u : 0u;
     A.n_sq_chunks = (n + 1023) / 1024;
     if (A.sq_exact) A.n_sq_seg = 1;
-    {   // compute_true_peak's filter (ebu_r128.rs:117-140): 49-tap Hann-windowed sinc, designed at 4 fs, unit sum
+    if (like) {
+        memcpy(A.tp_coef, like->tp_coef, sizeof A.tp_coef);
+    } else {   // compute_true_peak's filter (ebu_r128.rs:117-140): 49-tap Hann-windowed sinc, designed at 4 fs, unit sum
         const double oversample_rate = (double)sr * 4.0, cutoff = (double)sr * 0.45, center = 24.0;
         double sum = 0.0;
         for (int i = 0; i < 49; i++) {
@@ -2527,7 +2548,11 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
         A.points[i] = pts[i];
         A.point_ok[i] = pts[i] + 256 < spc ? 1u : 0u;
     }
-    // twiddles of the 256-point FFT: cos / sin in double, rounded to f32 (the values the oracle's FFT uses)
+    if (block_len_out) *block_len_out = std::move(block_len);
+}
+// twiddles of the 256-point FFT: cos / sin in double, rounded to f32 (the values the oracle's FFT uses)
+constexpr size_t kAnTwBytes = 8 * 128 * 2 * sizeof(float);
+static const float *analysis_twiddles() {
     // (a function-local static initialised by a lambda: thread-safe, contexts on several threads may meet here)
     struct Tw {
         float v[8 * 128 * 2];
@@ -2542,74 +2567,33 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
             }
         return t;
     }();
-    const float (&tw)[8 * 128 * 2] = tw_table.v;
-    // device buffers: pcm | results
-    DevMem d_pcm, d_res, d_cvs;
-    QuiesceOnExit quiesce_d_pcm(c);
-    if (!pcm_dev) HIPCHK(c, pool_alloc(&d_pcm.p, n * 4 + 64));
-    const size_t o_peaks = 0, o_sumsq = o_peaks + (((size_t)A.n_peaks * 4 + 15) & ~(size_t)15),
-                 o_pk = o_sumsq + (((size_t)A.n_sq_seg * 4 + 15) & ~(size_t)15), o_blocks = o_pk + 16,
-                 o_tw = o_blocks + (((size_t)ch * A.n_blocks * 16 + 15) & ~(size_t)15), o_band = o_tw + sizeof tw, o_bin = o_band + 3 * 16 * 4,
-                 o_kq = (o_bin + 3 * 8 * 4 + 15) & ~(size_t)15, o_kst = o_kq + (A.fast ? (size_t)ch * A.n_kseg * A.kq * 8 : 0),
-                 o_sqd = o_kst + (A.fast ? (size_t)ch * A.n_kseg * 32 : 0), o_sqr = o_sqd + (A.sq_exact ? (A.n_sq_chunks + 1) * 8 : 0),
-                 o_pkp = o_sqr + (A.sq_exact ? A.n_sq_chunks * 64 : 0),
-                 res_bytes = o_pkp + (A.fast ? ((((n + ch - 1) / ch + 2047) / 2048) * ch * 16) : 0);
-    HIPCHK(c, pool_alloc(&d_res.p, res_bytes + 64));
-    HIPCHK(c, pool_alloc(&d_cvs.p, (2 * A.n_chunks + 1) * 32 + 64));
-    int rc = ctx_stager(c);
-    if (rc != FLO_OK) return rc;
-    if (!pcm_dev) {
-        std::vector<UploadSeg> segs{{d_pcm.p, pcm, n * 4}};
-        std::string err;
-        const auto tu0 = std::chrono::steady_clock::now();
-        if (stager_upload(c->stager, segs, c->stream, err) != 0) return fail(c, FLO_ERR_DEVICE, err);
-        if (getenv("FLO_TRACE")) {
-            hipStreamSynchronize(c->stream);
-            fprintf(stderr, "[flo] analysis: upload of %.1f MB took %.0f us (%s)\n", (double)n * 4 / 1e6,
-                    (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tu0).count() / 1e3,
-                    stager_upload_choice(c->stager, nullptr, nullptr));
-        }
-    }
-    HIPCHK(c, hipMemsetAsync(d_res.p, 0, o_kst, c->stream));   // (what lies behind is fully written by its kernels)
-    HIPCHK(c, hipMemcpyAsync((char *)d_res.p + o_tw, tw, sizeof tw, hipMemcpyHostToDevice, c->stream));
-    A.pcm = pcm_dev ? pcm_dev : d_pcm.as<float>();
-    char *rb = (char *)d_res.p;
-    A.peaks = (float *)(rb + o_peaks);
-    A.sumsq_part = (float *)(rb + o_sumsq);
-    A.peak_bits = (unsigned long long *)(rb + o_pk);
-    A.block_part = (double *)(rb + o_blocks);
-    A.fft_tw = (const float *)(rb + o_tw);
-    A.band_sqrt = (float *)(rb + o_band);
-    A.peak_bin = (unsigned int *)(rb + o_bin);
-    A.kqpart = (double *)(rb + o_kq);
-    A.kstate = (double *)(rb + o_kst);
-    A.sq_dsum = (double *)(rb + o_sqd);
-    A.sq_rec = (double *)(rb + o_sqr);
-    A.peak_part = (double *)(rb + o_pkp);
-    A.cvs = d_cvs.as<unsigned int>();
-    if (!c->an_side_ready && !getenv("FLO_ANALYSIS_ONE_STREAM")) {
-        HIPCHK(c, hipEventCreateWithFlags(&c->an_side.fork, hipEventDisableTiming));
-        for (int i = 0; i < 3; i++) {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->an_side.st[i], hipStreamNonBlocking));
-            HIPCHK(c, hipEventCreateWithFlags(&c->an_side.join[i], hipEventDisableTiming));
-        }
-        c->an_side_ready = true;
-    }
-    rc = timed_launch(c, "analysis", [&] { return launch_analysis(A, c->stream, c->an_side_ready ? &c->an_side : nullptr); });
-    if (rc != FLO_OK && c->an_side_ready)   // (a failed launch may have left a side stream unjoined: the buffers below must outlive it)
-        for (int i = 0; i < 3; i++) hipStreamSynchronize(c->an_side.st[i]);
-    if (rc != FLO_OK) {
-        hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    std::vector<uint8_t> res(o_kst);   // (what lies behind - filter states, the chunk records of the sum of squares - stays on the device)
-    uint32_t root[8];
-    HIPCHK(c, hipMemcpyAsync(res.data(), d_res.p, o_kst, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(root, d_cvs.as<unsigned int>() + 2 * A.n_chunks * 8, 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return tw_table.v;
+}
+// what an analysis holds before the device has seen the samples (all of it for an empty clip)
+static void analysis_defaults(flo_analysis *out, size_t n, uint32_t sr, uint8_t ch) {
+    memset(out, 0, sizeof *out);
+    out->sample_rate = sr;
+    out->channels = ch;
+    out->integrated_lufs = -23.0;
+    out->loudness_range_lu = 0.0;
+    out->true_peak_dbtp = -150.0;
+    out->sample_peak_dbfs = -150.0;
+    out->length_ms = (uint64_t)((double)(n / ch) / (double)sr * 1000.0);
+}
+// what comes back from the device for one clip, and the host's share of the analysis: peak normalisation, the
+// fingerprint's u8 scalings, the two gates over the block energies `en` (ebu_r128.rs:268-318) and the peaks in dB
+struct AnalysisRaw {
+    const float *peaks, *sumsq_part, *band;   // [n_peaks] before normalisation | [n_sq_seg] | [3][16]
+    const uint32_t *bin, *root;               // [3][8] | [8]
+    const unsigned long long *peak_bits;      // [2]
+};
+static void analysis_finish(const AnalysisArgs &A, const AnalysisRaw &R, const std::vector<double> &en, float *peaks, flo_analysis *out) {
+    const size_t n = A.n;
+    const uint32_t sr = A.sample_rate;
+    const uint64_t spc = n / A.channels;
     // waveform peaks: normalise by the largest (analysis.rs:103-109)
     {
-        const float *pk = (const float *)(res.data() + o_peaks);
+        const float *pk = R.peaks;
         float mx = 0.f;
         for (unsigned i = 0; i < A.n_peaks; i++) mx = max_rust(mx, pk[i]);
         for (unsigned i = 0; i < A.n_peaks; i++) peaks[i] = mx > 0.f ? pk[i] / mx : pk[i];
@@ -2620,9 +2604,9 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
         const uint32_t d = dms >= 4294967295.0 ? 4294967295u : (dms <= 0 ? 0u : (uint32_t)dms);
         out->duration_ms = d < 1 ? 1 : d;
         for (int i = 0; i < 8; i++)
-            for (int k = 0; k < 4; k++) out->hash[4 * i + k] = (uint8_t)(root[i] >> (8 * k));
-        const float *bs = (const float *)(res.data() + o_band);
-        const uint32_t *pb = (const uint32_t *)(res.data() + o_bin);
+            for (int k = 0; k < 4; k++) out->hash[4 * i + k] = (uint8_t)(R.root[i] >> (8 * k));
+        const float *bs = R.band;
+        const uint32_t *pb = R.bin;
         float bands[16] = {0};
         uint8_t pk8[8] = {0};
         for (int p = 0; p < 3; p++) {
@@ -2638,51 +2622,18 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
         for (int b = 0; b < 16; b++) out->energy_profile[b] = mx > 0.f ? f32_as_u8(bands[b] / mx * 255.0f) : 0;
         memcpy(out->frequency_peaks, pk8, 8);
         float sumsq = 0.f;   // the segments' partial sums, in order (one segment: the reference's own sequential sum)
-        for (unsigned i = 0; i < A.n_sq_seg; i++) sumsq = i ? sumsq + ((const float *)(res.data() + o_sumsq))[i] : ((const float *)(res.data() + o_sumsq))[0];
+        for (unsigned i = 0; i < A.n_sq_seg; i++) sumsq = i ? sumsq + R.sumsq_part[i] : R.sumsq_part[0];
         out->sum_squares = sumsq;
         if (A.sq_exact && getenv("FLO_TRACE"))
             fprintf(stderr, "[analysis] sum of squares: %llu chunks, %g walked sample by sample\n", (unsigned long long)A.n_sq_chunks,
-                    (double)((const float *)(res.data() + o_sumsq))[1]);
+                    (double)R.sumsq_part[1]);
         const float rms = sumsq / (float)n;
         float v = -20.0f * log10f(rms + 1e-10f);
         if (v == v) v = v < -60.0f ? -60.0f : (v > 0.0f ? 0.0f : v);
         out->avg_loudness = f32_as_u8(v + 60.0f);
     }
-    // loudness: block energies summed over channels, the two gates, the range of the gated block loudness and the two
-    // peaks (ebu_r128.rs:211-355)
+    // loudness: the two gates, the range of the gated block loudness and the two peaks (ebu_r128.rs:211-355)
     {
-        const double *part = (const double *)(res.data() + o_blocks);
-        std::vector<double> fastpart;
-        if (A.fast) {
-            // the segments' shares of every 100 ms quantum, added in segment order; a block is its four quanta, in order
-            const uint64_t nq = (frames + A.hop - 1) / A.hop;
-            const double *kq = (const double *)(res.data() + o_kq);
-            std::vector<double> quanta((size_t)ch * nq, 0.0);
-            for (unsigned cc = 0; cc < ch; cc++)
-                for (uint64_t sg = 0; sg < A.n_kseg; sg++) {
-                    const uint64_t f0 = sg * A.kseg_frames, f1 = std::min<uint64_t>(f0 + A.kseg_frames, frames);
-                    if (f1 <= f0) continue;
-                    const uint64_t q0 = f0 / A.hop, q1 = (f1 - 1) / A.hop;
-                    for (uint64_t q = q0; q <= q1; q++) quanta[(size_t)cc * nq + q] += kq[((size_t)cc * A.n_kseg + sg) * A.kq + (q - q0)];
-                }
-            fastpart.assign((size_t)ch * A.n_blocks * 2, 0.0);
-            for (unsigned cc = 0; cc < ch; cc++)
-                for (unsigned k = 0; k < A.n_blocks; k++) {
-                    double e = 0.0;
-                    for (uint64_t q = k; q < (uint64_t)k + 4 && q < nq; q++) e += quanta[(size_t)cc * nq + q];
-                    fastpart[((size_t)cc * A.n_blocks + k) * 2] = e;
-                }
-            part = fastpart.data();
-        }
-        std::vector<double> en(A.n_blocks);
-        for (unsigned k = 0; k < A.n_blocks; k++) {
-            double e = 0.0;
-            for (unsigned cc = 0; cc < ch; cc++) {
-                const double *pp = part + ((size_t)cc * A.n_blocks + k) * 2;
-                e += (pp[0] + pp[1]) / (double)block_len[k];   // (a block inside one segment: x + 0.0, exact)
-            }
-            en[k] = e;
-        }
         double lufs = -23.0, lra = 0.0;
         if (!en.empty()) {
             const double abs_gate = std::pow(10.0, (-70.0 + 0.691) / 10.0);
@@ -2718,13 +2669,142 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
         }
         out->integrated_lufs = lufs;
         out->loudness_range_lu = lra;
-        const unsigned long long *pb = (const unsigned long long *)(res.data() + o_pk);
+        const unsigned long long *pb = R.peak_bits;
         double sp, tp;
         memcpy(&sp, &pb[0], 8);
         memcpy(&tp, &pb[1], 8);
         out->sample_peak_dbfs = sp > 1e-6 ? 20.0 * std::log10(sp) : -150.0;
         out->true_peak_dbtp = tp > 1e-9 ? 20.0 * std::log10(tp) : -150.0;
     }
+}
+
+// the analysis' three side streams, made once per context (FLO_ANALYSIS_ONE_STREAM=1: none, everything on the context's stream)
+static int analysis_side(flo_ctx *c) {
+    if (!c->an_side_ready && !getenv("FLO_ANALYSIS_ONE_STREAM")) {
+        HIPCHK(c, hipEventCreateWithFlags(&c->an_side.fork, hipEventDisableTiming));
+        for (int i = 0; i < 3; i++) {
+            HIPCHK(c, hipStreamCreateWithFlags(&c->an_side.st[i], hipStreamNonBlocking));
+            HIPCHK(c, hipEventCreateWithFlags(&c->an_side.join[i], hipEventDisableTiming));
+        }
+        c->an_side_ready = true;
+    }
+    return FLO_OK;
+}
+
+// pcm_dev: the samples are already on the device (a batch's clip): nothing is staged
+static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size_t n, uint32_t sr, uint8_t ch, uint32_t pps, float *peaks,
+                        size_t peaks_cap, flo_analysis *out) {
+    if (!c || !out || (n && !pcm && !pcm_dev) || !ch || !sr || !pps) return c ? fail(c, FLO_ERR_ARG, "flo_analyze: bad argument") : FLO_ERR_ARG;
+    analysis_defaults(out, n, sr, ch);
+    HIPCHK(c, hipSetDevice(c->device));
+    AnalysisArgs A{};
+    std::vector<uint64_t> block_len;
+    analysis_geometry(A, n, sr, ch, pps, &block_len);
+    out->n_peaks = A.n_peaks;
+    if (!n) return FLO_OK;
+    if (peaks_cap < A.n_peaks) return fail(c, FLO_ERR_ARG, "flo_analyze: peak buffer too small");
+    const uint64_t frames = n / ch;
+    const float *tw = analysis_twiddles();
+    // device buffers: pcm | results
+    DevMem d_pcm, d_res, d_cvs;
+    QuiesceOnExit quiesce_d_pcm(c);
+    if (!pcm_dev) HIPCHK(c, pool_alloc(&d_pcm.p, n * 4 + 64));
+    const size_t o_peaks = 0, o_sumsq = o_peaks + (((size_t)A.n_peaks * 4 + 15) & ~(size_t)15),
+                 o_pk = o_sumsq + (((size_t)A.n_sq_seg * 4 + 15) & ~(size_t)15), o_blocks = o_pk + 16,
+                 o_tw = o_blocks + (((size_t)ch * A.n_blocks * 16 + 15) & ~(size_t)15), o_band = o_tw + kAnTwBytes, o_bin = o_band + 3 * 16 * 4,
+                 o_kq = (o_bin + 3 * 8 * 4 + 15) & ~(size_t)15, o_kst = o_kq + (A.fast ? (size_t)ch * A.n_kseg * A.kq * 8 : 0),
+                 o_sqd = o_kst + (A.fast ? (size_t)ch * A.n_kseg * 32 : 0), o_sqr = o_sqd + (A.sq_exact ? (A.n_sq_chunks + 1) * 8 : 0),
+                 o_pkp = o_sqr + (A.sq_exact ? A.n_sq_chunks * 64 : 0),
+                 res_bytes = o_pkp + (A.fast ? ((((n + ch - 1) / ch + 2047) / 2048) * ch * 16) : 0);
+    HIPCHK(c, pool_alloc(&d_res.p, res_bytes + 64));
+    HIPCHK(c, pool_alloc(&d_cvs.p, (2 * A.n_chunks + 1) * 32 + 64));
+    int rc = ctx_stager(c);
+    if (rc != FLO_OK) return rc;
+    if (!pcm_dev) {
+        std::vector<UploadSeg> segs{{d_pcm.p, pcm, n * 4}};
+        std::string err;
+        const auto tu0 = std::chrono::steady_clock::now();
+        if (stager_upload(c->stager, segs, c->stream, err) != 0) return fail(c, FLO_ERR_DEVICE, err);
+        if (getenv("FLO_TRACE")) {
+            hipStreamSynchronize(c->stream);
+            fprintf(stderr, "[flo] analysis: upload of %.1f MB took %.0f us (%s)\n", (double)n * 4 / 1e6,
+                    (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tu0).count() / 1e3,
+                    stager_upload_choice(c->stager, nullptr, nullptr));
+        }
+    }
+    HIPCHK(c, hipMemsetAsync(d_res.p, 0, o_kst, c->stream));   // (what lies behind is fully written by its kernels)
+    HIPCHK(c, hipMemcpyAsync((char *)d_res.p + o_tw, tw, kAnTwBytes, hipMemcpyHostToDevice, c->stream));
+    A.pcm = pcm_dev ? pcm_dev : d_pcm.as<float>();
+    char *rb = (char *)d_res.p;
+    A.peaks = (float *)(rb + o_peaks);
+    A.sumsq_part = (float *)(rb + o_sumsq);
+    A.peak_bits = (unsigned long long *)(rb + o_pk);
+    A.block_part = (double *)(rb + o_blocks);
+    A.fft_tw = (const float *)(rb + o_tw);
+    A.band_sqrt = (float *)(rb + o_band);
+    A.peak_bin = (unsigned int *)(rb + o_bin);
+    A.kqpart = (double *)(rb + o_kq);
+    A.kstate = (double *)(rb + o_kst);
+    A.sq_dsum = (double *)(rb + o_sqd);
+    A.sq_rec = (double *)(rb + o_sqr);
+    A.peak_part = (double *)(rb + o_pkp);
+    A.cvs = d_cvs.as<unsigned int>();
+    if ((rc = analysis_side(c)) != FLO_OK) return rc;
+    rc = timed_launch(c, "analysis", [&] { return launch_analysis(A, c->stream, c->an_side_ready ? &c->an_side : nullptr); });
+    if (rc != FLO_OK && c->an_side_ready)   // (a failed launch may have left a side stream unjoined: the buffers below must outlive it)
+        for (int i = 0; i < 3; i++) hipStreamSynchronize(c->an_side.st[i]);
+    if (rc != FLO_OK) {
+        hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    std::vector<uint8_t> res(o_kst);   // (what lies behind - filter states, the chunk records of the sum of squares - stays on the device)
+    uint32_t root[8];
+    HIPCHK(c, hipMemcpyAsync(res.data(), d_res.p, o_kst, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(root, d_cvs.as<unsigned int>() + 2 * A.n_chunks * 8, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // block energies summed over channels (ebu_r128.rs:211-266)
+    std::vector<double> en(A.n_blocks);
+    {
+        const double *part = (const double *)(res.data() + o_blocks);
+        std::vector<double> fastpart;
+        if (A.fast) {
+            // the segments' shares of every 100 ms quantum, added in segment order; a block is its four quanta, in order
+            const uint64_t nq = (frames + A.hop - 1) / A.hop;
+            const double *kq = (const double *)(res.data() + o_kq);
+            std::vector<double> quanta((size_t)ch * nq, 0.0);
+            for (unsigned cc = 0; cc < ch; cc++)
+                for (uint64_t sg = 0; sg < A.n_kseg; sg++) {
+                    const uint64_t f0 = sg * A.kseg_frames, f1 = std::min<uint64_t>(f0 + A.kseg_frames, frames);
+                    if (f1 <= f0) continue;
+                    const uint64_t q0 = f0 / A.hop, q1 = (f1 - 1) / A.hop;
+                    for (uint64_t q = q0; q <= q1; q++) quanta[(size_t)cc * nq + q] += kq[((size_t)cc * A.n_kseg + sg) * A.kq + (q - q0)];
+                }
+            fastpart.assign((size_t)ch * A.n_blocks * 2, 0.0);
+            for (unsigned cc = 0; cc < ch; cc++)
+                for (unsigned k = 0; k < A.n_blocks; k++) {
+                    double e = 0.0;
+                    for (uint64_t q = k; q < (uint64_t)k + 4 && q < nq; q++) e += quanta[(size_t)cc * nq + q];
+                    fastpart[((size_t)cc * A.n_blocks + k) * 2] = e;
+                }
+            part = fastpart.data();
+        }
+        for (unsigned k = 0; k < A.n_blocks; k++) {
+            double e = 0.0;
+            for (unsigned cc = 0; cc < ch; cc++) {
+                const double *pp = part + ((size_t)cc * A.n_blocks + k) * 2;
+                e += (pp[0] + pp[1]) / (double)block_len[k];   // (a block inside one segment: x + 0.0, exact)
+            }
+            en[k] = e;
+        }
+    }
+    AnalysisRaw R{};
+    R.peaks = (const float *)(res.data() + o_peaks);
+    R.sumsq_part = (const float *)(res.data() + o_sumsq);
+    R.band = (const float *)(res.data() + o_band);
+    R.bin = (const uint32_t *)(res.data() + o_bin);
+    R.root = root;
+    R.peak_bits = (const unsigned long long *)(res.data() + o_pk);
+    analysis_finish(A, R, en, peaks, out);
     return FLO_OK;
 }
 
@@ -2733,18 +2813,8 @@ extern "C" int flo_analyze(flo_ctx *c, const float *pcm, size_t n, uint32_t sr, 
     return analyze_impl(c, pcm, nullptr, n, sr, ch, pps, peaks, peaks_cap, out);
 }
 
-static int analysis_metadata_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size_t n, uint32_t sr, uint8_t ch, uint32_t pps,
-                                  uint8_t **out, size_t *out_len) {
-    if (!c || !out || !out_len) return FLO_ERR_ARG;
-    *out = nullptr;
-    *out_len = 0;
-    if (!ch || !sr || !pps) return fail(c, FLO_ERR_ARG, "flo_analysis_metadata: bad argument");
-    // (one peak per 1 / pps seconds: ceil(frames * pps / rate) of them - a vector of one float per sample frame was 32 MB of
-    // zeroed fresh pages for a 3-minute clip, 4 ms of a 7 ms call)
-    std::vector<float> peaks((size_t)std::ceil((double)(n / ch) * (double)pps / (double)sr) + 16);
-    flo_analysis an;
-    int rc = analyze_impl(c, pcm, pcm_dev, n, sr, ch, pps, peaks.data(), peaks.size(), &an);
-    if (rc != FLO_OK) return rc;
+// the MessagePack META of one analysis (rmp_serde::to_vec_named of FloMetadata: the fields that are set, in order)
+static std::vector<uint8_t> analysis_meta_bytes(const flo_analysis &an, const float *peaks, uint32_t pps, size_t n, uint32_t sr, uint8_t ch) {
     Mp m, fp;
     m.b.push_back(0x84);
     m.s("length_ms");
@@ -2785,11 +2855,26 @@ static int analysis_metadata_impl(flo_ctx *c, const float *pcm, const float *pcm
     m.u(0);
     m.s("lufs");
     m.f((float)an.integrated_lufs);
-    uint8_t *p = (uint8_t *)malloc(m.b.size());
+    return std::move(m.b);
+}
+static int analysis_metadata_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size_t n, uint32_t sr, uint8_t ch, uint32_t pps,
+                                  uint8_t **out, size_t *out_len) {
+    if (!c || !out || !out_len) return FLO_ERR_ARG;
+    *out = nullptr;
+    *out_len = 0;
+    if (!ch || !sr || !pps) return fail(c, FLO_ERR_ARG, "flo_analysis_metadata: bad argument");
+    // (one peak per 1 / pps seconds: ceil(frames * pps / rate) of them - a vector of one float per sample frame was 32 MB of
+    // zeroed fresh pages for a 3-minute clip, 4 ms of a 7 ms call)
+    std::vector<float> peaks((size_t)std::ceil((double)(n / ch) * (double)pps / (double)sr) + 16);
+    flo_analysis an;
+    int rc = analyze_impl(c, pcm, pcm_dev, n, sr, ch, pps, peaks.data(), peaks.size(), &an);
+    if (rc != FLO_OK) return rc;
+    const std::vector<uint8_t> mb = analysis_meta_bytes(an, peaks.data(), pps, n, sr, ch);
+    uint8_t *p = (uint8_t *)malloc(mb.size());
     if (!p) return fail(c, FLO_ERR_NOMEM, "malloc failed");
-    memcpy(p, m.b.data(), m.b.size());
+    memcpy(p, mb.data(), mb.size());
     *out = p;
-    *out_len = m.b.size();
+    *out_len = mb.size();
     return FLO_OK;
 }
 extern "C" int flo_analysis_metadata(flo_ctx *c, const float *pcm, size_t n, uint32_t sr, uint8_t ch, uint32_t pps,
@@ -2801,6 +2886,239 @@ extern "C" int flo_analysis_metadata(flo_ctx *c, const float *pcm, size_t n, uin
 extern "C" int flo_batch_analysis_metadata(flo_batch *b, size_t clip, uint32_t pps, uint8_t **out, size_t *out_len) {
     if (!b || clip >= b->n_clips) return FLO_ERR_ARG;
     return analysis_metadata_impl(b->ctx, nullptr, b->n_il[clip] ? b->d_pcm + b->clip_off[clip] : nullptr, b->n_il[clip], b->sr, b->ch, pps, out, out_len);
+}
+// ------------------------------------------------------------------------------------------------ batched analysis
+// flo_batch_analyze_all: every clip's AnalysisArgs (the per-clip geometry, analysis_geometry) becomes a descriptor, the
+// kernels of launch_analysis_batch (analysis_batch_kernels.hip) run over groups of clips - one fixed set of launches per
+// group - and one read-back brings every clip's results home: the raw peaks, the fingerprint's pieces, the two peak maxima
+// and the block energies, already built on the device in the host's order of additions. The host's share per clip is that
+// of the per-clip path (analysis_finish). A group's scratch (filter states, quanta, the chunk records of the sum of
+// squares, the hash's chaining values; ~460 KB for 10 s of stereo) stays under FLO_BATCH_ANALYSIS_GROUP_BYTES (1 GiB).
+namespace {
+constexpr size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+// one clip's results: peaks [n_peaks] | sum of squares [2] | peak bits [2] | band [3][16] | bin [3][8] | root [8] | energies [n_blocks]
+struct AnResLayout {
+    size_t peaks, sumsq, pk, band, bin, root, en, bytes;
+    explicit AnResLayout(const AnalysisArgs &A) {
+        peaks = 0;
+        sumsq = al16((size_t)A.n_peaks * 4);
+        pk = sumsq + 16;
+        band = pk + 16;
+        bin = band + 3 * 16 * 4;
+        root = bin + 3 * 8 * 4;
+        en = root + 32;
+        bytes = al16(en + (size_t)A.n_blocks * 8);
+    }
+};
+// one clip's scratch: zeroed before the group (block sums, quanta) | not (filter states, chunk records, maxima, hash)
+struct AnScratch {
+    size_t blocks, kq, zbytes, kst, sqd, sqr, pkp, cvs, ubytes;
+    explicit AnScratch(const AnalysisArgs &A) {
+        const size_t ch = A.channels, tiles = (size_t)(((A.n + ch - 1) / ch + kAnTile - 1) / kAnTile);
+        blocks = 0;
+        kq = al16(A.fast ? 0 : ch * A.n_blocks * 16);
+        zbytes = al16(kq + (A.fast ? ch * A.n_kseg * A.kq * 8 : 0));
+        kst = 0;
+        sqd = al16(A.fast ? ch * A.n_kseg * 32 : 0);
+        sqr = al16(sqd + (A.sq_exact ? (A.n_sq_chunks + 1) * 8 : 0));
+        pkp = al16(sqr + (A.sq_exact ? A.n_sq_chunks * 64 : 0));
+        cvs = al16(pkp + (A.fast ? tiles * ch * 16 : 0));
+        ubytes = al16(cvs + (A.n ? (2 * A.n_chunks + 1) * 32 : 0));
+    }
+};
+struct AnGroup {
+    size_t first = 0, count = 0, zbytes = 0, ubytes = 0, pre_off = 0;
+    unsigned long long total[kAnlCount] = {};
+};
+}  // namespace
+
+// workgroups of every list for one clip (an_batch_per_wg items each)
+static void an_batch_wgs(const AnalysisArgs &A, unsigned long long (&wg)[kAnlCount]) {
+    an_batch_items(A, wg);
+    for (int k = 0; k < kAnlCount; k++) wg[k] = (wg[k] + an_batch_per_wg(k) - 1) / an_batch_per_wg(k);
+}
+static size_t batch_analysis_group_bytes() {
+    const char *e = getenv("FLO_BATCH_ANALYSIS_GROUP_BYTES");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (size_t)v : ((size_t)1 << 30);
+}
+
+static void batch_peak_offsets(const flo_batch *b, uint32_t pps, std::vector<AnalysisArgs> &A, uint64_t *peak_off) {
+    A.assign(b->n_clips, AnalysisArgs{});
+    peak_off[0] = 0;
+    for (size_t i = 0; i < b->n_clips; i++) {
+        analysis_geometry(A[i], b->n_il[i], b->sr, b->ch, pps, nullptr, true);
+        peak_off[i + 1] = peak_off[i] + A[i].n_peaks;
+    }
+}
+
+extern "C" int flo_batch_analyze_all(flo_batch *b, uint32_t pps, flo_analysis *out, float *peaks, size_t peaks_cap, uint64_t *peak_off) {
+    if (!b) return FLO_ERR_ARG;
+    flo_ctx *c = b->ctx;
+    if (!pps) return fail(c, FLO_ERR_ARG, "flo_batch_analyze_all: peaks_per_second must be non-zero");
+    if (!peak_off || (peaks && !out)) return fail(c, FLO_ERR_ARG, "flo_batch_analyze_all: NULL output");
+    std::vector<AnalysisArgs> A;
+    batch_peak_offsets(b, pps, A, peak_off);
+    if (!peaks) return FLO_OK;   // the sizing call
+    const size_t n_clips = b->n_clips;
+    if (peaks_cap < peak_off[n_clips]) return fail(c, FLO_ERR_ARG, "flo_batch_analyze_all: peak buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    for (size_t i = 0; i < n_clips; i++) {
+        analysis_defaults(&out[i], b->n_il[i], b->sr, b->ch);
+        out[i].n_peaks = A[i].n_peaks;
+    }
+    if (!n_clips) return FLO_OK;
+    // geometry, results and scratch of every clip; the groups
+    std::vector<size_t> res_off(n_clips + 1, 0), z_off(n_clips), u_off(n_clips), stage_off(n_clips, SIZE_MAX);
+    std::vector<AnGroup> groups;
+    const size_t cap = batch_analysis_group_bytes();
+    const unsigned long long max_items = 1ull << 22;   // workgroups per launch (a single clip may have more, as alone)
+    size_t stage_floats = 0;
+    const AnalysisArgs *like = nullptr;   // (the last clip with samples: its rate's coefficients are reused)
+    for (size_t i = 0; i < n_clips; i++) {
+        A[i] = AnalysisArgs{};
+        analysis_geometry(A[i], b->n_il[i], b->sr, b->ch, pps, nullptr, false, like);
+        if (A[i].n) like = &A[i];
+        res_off[i + 1] = res_off[i] + AnResLayout(A[i]).bytes;
+        if (i < b->tail.size() && !b->tail[i].empty()) {   // an odd-length lossy clip: staged whole (frames, then the tail)
+            stage_off[i] = stage_floats;
+            stage_floats += al16(b->n_il[i] * 4 + 64) / 4;
+        }
+        const AnScratch S(A[i]);
+        unsigned long long it[kAnlCount];
+        an_batch_wgs(A[i], it);
+        bool fits = !groups.empty() && groups.back().zbytes + groups.back().ubytes + S.zbytes + S.ubytes <= cap;
+        for (int k = 0; fits && k < kAnlCount; k++) fits = groups.back().total[k] + it[k] <= max_items;
+        if (!fits) {
+            groups.emplace_back();
+            groups.back().first = i;
+        }
+        AnGroup &g = groups.back();
+        z_off[i] = g.zbytes;
+        u_off[i] = g.ubytes;
+        g.zbytes += S.zbytes;
+        g.ubytes += S.ubytes;
+        g.count++;
+        for (int k = 0; k < kAnlCount; k++) g.total[k] += it[k];
+    }
+    size_t scratch_bytes = 16;
+    for (const AnGroup &g : groups) scratch_bytes = std::max(scratch_bytes, al16(g.zbytes) + g.ubytes);
+    // one upload: descriptors | twiddles | the work lists' prefixes of every group
+    const size_t o_tw = al16(n_clips * sizeof(AnalysisArgs)), o_pre = o_tw + kAnTwBytes;
+    size_t pre_words = 0;
+    for (AnGroup &g : groups) {
+        g.pre_off = pre_words;
+        pre_words += (size_t)kAnlCount * (g.count + 1);
+    }
+    std::vector<uint8_t> up(o_pre + pre_words * 4, 0);   // (outlives the stream: destroyed behind `quiesce`)
+    DevMem d_desc, d_res, d_scr, d_stage;
+    QuiesceOnExit quiesce(c);
+    HIPCHK(c, pool_alloc(&d_desc.p, o_pre + pre_words * 4 + 64));
+    HIPCHK(c, pool_alloc(&d_res.p, res_off[n_clips] + 64));
+    HIPCHK(c, pool_alloc(&d_scr.p, scratch_bytes + 64));
+    if (stage_floats) HIPCHK(c, pool_alloc(&d_stage.p, stage_floats * 4 + 64));
+    char *rb = (char *)d_res.p, *sb = (char *)d_scr.p;
+    const float *d_tw = (const float *)((char *)d_desc.p + o_tw);
+    for (const AnGroup &g : groups) {
+        uint32_t *pre = (uint32_t *)(up.data() + o_pre) + g.pre_off;
+        for (int k = 0; k < kAnlCount; k++) pre[(size_t)k * (g.count + 1)] = 0;
+        for (size_t j = 0; j < g.count; j++) {
+            const size_t i = g.first + j;
+            AnalysisArgs &a = A[i];
+            unsigned long long it[kAnlCount];
+            an_batch_wgs(a, it);
+            for (int k = 0; k < kAnlCount; k++) pre[(size_t)k * (g.count + 1) + j + 1] = pre[(size_t)k * (g.count + 1) + j] + (uint32_t)it[k];
+            a.pcm = stage_off[i] != SIZE_MAX ? d_stage.as<float>() + stage_off[i] : b->d_pcm + b->clip_off[i];
+            const AnResLayout R(a);
+            char *r = rb + res_off[i];
+            a.peaks = (float *)(r + R.peaks);
+            a.sumsq_part = (float *)(r + R.sumsq);
+            a.peak_bits = (unsigned long long *)(r + R.pk);
+            a.band_sqrt = (float *)(r + R.band);
+            a.peak_bin = (unsigned int *)(r + R.bin);
+            a.root = (unsigned int *)(r + R.root);
+            a.block_energy = (double *)(r + R.en);
+            a.fft_tw = d_tw;
+            const AnScratch S(a);
+            char *z = sb + z_off[i], *u = sb + al16(g.zbytes) + u_off[i];
+            a.block_part = (double *)(z + S.blocks);
+            a.kqpart = (double *)(z + S.kq);
+            a.kstate = (double *)(u + S.kst);
+            a.sq_dsum = (double *)(u + S.sqd);
+            a.sq_rec = (double *)(u + S.sqr);
+            a.peak_part = (double *)(u + S.pkp);
+            a.cvs = (unsigned int *)(u + S.cvs);
+        }
+    }
+    memcpy(up.data(), A.data(), n_clips * sizeof(AnalysisArgs));
+    memcpy(up.data() + o_tw, analysis_twiddles(), kAnTwBytes);
+    HIPCHK(c, hipMemcpyAsync(d_desc.p, up.data(), up.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_res.p, 0, res_off[n_clips], c->stream));
+    for (size_t i = 0; i < n_clips; i++)
+        if (stage_off[i] != SIZE_MAX) {
+            float *dst = d_stage.as<float>() + stage_off[i];
+            const size_t whole = b->clip_nsf[i] * b->ch, nt = b->tail[i].size();
+            if (whole) HIPCHK(c, hipMemcpyAsync(dst, b->d_pcm + b->clip_off[i], whole * 4, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(dst + whole, b->tail[i].data(), nt * 4, hipMemcpyHostToDevice, c->stream));
+        }
+    int rc = analysis_side(c);
+    if (rc != FLO_OK) return rc;
+    const AnalysisArgs *d_clips = (const AnalysisArgs *)d_desc.p;
+    const uint32_t *d_pre = (const uint32_t *)((char *)d_desc.p + o_pre);
+    for (const AnGroup &g : groups) {
+        if (g.zbytes) HIPCHK(c, hipMemsetAsync(sb, 0, g.zbytes, c->stream));   // (the previous group's kernels on this stream are done with it)
+        const AnBatchArgs G{d_clips + g.first, d_pre + g.pre_off, (unsigned)g.count};
+        rc = timed_launch(c, "analysis_batch", [&] { return launch_analysis_batch(G, g.total, c->stream, c->an_side_ready ? &c->an_side : nullptr); });
+        if (rc != FLO_OK) {
+            if (c->an_side_ready)   // (a failed launch may have left a side stream unjoined: the buffers must outlive it)
+                for (int i = 0; i < 3; i++) hipStreamSynchronize(c->an_side.st[i]);
+            hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    }
+    std::vector<uint8_t> res(res_off[n_clips]);
+    HIPCHK(c, hipMemcpyAsync(res.data(), d_res.p, res.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n_clips; i++) {
+        if (!A[i].n) continue;
+        const AnResLayout L(A[i]);
+        const uint8_t *r = res.data() + res_off[i];
+        AnalysisRaw R{};
+        R.peaks = (const float *)(r + L.peaks);
+        R.sumsq_part = (const float *)(r + L.sumsq);
+        R.band = (const float *)(r + L.band);
+        R.bin = (const uint32_t *)(r + L.bin);
+        R.root = (const uint32_t *)(r + L.root);
+        R.peak_bits = (const unsigned long long *)(r + L.pk);
+        const double *e = (const double *)(r + L.en);
+        analysis_finish(A[i], R, std::vector<double>(e, e + A[i].n_blocks), peaks + peak_off[i], &out[i]);
+    }
+    return FLO_OK;
+}
+
+extern "C" int flo_batch_analysis_metadata_all(flo_batch *b, uint32_t pps, uint8_t **out, uint64_t *off) {
+    if (!b) return FLO_ERR_ARG;
+    flo_ctx *c = b->ctx;
+    if (!out || !off) return fail(c, FLO_ERR_ARG, "flo_batch_analysis_metadata_all: NULL output");
+    *out = nullptr;
+    std::vector<uint64_t> poff(b->n_clips + 1);
+    int rc = flo_batch_analyze_all(b, pps, nullptr, nullptr, 0, poff.data());
+    if (rc != FLO_OK) return rc;
+    std::vector<float> peaks(poff[b->n_clips] + 1);
+    std::vector<flo_analysis> an(b->n_clips);
+    if ((rc = flo_batch_analyze_all(b, pps, an.data(), peaks.data(), peaks.size(), poff.data())) != FLO_OK) return rc;
+    std::vector<uint8_t> all;
+    off[0] = 0;
+    for (size_t i = 0; i < b->n_clips; i++) {
+        const std::vector<uint8_t> m = analysis_meta_bytes(an[i], peaks.data() + poff[i], pps, b->n_il[i], b->sr, b->ch);
+        all.insert(all.end(), m.begin(), m.end());
+        off[i + 1] = all.size();
+    }
+    uint8_t *p = (uint8_t *)malloc(all.size() ? all.size() : 1);
+    if (!p) return fail(c, FLO_ERR_NOMEM, "malloc failed");
+    if (!all.empty()) memcpy(p, all.data(), all.size());
+    *out = p;
+    return FLO_OK;
 }
 extern "C" int flo_batch_set_bit_depth(flo_batch *b, uint8_t bit_depth) {
     if (!b) return FLO_ERR_ARG;

@@ -236,6 +236,9 @@ int flo_batch_create(flo_ctx *ctx, int mode, size_t n_clips, const size_t *n_int
 void flo_batch_destroy(flo_batch *b);
 /* device pointer to clip i's interleaved f32 PCM (n_interleaved[i] floats) — fill it however you like */
 float *flo_batch_clip_device_ptr(flo_batch *b, size_t clip);
+/* the same address, for reading the clip as it sits in the batch. flo_batch_clip_device_ptr is taken to mean that the
+ * caller writes the clip (a lossy clip's kept trailing samples are then dropped, see flo_batch_analyze_all); this is not */
+const float *flo_batch_clip_device_data(const flo_batch *b, size_t clip);
 /* H2D copy of one clip */
 int flo_batch_upload(flo_batch *b, size_t clip, const float *pcm);
 /* fill every clip with the integer-exact synthetic signal of flo_synth.h (device kernel), seeded by seed;
@@ -357,6 +360,18 @@ int flo_analysis_metadata(flo_ctx *ctx, const float *pcm, size_t n_interleaved, 
  *   flo_batch_create(1 clip); flo_batch_upload; flo_batch_analysis_metadata -> META (merge with the caller's);
  *   flo_batch_set_bit_depth (lossless); flo_batch_encode; flo_batch_sync; flo_batch_fetch(meta) */
 int flo_batch_analysis_metadata(flo_batch *b, size_t clip, uint32_t peaks_per_second, uint8_t **out, size_t *out_len);
+/* the analysis of EVERY clip of a batch (after its uploads) in one device pass: a fixed number of launches per group of
+ * clips, not per clip (groups keep the device scratch under FLO_BATCH_ANALYSIS_GROUP_BYTES, default 1 GiB, read per call).
+ * out[n_clips]; the peaks concatenated, clip i's at peaks[peak_off[i] .. peak_off[i + 1]). With peaks == NULL only
+ * peak_off (n_clips + 1 entries) is filled: the sizing call. Every field, peak and META byte equals what
+ * flo_batch_analysis_metadata / flo_analyze give for a clip whose device copy holds all of the caller's samples.
+ * Lossy clips of n_interleaved % channels != 0 uploaded through flo_batch_upload are analysed over ALL of the caller's
+ * samples (the trailing partial sample-frame, which the encoder drops, is kept on the host for this), as libflo::encode_lossy
+ * does; clips written through flo_batch_clip_device_ptr or flo_batch_fill_synthetic are analysed as the device holds them. */
+int flo_batch_analyze_all(flo_batch *b, uint32_t peaks_per_second, flo_analysis *out, float *peaks, size_t peaks_cap,
+                          uint64_t *peak_off);
+/* the MessagePack META of every clip, concatenated in one malloc'ed buffer (flo_free): clip i's at off[i] .. off[i + 1] */
+int flo_batch_analysis_metadata_all(flo_batch *b, uint32_t peaks_per_second, uint8_t **out, uint64_t *off);
 /* the bit depth a lossless batch's files declare (16 unless set; flo_encode_lossless's argument) */
 int flo_batch_set_bit_depth(flo_batch *b, uint8_t bit_depth);
 
