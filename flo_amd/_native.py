@@ -37,6 +37,8 @@ EXPORTS = [
     "flo_sdec_create", "flo_sdec_destroy", "flo_sdec_attach", "flo_sdec_last_error", "flo_sdec_feed", "flo_sdec_state",
     "flo_sdec_info", "flo_sdec_frames_available", "flo_sdec_available_frames", "flo_sdec_current_frame_index",
     "flo_sdec_buffered_bytes", "flo_sdec_next_frame", "flo_sdec_decode_available", "flo_sdec_reset", "flo_sdec_decode_ready",
+    "flo_spectral_similarity", "flo_fpindex_create", "flo_fpindex_destroy", "flo_fpindex_topk", "flo_fpindex_topk_self",
+    "flo_fpindex_pairs",
 ]
 
 
@@ -69,6 +71,12 @@ class SeekResultC(C.Structure):
 class SdecInfoC(C.Structure):
     _fields_ = [("sample_rate", C.c_uint32), ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("is_lossy", C.c_uint8),
                 ("pad", C.c_uint8), ("total_samples", C.c_uint64)]
+
+
+class Fingerprint(C.Structure):   # flo_fingerprint (SpectralFingerprint, core/analysis.rs:10-26)
+    _fields_ = [("hash", C.c_uint8 * 32), ("duration_ms", C.c_uint32), ("sample_rate", C.c_uint32), ("channels", C.c_uint8),
+                ("avg_loudness", C.c_uint8), ("pad0", C.c_uint8), ("pad1", C.c_uint8), ("frequency_peaks", C.c_uint8 * 8),
+                ("energy_profile", C.c_uint8 * 16)]
 
 
 class FloError(RuntimeError):
@@ -201,5 +209,14 @@ def lib():
     L.flo_sdec_reset.argtypes = [vp]
     L.flo_sdec_reset.restype = None
     L.flo_sdec_decode_ready.argtypes = [vp, sz, vp, C.c_uint32, vp, sz, vp, vp, vp]
+    fpp = C.POINTER(Fingerprint)
+    L.flo_spectral_similarity.argtypes = [fpp, fpp]
+    L.flo_spectral_similarity.restype = C.c_float
+    L.flo_fpindex_create.argtypes = [vp, vp, sz, C.POINTER(vp)]
+    L.flo_fpindex_destroy.argtypes = [vp]
+    L.flo_fpindex_destroy.restype = None
+    L.flo_fpindex_topk.argtypes = [vp, vp, sz, C.c_uint32, vp, vp]
+    L.flo_fpindex_topk_self.argtypes = [vp, C.c_uint32, vp, vp]
+    L.flo_fpindex_pairs.argtypes = [vp, C.c_float, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]
     _LIB = L
     return L

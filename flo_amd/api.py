@@ -991,3 +991,159 @@ def encode_with_bitrate_many(clips, sample_rate, channels, _bit_depth, target_bi
     """encode_with_bitrate (libflo::encode_with_bitrate) of every clip, the analysis of all of them in one device pass"""
     q = QualityPreset.from_bitrate(target_bitrate_kbps, sample_rate, channels).as_f32()
     return _encode_analysed_many(MODE_LOSSY, clips, sample_rate, channels, q, 16, metadata)
+
+
+# -- spectral similarity (core/analysis.rs:359-437) -----------------------------------------------------------------------
+FINGERPRINT_DTYPE = np.dtype([("hash", "u1", 32), ("duration_ms", "<u4"), ("sample_rate", "<u4"), ("channels", "u1"),
+                              ("avg_loudness", "u1"), ("pad0", "u1"), ("pad1", "u1"), ("frequency_peaks", "u1", 8),
+                              ("energy_profile", "u1", 16)])   # flo_fingerprint of include/flo_hip.h
+assert FINGERPRINT_DTYPE.itemsize == C.sizeof(_native.Fingerprint)
+
+
+def fingerprint_array(fps) -> np.ndarray:
+    """Fingerprints as a contiguous FINGERPRINT_DTYPE array. Takes such an array, one fingerprint dict or a sequence of
+    them: the dicts Context.analyze / Batch.analyze_all return, or SpectralFingerprint fields as the META holds them."""
+    if isinstance(fps, np.void):   # one record of such an array
+        fps = np.array(fps, fps.dtype)
+    if isinstance(fps, np.ndarray) and fps.dtype.names:
+        if fps.dtype != FINGERPRINT_DTYPE:
+            raise FloError(f"fingerprint array must have dtype {FINGERPRINT_DTYPE}")
+        return np.ascontiguousarray(fps.reshape(-1))
+    if isinstance(fps, dict):
+        fps = [fps]
+    fps = list(fps)
+    out = np.zeros(len(fps), FINGERPRINT_DTYPE)
+    for i, f in enumerate(fps):
+        h = bytes(bytearray(f["hash"]))
+        if len(h) != 32 or len(f["frequency_peaks"]) != 8 or len(f["energy_profile"]) != 16:
+            raise FloError(f"fingerprint {i}: hash, frequency_peaks and energy_profile must hold 32, 8 and 16 bytes")
+        out[i]["hash"] = np.frombuffer(h, np.uint8)
+        out[i]["duration_ms"] = int(f.get("duration_ms", 0))
+        out[i]["sample_rate"] = int(f["sample_rate"])
+        out[i]["channels"] = int(f["channels"])
+        out[i]["avg_loudness"] = int(f["avg_loudness"])
+        out[i]["frequency_peaks"] = np.asarray(f["frequency_peaks"], np.uint8)
+        out[i]["energy_profile"] = np.asarray(f["energy_profile"], np.uint8)
+    return out
+
+
+def spectral_similarity(fp_a, fp_b) -> np.float32:
+    """spectral_similarity (analysis.rs:395-437; spectral_similarity_score, lib.rs:1357), bit for bit; on the host"""
+    a, b = fingerprint_array(fp_a), fingerprint_array(fp_b)
+    if a.size != 1 or b.size != 1:
+        raise FloError("spectral_similarity compares two single fingerprints")
+    fpp = C.POINTER(_native.Fingerprint)
+    return np.float32(_native.lib().flo_spectral_similarity(C.cast(a.ctypes.data, fpp), C.cast(b.ctypes.data, fpp)))
+
+
+def extract_dominant_frequencies(fp, num_frequencies: int):
+    """extract_dominant_frequencies (analysis.rs:367-387): one frame of at most 8 frequencies in Hz (f64), the peak bands
+    mapped back from 0..255 to 0 .. Nyquist"""
+    f = fingerprint_array(fp)[0]
+    n = min(int(num_frequencies), 8)
+    return [[float(f["frequency_peaks"][i]) / 255.0 * (float(f["sample_rate"]) / 2.0) for i in range(n)]]
+
+
+def file_metadata(flo_bytes: bytes):
+    """the decoded META chunk of a .flo file (a dict), or None when it has none (reflo::get_metadata)"""
+    from . import meta as _meta
+    i = probe_container(flo_bytes)
+    meta_size = int.from_bytes(flo_bytes[62:70], "little")
+    start = i.data_start + i.data_size + int.from_bytes(flo_bytes[54:62], "little")
+    if meta_size == 0 or start + meta_size > len(flo_bytes):
+        return None
+    return _meta.unpack(flo_bytes[start:start + meta_size])
+
+
+def fingerprints_from_files(files) -> np.ndarray:
+    """The `spectrum_fingerprint` each file's META carries (what libflo::encode* store: rmp_serde::to_vec_named of the
+    SpectralFingerprint, lib.rs:244-258), as a FINGERPRINT_DTYPE array. Files are paths or file bytes; a file without a
+    fingerprint raises FloError naming it."""
+    from . import meta as _meta
+    out = []
+    for n, f in enumerate(files):
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            name, data = f"file {n}", bytes(f)
+        else:
+            name = str(f)
+            with open(f, "rb") as fh:
+                data = fh.read()
+        try:
+            md = file_metadata(data)
+        except FloError as ex:
+            raise FloError(f"{name}: {ex}") from None
+        raw = md.get("spectrum_fingerprint") if isinstance(md, dict) else None
+        if not isinstance(raw, (bytes, bytearray)) or not raw:
+            raise FloError(f"{name}: no spectrum_fingerprint in the file's metadata")
+        try:
+            out.append(fingerprint_array(_meta.unpack(bytes(raw)))[0])
+        except (KeyError, TypeError, ValueError, FloError) as ex:
+            raise FloError(f"{name}: unreadable spectrum_fingerprint ({ex})") from None
+    return np.array(out, FINGERPRINT_DTYPE)
+
+
+class FingerprintIndex:
+    """Fingerprints resident on the device (flo_fpindex), compared under spectral_similarity at collection scale.
+
+    topk(queries, k) / topk_self(k) -> (idx [n, k] uint32, score [n, k] float32): the k best members per query, score
+    descending then member index ascending; topk_self never lists a member as its own neighbour. Slots beyond the
+    candidates hold 0xFFFFFFFF and -1.0. pairs(threshold) -> (i, j, score): every pair i < j scoring >= threshold,
+    ordered by (i, j). Every score is the reference's, bit for bit; k is at most 64."""
+
+    def __init__(self, fps, ctx=None):
+        self._ctx = ctx or default_context()
+        self._L = self._ctx._L
+        arr = fingerprint_array(fps)
+        h = C.c_void_p()
+        self._ctx._chk(self._L.flo_fpindex_create(self._ctx._h, arr.ctypes.data, arr.size, C.byref(h)))
+        self._h = h
+        self.n = arr.size
+        self._pair_cap = 1 << 16
+        self._ctx._batches.add(self)   # closed before its context
+
+    def __len__(self):
+        return self.n
+
+    @staticmethod
+    def _k(k):
+        k = int(k)
+        if k < 0:
+            raise FloError("k must not be negative")
+        return k
+
+    def topk(self, queries, k: int):
+        q, k = fingerprint_array(queries), self._k(k)
+        idx, score = np.empty((q.size, k), np.uint32), np.empty((q.size, k), np.float32)
+        self._ctx._chk(self._L.flo_fpindex_topk(self._h, q.ctypes.data, q.size, k, idx.ctypes.data, score.ctypes.data))
+        return idx, score
+
+    def topk_self(self, k: int):
+        k = self._k(k)
+        idx, score = np.empty((self.n, k), np.uint32), np.empty((self.n, k), np.float32)
+        self._ctx._chk(self._L.flo_fpindex_topk_self(self._h, k, idx.ctypes.data, score.ctypes.data))
+        return idx, score
+
+    def pairs(self, threshold: float):
+        n = C.c_uint64()
+        while True:
+            cap = self._pair_cap
+            i, j, s = np.empty(cap, np.uint32), np.empty(cap, np.uint32), np.empty(cap, np.float32)
+            rc = self._L.flo_fpindex_pairs(self._h, float(threshold), cap, i.ctypes.data, j.ctypes.data, s.ctypes.data,
+                                           C.byref(n))
+            if rc == 3 and n.value > cap:   # FLO_ERR_NOMEM: room for the exact count, then again
+                self._pair_cap = int(n.value)
+                continue
+            self._ctx._chk(rc)
+            m = int(n.value)
+            return i[:m].copy(), j[:m].copy(), s[:m].copy()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.flo_fpindex_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

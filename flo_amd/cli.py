@@ -9,6 +9,7 @@ printed fields for the parts that sit on this repository's path -
     validate <in.flo>
     metadata <in.flo> [--json]
     analysis <in.flo> [--waveform] [--spectrum] [--json]
+    similar  <in.flo>... [-k N | --threshold T] [--json]
 Ingestion is WAV only (flo_amd/wav.py; the reference demuxes MP3/FLAC/OGG/AAC through symphonia, reflo/src/audio.rs:57-166).
 `encode` writes the META chunk the reference CLI writes for an untagged file (reflo/src/lib.rs:202-283, flo_amd/meta.py):
 length_ms, encoding_time, encoder_settings, flo_encoder_version, source_format (+ --title / --artist / --album) - the
@@ -16,6 +17,8 @@ reference-made Examples/*.flo are reproduced including META, the encoding time a
 (RIFF INFO) are not carried over. `analysis` (reflo/src/main.rs:619-800) decodes the file and prints what flo_analyze
 computes on the device: EBU R128 loudness, range, true peak and sample peak (core/ebu_r128.rs), and on request the
 waveform peaks at 60 per second and the spectral fingerprint (core/analysis.rs).
+`similar` (not in reflo) compares the spectrum fingerprints the files' META carry under spectral_similarity
+(core/analysis.rs:395-437) on the device: each file's k nearest other files, or every pair at or above a threshold.
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
 """
@@ -65,12 +68,7 @@ def encode_from_audio(audio_bytes: bytes, level=5, lossy=False, quality=0.6, bit
 
 def get_metadata(flo_bytes: bytes):
     """reflo::get_metadata: the decoded META chunk (a dict), or None when the file has none."""
-    i = api.probe_container(flo_bytes)
-    meta_size = int.from_bytes(flo_bytes[62:70], "little")
-    start = i.data_start + i.data_size + int.from_bytes(flo_bytes[54:62], "little")
-    if meta_size == 0 or start + meta_size > len(flo_bytes):
-        return None
-    return meta.unpack(flo_bytes[start:start + meta_size])
+    return api.file_metadata(flo_bytes)
 
 
 def decode_to_wav(flo_bytes: bytes, ctx=None) -> bytes:
@@ -124,6 +122,34 @@ def analysis_report(flo_bytes: bytes, waveform=False, spectrum=False, ctx=None) 
     return out
 
 
+def similar_report(paths, k=None, threshold=None, as_json=False, ctx=None) -> str:
+    """The `similar` command's output: each file's nearest neighbours (k, default 5) among the others, or the pairs
+    scoring at least `threshold`, from the fingerprints in the files' META."""
+    fps = api.fingerprints_from_files(paths)
+    ix = api.FingerprintIndex(fps, ctx)
+    try:
+        if threshold is not None:
+            i, j, s = ix.pairs(threshold)
+            pairs = [(paths[a], paths[b], float(c)) for a, b, c in zip(i.tolist(), j.tolist(), s)]
+            if as_json:
+                return json.dumps({"threshold": threshold, "pairs": [{"a": x, "b": y, "score": c} for x, y, c in pairs]}, indent=2)
+            lines = [f"Pairs with similarity >= {threshold}: {len(pairs)}"]
+            lines += [f"  {c:.6f}  {x}  {y}" for x, y, c in pairs]
+            return "\n".join(lines)
+        idx, score = ix.topk_self(5 if k is None else k)
+        near = [(p, [(paths[j], float(c)) for j, c in zip(idx[n].tolist(), score[n]) if j != 0xFFFFFFFF])
+                for n, p in enumerate(paths)]
+        if as_json:
+            return json.dumps([{"file": p, "neighbours": [{"file": f, "score": c} for f, c in v]} for p, v in near], indent=2)
+        lines = []
+        for p, v in near:
+            lines.append(p)
+            lines += [f"  {c:.6f}  {f}" for f, c in v] or ["  (no other files)"]
+        return "\n".join(lines)
+    finally:
+        ix.close()
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="flo", description="flo audio format converter (MI355X-native encode / decode)")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -153,6 +179,12 @@ def main(argv=None) -> int:
     an.add_argument("-w", "--waveform", action="store_true", help="Show waveform peaks")
     an.add_argument("-s", "--spectrum", action="store_true", help="Show spectral fingerprint")
     an.add_argument("--json", action="store_true", help="Output as JSON")
+    si = sub.add_parser("similar", help="Find similar files by their spectral fingerprints")
+    si.add_argument("inputs", nargs="+", metavar="input")
+    sg = si.add_mutually_exclusive_group()
+    sg.add_argument("-k", type=int, default=None, help="Nearest neighbours per file (default 5, at most 64)")
+    sg.add_argument("--threshold", type=float, default=None, help="List every pair scoring at least this")
+    si.add_argument("--json", action="store_true", help="Output as JSON")
     a = ap.parse_args(argv)
     try:
         if a.command == "encode":
@@ -272,6 +304,8 @@ def main(argv=None) -> int:
                     print(f"  Average loudness:    {sp['average_loudness']}")
                     print(f"  Spectral hash (first 8 bytes):   {sp['spectral_hash_hex']}")
                     print()
+        elif a.command == "similar":
+            print(similar_report(a.inputs, a.k, a.threshold, a.json))
         elif a.command == "validate":
             try:
                 ok = flo_info(open(a.input, "rb").read())["crc_valid"]

@@ -375,6 +375,41 @@ int flo_batch_analysis_metadata_all(flo_batch *b, uint32_t peaks_per_second, uin
 /* the bit depth a lossless batch's files declare (16 unless set; flo_encode_lossless's argument) */
 int flo_batch_set_bit_depth(flo_batch *b, uint8_t bit_depth);
 
+/* ---- spectral similarity: spectral_similarity (core/analysis.rs:395-437, exported as spectral_similarity_score,
+ * lib.rs:1357) over fingerprint sets ----------------------------------------------------------------------------------
+ * flo_fingerprint is SpectralFingerprint (analysis.rs:10-26): what flo_analyze / flo_batch_analyze_all return in those
+ * fields, or the `spectrum_fingerprint` of a file's META. The score of two fingerprints is the reference's, bit for bit in
+ * f32: 1.0 for equal hashes (tested first), else 0.0 for a different sample rate or channel count, else
+ * fl(fl(fl(e * 0.5) + fl(p * 0.3)) + fl(l * 0.2)) with e, p the sequential sums over the 16 energy and 8 peak bytes of
+ * 1 - |a - b| / 255, divided by 16 and 8, and l that term of the loudness bytes. Symmetric bit for bit.
+ * flo_spectral_similarity scores one pair on the host (no context needed).
+ * flo_fpindex_create copies n fingerprints to the device once (fps may be freed afterwards; n = 0 is a valid, empty index);
+ * the queries below run on the device, on the context's stream, and return when their results are in the caller's arrays.
+ * Ranking: score descending, then member index ascending; the result does not depend on how the work is split.
+ *   flo_fpindex_topk:      for each of n_q queries, the k best members: idx / score [n_q][k]. k in 0 .. 64 (FLO_ERR_ARG
+ *                          above); n_q = 0 or k = 0 do nothing. Members of another format are candidates at 0.0.
+ *   flo_fpindex_topk_self: the same for every member against the others: idx / score [n][k]; a member is never its own
+ *                          neighbour (other members with its hash are, at 1.0).
+ *   Slots beyond the candidates there are hold UINT32_MAX and -1.0f.
+ *   flo_fpindex_pairs:     every pair i < j with score >= threshold as (i[p], j[p], score[p]), ordered by (i, j).
+ *                          *n_pairs is always the exact count; when it exceeds cap, nothing is written and the call
+ *                          returns FLO_ERR_NOMEM (call again with cap = *n_pairs). A NaN threshold is FLO_ERR_ARG. */
+typedef struct flo_fingerprint {   /* SpectralFingerprint, analysis.rs:10-26 */
+    uint8_t hash[32];
+    uint32_t duration_ms, sample_rate;
+    uint8_t channels, avg_loudness, pad0, pad1;
+    uint8_t frequency_peaks[8];
+    uint8_t energy_profile[16];
+} flo_fingerprint;
+float flo_spectral_similarity(const flo_fingerprint *a, const flo_fingerprint *b);
+typedef struct flo_fpindex flo_fpindex;
+int flo_fpindex_create(flo_ctx *ctx, const flo_fingerprint *fps, size_t n, flo_fpindex **out);
+void flo_fpindex_destroy(flo_fpindex *ix);
+int flo_fpindex_topk(flo_fpindex *ix, const flo_fingerprint *q, size_t n_q, uint32_t k, uint32_t *idx, float *score);
+int flo_fpindex_topk_self(flo_fpindex *ix, uint32_t k, uint32_t *idx, float *score);
+int flo_fpindex_pairs(flo_fpindex *ix, float threshold, uint64_t cap, uint32_t *i, uint32_t *j, float *score,
+                      uint64_t *n_pairs);
+
 /* ---- streaming encoder: StreamingEncoder of libflo/src/streaming/encoder.rs:6-257 -----------------------------
  * Samples are pushed (interleaved f32); every complete one-second frame is encoded losslessly - all frames a push
  * completes in ONE device batch - and queued; frames are pulled one by one, or assembled into a complete .flo file.
