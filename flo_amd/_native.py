@@ -38,7 +38,7 @@ EXPORTS = [
     "flo_sdec_info", "flo_sdec_frames_available", "flo_sdec_available_frames", "flo_sdec_current_frame_index",
     "flo_sdec_buffered_bytes", "flo_sdec_next_frame", "flo_sdec_decode_available", "flo_sdec_reset", "flo_sdec_decode_ready",
     "flo_spectral_similarity", "flo_fpindex_create", "flo_fpindex_destroy", "flo_fpindex_topk", "flo_fpindex_topk_self",
-    "flo_fpindex_pairs",
+    "flo_fpindex_pairs", "flo_batch_fidelity", "flo_compare",
 ]
 
 
@@ -77,6 +77,18 @@ class Fingerprint(C.Structure):   # flo_fingerprint (SpectralFingerprint, core/a
     _fields_ = [("hash", C.c_uint8 * 32), ("duration_ms", C.c_uint32), ("sample_rate", C.c_uint32), ("channels", C.c_uint8),
                 ("avg_loudness", C.c_uint8), ("pad0", C.c_uint8), ("pad1", C.c_uint8), ("frequency_peaks", C.c_uint8 * 8),
                 ("energy_profile", C.c_uint8 * 16)]
+
+
+class FidelityBlock(C.Structure):   # flo_fidelity_block
+    _fields_ = [("signal", C.c_double), ("error", C.c_double), ("peak_error", C.c_float), ("peak_out", C.c_float),
+                ("clipped", C.c_uint32), ("n", C.c_uint32)]
+
+
+class Fidelity(C.Structure):   # flo_fidelity: one channel of one clip
+    _fields_ = [("signal", C.c_double), ("error", C.c_double), ("tail_energy", C.c_double), ("snr_db", C.c_double),
+                ("seg_snr_db", C.c_double), ("peak_error", C.c_float), ("peak_out", C.c_float), ("clipped", C.c_uint64),
+                ("compared_frames", C.c_uint64), ("source_frames", C.c_uint64), ("decoded_frames", C.c_uint64),
+                ("n_blocks", C.c_uint32), ("seg_blocks", C.c_uint32)]
 
 
 class FloError(RuntimeError):
@@ -218,5 +230,7 @@ def lib():
     L.flo_fpindex_topk.argtypes = [vp, vp, sz, C.c_uint32, vp, vp]
     L.flo_fpindex_topk_self.argtypes = [vp, C.c_uint32, vp, vp]
     L.flo_fpindex_pairs.argtypes = [vp, C.c_float, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]
+    L.flo_batch_fidelity.argtypes = [vp, vp, vp, sz, vp]
+    L.flo_compare.argtypes = [vp, vp, sz, C.c_char_p, sz, vp, vp, sz, C.POINTER(sz)]
     _LIB = L
     return L

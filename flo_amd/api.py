@@ -211,6 +211,20 @@ class Context:
         self._L.flo_free(out)
         return a
 
+    def compare(self, samples, flo: bytes, blocks=False):
+        """How far a .flo file's decoded audio lies from `samples` (its source, interleaved f32 with the file's channel
+        count), measured on the device (flo_compare, include/flo_hip.h): a dict as fidelity_dict returns it."""
+        p = _f32(samples)
+        flo = bytes(flo)
+        ch = max(int(probe_container(flo).channels), 1)
+        out = np.zeros(ch, FIDELITY_DTYPE)
+        cap = ((p.size // ch + 1023) // 1024) * ch   # n_blocks <= ceil(source frames / 1024)
+        blk = np.zeros(max(cap, 1), FIDELITY_BLOCK_DTYPE) if blocks else None
+        nb = C.c_size_t()
+        self._chk(self._L.flo_compare(self._h, p.ctypes.data, p.size, flo, len(flo), out.ctypes.data,
+                                      blk.ctypes.data if blocks else None, cap if blocks else 0, C.byref(nb)))
+        return fidelity_dict(out, blk[:nb.value * ch].reshape(-1, ch) if blocks else None)
+
     def get_toc(self, flo: bytes):
         return get_toc(flo)
 
@@ -312,6 +326,7 @@ class Batch:
 
     def __init__(self, ctx: Context, mode, n_interleaved, sample_rate, channels, quality_or_level):
         self.ctx, self._L = ctx, ctx._L
+        self.channels = int(channels)
         self.n_clips = len(n_interleaved)
         self.n_interleaved = list(int(x) for x in n_interleaved)
         lens = (C.c_size_t * self.n_clips)(*self.n_interleaved)
@@ -415,6 +430,21 @@ class Batch:
         offs = (C.c_uint64 * max(self.n_clips, 1))()
         self.ctx._chk(self._L.flo_batch_decode(self._h, dst_ptr, dst_cap_floats, offs))
         return list(offs[: self.n_clips])
+
+    def fidelity(self, blocks=False):
+        """How far each clip's decoded audio lies from its source (flo_batch_fidelity, include/flo_hip.h), measured on the
+        device after encode + sync: one dict per clip (see fidelity_dict); blocks=True adds the block records."""
+        ch = self.channels
+        off = np.zeros(self.n_clips + 1, np.uint64)
+        self.ctx._chk(self._L.flo_batch_fidelity(self._h, None, None, 0, off.ctypes.data))
+        out = np.zeros(max(self.n_clips * ch, 1), FIDELITY_DTYPE)
+        nrec = int(off[-1]) * ch
+        blk = np.zeros(max(nrec, 1), FIDELITY_BLOCK_DTYPE) if blocks else None
+        self.ctx._chk(self._L.flo_batch_fidelity(self._h, out.ctypes.data, blk.ctypes.data if blocks else None,
+                                                 nrec if blocks else 0, off.ctypes.data))
+        return [fidelity_dict(out[i * ch:(i + 1) * ch],
+                              blk[int(off[i]) * ch:int(off[i + 1]) * ch].reshape(-1, ch) if blocks else None)
+                for i in range(self.n_clips)]
 
     def device_streams(self):
         base = C.c_void_p()
@@ -663,6 +693,49 @@ def seek_to_time(data: bytes, target_ms: int):
 def decode_frame_at(data: bytes, frame_index: int):
     """seeking::decode_frame_at (seeking.rs:43-63)"""
     return default_context().decode_frame_at(data, frame_index)
+
+
+# -- fidelity reports (flo_batch_fidelity, flo_compare; definitions in include/flo_hip.h) ---------------------------------
+FIDELITY_DTYPE = np.dtype([("signal", "<f8"), ("error", "<f8"), ("tail_energy", "<f8"), ("snr_db", "<f8"), ("seg_snr_db", "<f8"),
+                           ("peak_error", "<f4"), ("peak_out", "<f4"), ("clipped", "<u8"), ("compared_frames", "<u8"),
+                           ("source_frames", "<u8"), ("decoded_frames", "<u8"), ("n_blocks", "<u4"), ("seg_blocks", "<u4")])
+FIDELITY_BLOCK_DTYPE = np.dtype([("signal", "<f8"), ("error", "<f8"), ("peak_error", "<f4"), ("peak_out", "<f4"),
+                                 ("clipped", "<u4"), ("n", "<u4")])
+assert FIDELITY_DTYPE.itemsize == C.sizeof(_native.Fidelity)
+assert FIDELITY_BLOCK_DTYPE.itemsize == C.sizeof(_native.FidelityBlock)
+
+
+def snr_db(signal: float, error: float) -> float:
+    """10 log10(signal / error): +inf when error = 0, -inf when signal = 0 < error"""
+    if error == 0.0:
+        return float("inf")
+    if signal == 0.0:
+        return float("-inf")
+    return 10.0 * float(np.log10(signal / error))
+
+
+def fidelity_dict(rec, blocks=None) -> dict:
+    """One clip's report from its FIDELITY_DTYPE records [channels]: per-channel arrays signal, error, tail_energy, snr_db,
+    seg_snr_db, peak_error, peak_out, clipped, seg_blocks; the counts compared_frames, source_frames, decoded_frames,
+    n_blocks; snr_db_all over all channels (the channels' sums added in channel order); `blocks`: the FIDELITY_BLOCK_DTYPE
+    records [n_blocks, channels] when asked for."""
+    d = {k: rec[k].copy() for k in ("signal", "error", "tail_energy", "snr_db", "seg_snr_db", "peak_error", "peak_out",
+                                      "clipped", "seg_blocks")}
+    for k in ("compared_frames", "source_frames", "decoded_frames", "n_blocks"):
+        d[k] = int(rec[k][0]) if rec.size else 0
+    s = e = 0.0
+    for c in range(rec.size):   # (sequential: Python's sum() of floats is compensated)
+        s += float(rec["signal"][c])
+        e += float(rec["error"][c])
+    d["snr_db_all"] = snr_db(s, e)
+    if blocks is not None:
+        d["blocks"] = np.ascontiguousarray(blocks)
+    return d
+
+
+def compare(samples, flo: bytes, blocks=False) -> dict:
+    """Context.compare on the default context: how far a .flo file's decoded audio lies from its source"""
+    return default_context().compare(samples, flo, blocks)
 
 
 class Corpus:

@@ -10,6 +10,7 @@ printed fields for the parts that sit on this repository's path -
     metadata <in.flo> [--json]
     analysis <in.flo> [--waveform] [--spectrum] [--json]
     similar  <in.flo>... [-k N | --threshold T] [--json]
+    compare  <source.wav> <in.flo> [--json] [--blocks]
 Ingestion is WAV only (flo_amd/wav.py; the reference demuxes MP3/FLAC/OGG/AAC through symphonia, reflo/src/audio.rs:57-166).
 `encode` writes the META chunk the reference CLI writes for an untagged file (reflo/src/lib.rs:202-283, flo_amd/meta.py):
 length_ms, encoding_time, encoder_settings, flo_encoder_version, source_format (+ --title / --artist / --album) - the
@@ -19,6 +20,9 @@ computes on the device: EBU R128 loudness, range, true peak and sample peak (cor
 waveform peaks at 60 per second and the spectral fingerprint (core/analysis.rs).
 `similar` (not in reflo) compares the spectrum fingerprints the files' META carry under spectral_similarity
 (core/analysis.rs:395-437) on the device: each file's k nearest other files, or every pair at or above a threshold.
+`compare` (not in reflo; the reference's TODO lists it as "compare original vs encoded") measures on the device how far
+the file's decoded audio lies from the source WAV: SNR, segmental SNR, peak error, clipped samples and the energy of the
+decoded tail past the source's end, per channel (flo_compare, include/flo_hip.h).
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
 """
@@ -150,6 +154,40 @@ def similar_report(paths, k=None, threshold=None, as_json=False, ctx=None) -> st
         ix.close()
 
 
+def _num(v: float):
+    """a float for JSON: non-finite values as the strings "inf", "-inf", "nan" (float() reads them back)"""
+    v = float(v)
+    return v if v == v and v not in (float("inf"), float("-inf")) else str(v)
+
+
+def _dbfs(v: float) -> float:
+    import math
+    return 20.0 * math.log10(v) if v > 0 else float("-inf")
+
+
+def compare_report(audio_bytes: bytes, flo_bytes: bytes, blocks=False, ctx=None) -> dict:
+    """The `compare` command's report: the WAV source against the file's decoded audio (Context.compare), per channel.
+    A WAV whose sample rate or channel count differs from the file's header is refused (ValueError)."""
+    samples, sr, ch = read_wav_bytes(audio_bytes)
+    info = api.probe_container(flo_bytes)
+    if sr != info.sample_rate or ch != info.channels:
+        raise ValueError(f"the WAV is {sr} Hz / {ch} channels, the file {info.sample_rate} Hz / {info.channels} channels")
+    c = ctx or api.default_context()
+    r = c.compare(samples, flo_bytes, blocks)
+    rep = {"sample_rate": sr, "channels": ch, "compared_frames": r["compared_frames"], "decoded_frames": r["decoded_frames"],
+           "source_frames": r["source_frames"], "snr_db": _num(r["snr_db_all"]),
+           "per_channel": [{"channel": k, "snr_db": _num(r["snr_db"][k]), "seg_snr_db": _num(r["seg_snr_db"][k]),
+                            "seg_blocks": int(r["seg_blocks"][k]), "peak_error_dbfs": _num(_dbfs(float(r["peak_error"][k]))),
+                            "peak_error": _num(r["peak_error"][k]), "clipped": int(r["clipped"][k]),
+                            "tail_energy": _num(r["tail_energy"][k]), "signal": _num(r["signal"][k]), "error": _num(r["error"][k])}
+                           for k in range(ch)]}
+    if blocks:
+        b = r["blocks"]
+        rep["block_snr_db"] = [[_num(api.snr_db(float(b[i, k]["signal"]), float(b[i, k]["error"]))) for k in range(ch)]
+                               for i in range(b.shape[0])]
+    return rep
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="flo", description="flo audio format converter (MI355X-native encode / decode)")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -185,6 +223,11 @@ def main(argv=None) -> int:
     sg.add_argument("-k", type=int, default=None, help="Nearest neighbours per file (default 5, at most 64)")
     sg.add_argument("--threshold", type=float, default=None, help="List every pair scoring at least this")
     si.add_argument("--json", action="store_true", help="Output as JSON")
+    cp = sub.add_parser("compare", help="Compare a flo file's decoded audio with its source WAV")
+    cp.add_argument("source")
+    cp.add_argument("input")
+    cp.add_argument("--json", action="store_true", help="Output as JSON")
+    cp.add_argument("--blocks", action="store_true", help="Also print the SNR of every 1024-frame block")
     a = ap.parse_args(argv)
     try:
         if a.command == "encode":
@@ -306,6 +349,24 @@ def main(argv=None) -> int:
                     print()
         elif a.command == "similar":
             print(similar_report(a.inputs, a.k, a.threshold, a.json))
+        elif a.command == "compare":
+            rep = compare_report(open(a.source, "rb").read(), open(a.input, "rb").read(), a.blocks)
+            if a.json:
+                print(json.dumps(rep, indent=2))
+            else:
+                print(f"Comparing {a.input} with {a.source}")
+                print(f"  Sample rate: {rep['sample_rate']} Hz, channels: {rep['channels']}")
+                print(f"  Frames: {rep['compared_frames']} compared, {rep['decoded_frames']} decoded, "
+                      f"{rep['source_frames']} in the source")
+                print(f"  SNR (all channels): {float(rep['snr_db']):.4f} dB")
+                for p in rep["per_channel"]:
+                    print(f"  Channel {p['channel']}: SNR {float(p['snr_db']):.4f} dB, segmental SNR {float(p['seg_snr_db']):.4f} dB "
+                          f"({p['seg_blocks']} blocks), peak error {float(p['peak_error_dbfs']):.4f} dBFS, "
+                          f"clipped {p['clipped']}, tail energy {float(p['tail_energy']):.6e}")
+                if a.blocks:
+                    print("  Block SNR (dB), one column per channel:")
+                    for i, row in enumerate(rep["block_snr_db"]):
+                        print(f"    {i:6d}  " + "  ".join(f"{float(v):9.4f}" for v in row))
         elif a.command == "validate":
             try:
                 ok = flo_info(open(a.input, "rb").read())["crc_valid"]

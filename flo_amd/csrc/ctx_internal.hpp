@@ -9,6 +9,7 @@
 
 #include "../../include/flo_hip.h"
 #include "analysis_kernels.hpp"
+#include "fidelity_kernels.hpp"
 #include "lossy_device.hpp"
 #include "stager.hpp"
 #include "tables.hpp"
@@ -63,6 +64,27 @@ int profile_drain(flo_ctx *c, bool wait);
 int get_tables(flo_ctx *c, uint32_t sr, float quality, TableSet **out);
 // the context's pinned staging ring and copy threads (made on first use)
 int ctx_stager(flo_ctx *c);
+
+// ---- fidelity reports (fidelity.cpp): what flo_api.cpp, which owns batches and the file decode paths, lends them --------
+// A synced batch as the comparison sees it: clip i's source is the batch's device copy, src_frames[i] whole frames at
+// pcm + src_off[i]; dec_frames[i] is what its file decodes to. FLO_ERR_STATE before sync.
+struct FidBatchView {
+    flo_ctx *ctx = nullptr;
+    bool lossy = false;
+    int channels = 0;
+    const float *pcm = nullptr;
+    std::vector<unsigned long long> src_off, src_frames, dec_frames;
+};
+int batch_fidelity_view(flo_batch *b, FidBatchView &v);
+// the fused pass over a synced lossy batch: lossy_decode_kernel<kDecCompare>, clip i against cmp's clip i (stream idle on return)
+int batch_lossy_compare(flo_batch *b, const LossyCmpArgs &cmp);
+// a parsed file whose bytes are at d_bytes: the fused pass of a transform file (one clip), the decode of a lossless one
+// into d_out (its frames' samples x channels floats); both leave the stream idle
+namespace flo {
+struct ParsedFile;
+}
+int file_lossy_compare(flo_ctx *c, const ParsedFile &f, const uint8_t *d_bytes, const LossyCmpArgs &cmp);
+int file_lossless_decode(flo_ctx *c, const ParsedFile &f, const uint8_t *d_bytes, float *d_out);
 
 // Launch through `launch` on the ctx stream; with profiling on, bracketed by events under `name`.
 template <typename F>

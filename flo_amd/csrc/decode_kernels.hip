@@ -47,9 +47,11 @@ constexpr int kBlobStage = 2304;
 // is one run of blocks of one window, the run is trimmed to the window's blocks and its stores to the window's samples.
 // kDecStream: streaming decoders (launch_lossy_stream): the unit of work is one run of one stream's frames in the call's
 // frame list; the overlap comes from the stream's device state and goes back to it (LossyRunDev::flags).
+// kDecCompare: the work of kDecWhole, but every block is compared with the clip's source (LossyDecArgs::cmp) instead of
+// stored: the source loads take the place of the stores, the block's record (fidelity_kernels.hpp) is what is written.
 template <int MODE>
 __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
-    constexpr bool WIN = MODE == kDecWindow, STRM = MODE == kDecStream;
+    constexpr bool WIN = MODE == kDecWindow, STRM = MODE == kDecStream, CMP = MODE == kDecCompare;
     const LossyWinArgs &W = D.win;
     // One 8 KiB buffer serves three phases of a channel-frame in turn: the parse table of the record headers, then the
     // integers + the FFT exchange buffer, then the windowed output. Everything that does not change from frame to frame
@@ -88,7 +90,9 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     unsigned long long wfirst = 0, wend = 0, frame0 = 0;   // (WIN) the window's samples [wfirst, wend), its file's first frame
     float *st = nullptr;    // (STRM) the stream's overlap state
     unsigned sflags = 0;    // (STRM) kRun*
-    if constexpr (MODE == kDecWhole) {
+    const float *csrc = nullptr;                           // (CMP) the clip's source
+    unsigned long long cmp_frames = 0, cmp_blk0 = 0;       // (CMP) its compared frames, its first block record
+    if constexpr (MODE == kDecWhole || CMP) {
     if (P >= (unsigned long long)D.n_clips * D.n_runs) return;
     clip = (unsigned)(P % (unsigned)D.n_clips);   // (clips fastest)
     const unsigned nframes = D.clip_frames[clip];
@@ -96,7 +100,16 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     h0 = (unsigned)(P / (unsigned)D.n_clips) * run;   // first frame of the run = first output block
     if (nframes < 2 || h0 + 1 >= nframes) return;
     h1 = h0 + run < nframes - 1 ? h0 + run : nframes - 1;   // last frame of the run
-    out = D.out + D.clip_out[clip];
+    if constexpr (CMP) {
+        out = nullptr;
+        const FidClipDev cd = D.cmp.clip[clip];
+        const unsigned long long dec_frames = (unsigned long long)(nframes - 1) * 1024ull;
+        csrc = D.cmp.src + cd.src;
+        cmp_frames = cd.src_frames < dec_frames ? cd.src_frames : dec_frames;
+        cmp_blk0 = cd.blk0;
+    } else {
+        out = D.out + D.clip_out[clip];
+    }
     } else if constexpr (MODE == kDecWindow) {
         // window w, run r of its runs (runs fastest): blocks b0 + r run .. of the window's blocks b0 .. b1, which need frames
         // b0 .. b1 + 1 of the file; output past the file's last block is the zero tail, written by window_tail_kernel
@@ -166,7 +179,7 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
         wave_sync();
         if ((unsigned)lane <= h1 - h0) {
             unsigned long long f;
-            if constexpr (MODE != kDecWhole) f = frame0 + h0 + (unsigned)lane;
+            if constexpr (WIN || STRM) f = frame0 + h0 + (unsigned)lane;
             else f = D.clip_frame0[clip] + h0 + (unsigned)lane;
             const unsigned long long foff = D.blob_off[f];
             const uint32_t flen = D.blob_len[f];
@@ -233,6 +246,23 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
         // (the lane index behind an optimisation barrier: inside the frame loop every lane-derived address is recomputed - a
         // few integer operations - instead of being hoisted into dozens of loop-invariant registers)
         const int ln = lane_id_opaque();
+        // (CMP) block h - 1's source samples at the positions the lane compares, loaded now: the frame's decode hides
+        // their latency (the same strided pattern as the stores of kDecWhole, paired channels on one XCD alike)
+        [[maybe_unused]] float xs[16];
+        [[maybe_unused]] uint32_t in_end = 0;   // compared positions of the block: [0, in_end); the decoded rest is its tail
+        if constexpr (CMP) {
+            if (h > h0) {
+                const unsigned long long f0 = (unsigned long long)(h - 1) * 1024ull;
+                in_end = cmp_frames > f0 ? (cmp_frames - f0 < 1024ull ? (uint32_t)(cmp_frames - f0) : 1024u) : 0u;
+                const float *sb = csrc + f0 * D.channels + c;
+                const uint32_t nchu = (uint32_t)D.channels;
+#pragma unroll
+                for (int k = 0; k < 16; k++) {
+                    const uint32_t j = (uint32_t)ln + 64u * (uint32_t)k;
+                    xs[k] = j < in_end ? sb[j * nchu] : 0.0f;
+                }
+            }
+        }
         {
             DSTAMP(1);
             if (present) {
@@ -512,7 +542,18 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
             // overlap-add (mdct.rs:449-456): block h - 1 = first half of this frame + second half of the previous one
             // (carried in registers). A channel the frame does not carry gives a silent block and leaves the overlap
             // alone (the reference would fail on such a frame; the oracle behaves like this).
-            if constexpr (!WIN) {
+            if constexpr (CMP) {
+                if (h > h0) {   // block h - 1: compared with the source, its record written (no PCM)
+                    FidAcc acc = fid_acc_zero();
+#pragma unroll
+                    for (int k = 0; k < 16; k++) {
+                        const uint32_t j = (uint32_t)ln + 64u * (uint32_t)k;
+                        const float a = present ? recon[j] + pv[k] : 0.0f;
+                        fid_acc_add(acc, xs[k], a, j < in_end, j >= in_end);
+                    }
+                    fid_block_store(acc, in_end, D.cmp.blk + (cmp_blk0 + (h - 1)) * (unsigned long long)D.channels + c, ln);
+                }
+            } else if constexpr (!WIN) {
             if (h > h0 || (STRM && (sflags & kRunWriteFirst))) {
                 // (a uniform block base and a 32-bit lane offset: the stores take the scalar-base form, no 64-bit address
                 // arithmetic per store; a stream run's blocks start at its first frame that writes one)
@@ -898,6 +939,20 @@ int launch_lossy_decode(const LossyDecArgs &A0, unsigned max_frames, hipStream_t
         fprintf(stderr, " total=%.0f\n", tot / fc);
     }
 #endif
+    return 0;
+}
+int launch_lossy_compare(const LossyDecArgs &A0, unsigned max_frames, hipStream_t s) {
+    if (max_frames < 2 || !A0.n_clips || A0.channels < 1) return 0;
+    LossyDecArgs A = A0;
+    // the grid of launch_lossy_decode: the same runs, so the same waves touch the same lines of the source
+    const unsigned long long blocks = (unsigned long long)A.n_clips * (max_frames - 1);
+    A.run = blocks >= 8ull * 4096ull ? kDecRunLong : kDecRunShort;
+    const unsigned runs = (max_frames - 1 + (unsigned)A.run - 1) / (unsigned)A.run;
+    A.n_runs = runs;
+    const unsigned long long wgs = ((unsigned long long)A.n_clips * runs + 7ull) / 8ull * 8ull * (unsigned)A.channels;
+    if (wgs > 0x7FFFFFFFull) return -1;
+    hipLaunchKernelGGL(lossy_decode_kernel<kDecCompare>, dim3((unsigned)wgs), dim3(64), 0, s, A);
+    FLO_LAUNCH_CHECK();
     return 0;
 }
 int launch_lossy_window(const LossyDecArgs &A0, const LossyWinArgs &W, unsigned run, hipStream_t s) {

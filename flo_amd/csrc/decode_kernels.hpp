@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fidelity_kernels.hpp"
 #include "lossy_device.hpp"
 
 namespace flo {
@@ -41,7 +42,9 @@ struct LossyStreamArgs {
     unsigned int n_runs;
     unsigned int pad;
 };
-enum DecMode : int { kDecWhole = 0, kDecWindow = 1, kDecStream = 2 };
+// kDecCompare: whole clips as kDecWhole, every block compared with the clip's source instead of stored (fidelity reports:
+// LossyDecArgs::cmp, fidelity_kernels.hpp)
+enum DecMode : int { kDecWhole = 0, kDecWindow = 1, kDecStream = 2, kDecCompare = 3 };
 
 // One transform frame = one wavefront. Frames of a clip are addressed by (clip, local frame index).
 struct LossyDecArgs {
@@ -62,6 +65,7 @@ struct LossyDecArgs {
     unsigned long long *dbg;          // FLO_DEC_STAMPS builds only: phase tick sums (set by the launcher)
     LossyWinArgs win;                 // corpus windows only (set by launch_lossy_window)
     LossyStreamArgs strm;             // streaming decoders only (set by launch_lossy_stream)
+    LossyCmpArgs cmp;                 // fidelity reports only (launch_lossy_compare); `out` is not written then
 };
 
 // One ALPC / raw / silent channel wrapper of one frame = one thread.
@@ -152,5 +156,7 @@ int launch_ll_window_finish(const LlWinFinishArgs &A, unsigned max_count, hipStr
 // streaming decoders: one wavefront per run and channel
 int launch_lossy_stream(const LossyDecArgs &A, const LossyStreamArgs &S, hipStream_t s);
 int launch_window_tail(const WinTailDev *tails, unsigned n, float *out, hipStream_t s);
+// fidelity reports: the grid of launch_lossy_decode, every block compared with A.cmp's sources instead of stored
+int launch_lossy_compare(const LossyDecArgs &A, unsigned max_frames, hipStream_t s);
 
 }  // namespace flo

@@ -1498,11 +1498,12 @@ static int ll_decode_device(flo_ctx *c, const LlWrapperList &w, uint64_t out_sf,
 
 // lossy_decode_kernel<kDecWhole> over the clips whose bytes sit at `bytes`: the frame and clip tables and a cleared
 // error word go up, the kernel runs, the error word comes back (the ctx stream is idle on return). FLO_ERR_FORMAT when a
-// frame does not deserialise.
+// frame does not deserialise. With `cmp` (fidelity reports), lossy_decode_kernel<kDecCompare>: clip i is compared with
+// cmp's clip i and nothing is written to `out`.
 static int lossy_decode_whole(flo_ctx *c, const TableSet *ts, const uint8_t *bytes, int channels, const std::vector<unsigned long long> &blob_off,
                               const std::vector<unsigned int> &blob_len, const std::vector<unsigned long long> &clip_frame0,
                               const std::vector<unsigned int> &clip_frames, const std::vector<unsigned long long> &clip_out,
-                              unsigned max_frames, float *out) {
+                              unsigned max_frames, float *out, const LossyCmpArgs *cmp = nullptr) {
     DevMem d_off, d_len, d_c0, d_cn, d_co, d_err;
     QuiesceOnExit quiesce_d_off(c);
     const std::vector<int> zero{0};
@@ -1523,7 +1524,12 @@ static int lossy_decode_whole(flo_ctx *c, const TableSet *ts, const uint8_t *byt
     A.channels = channels;
     A.out = out;
     A.error = d_err.as<int>();
-    if ((rc = timed_launch(c, "lossy_decode", [&] { return launch_lossy_decode(A, max_frames, c->stream); })) != FLO_OK) return rc;
+    if (cmp) {
+        A.cmp = *cmp;
+        if ((rc = timed_launch(c, "fidelity", [&] { return launch_lossy_compare(A, max_frames, c->stream); })) != FLO_OK) return rc;
+    } else if ((rc = timed_launch(c, "lossy_decode", [&] { return launch_lossy_decode(A, max_frames, c->stream); })) != FLO_OK) {
+        return rc;
+    }
     int herr = 0;
     HIPCHK(c, hipMemcpyAsync(&herr, d_err.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1638,6 +1644,35 @@ static int decode_impl(flo_ctx *c, const uint8_t *flo, size_t len, float **pcm, 
     return FLO_OK;
 }
 
+// ---- fidelity reports (fidelity.cpp): decode_impl's two device paths, for a file already parsed and uploaded ----------
+int file_lossy_compare(flo_ctx *c, const ParsedFile &f, const uint8_t *d_bytes, const LossyCmpArgs &cmp) {
+    std::vector<unsigned long long> blob_off;
+    std::vector<unsigned int> blob_len;
+    for (const FrameDesc &fr : f.frames) {
+        if (!fr.n_channels) continue;
+        const ChannelDesc &cd = f.channels_desc[fr.first_channel];
+        blob_off.push_back(cd.off);
+        blob_len.push_back(cd.len);
+    }
+    const size_t nf = blob_off.size();
+    if (!nf) return FLO_OK;
+    if (f.channels == 0) return fail(c, FLO_ERR_FORMAT, "Failed to deserialize transform frame");
+    TableSet *ts;
+    int rc = get_tables(c, f.sample_rate, 0.5f, &ts);
+    if (rc != FLO_OK) return rc;
+    return lossy_decode_whole(c, ts, d_bytes, f.channels, blob_off, blob_len, {0}, {(unsigned int)nf}, {0}, (unsigned)nf, nullptr, &cmp);
+}
+int file_lossless_decode(flo_ctx *c, const ParsedFile &f, const uint8_t *d_bytes, float *d_out) {
+    LlWrapperList w;
+    uint64_t out_sf = 0;
+    const bool force_serial = ll_force_serial();
+    for (const FrameDesc &fr : f.frames) {
+        add_parsed_frame(w, f, fr, out_sf, force_serial);
+        out_sf += fr.samples;
+    }
+    return ll_decode_device(c, w, out_sf, d_bytes, f.channels, d_out, nullptr);
+}
+
 // Lossless batches: the finished files stay where the encoder left them in HBM, and what a reader would find in them
 // is known from the encoder's own frame and channel records (lossless_describe): nothing is read back or parsed, every
 // wrapper of every clip is decoded in one set of launches.
@@ -1692,22 +1727,24 @@ static int batch_decode_lossless(flo_batch *b, float *dst, size_t dst_cap, uint6
     return rc;
 }
 
-// Decode every clip of an encoded batch from its device bitstreams (no host round trip of the payload).
-extern "C" int flo_batch_decode(flo_batch *b, float *dst, size_t dst_cap, uint64_t *offsets) {
-    if (!b || !offsets || (!dst && dst_cap)) return FLO_ERR_ARG;
+// The frame and clip tables of a synced lossy batch's decode, read from the encoder's own records: clip i's PCM at
+// co[i] floats, `total` floats in all (flo_batch_decode, and the fidelity reports' fused pass).
+static int batch_lossy_tables(flo_batch *b, std::vector<unsigned long long> &blob_off, std::vector<unsigned int> &blob_len,
+                              std::vector<unsigned long long> &c0, std::vector<unsigned int> &cn, std::vector<unsigned long long> &co,
+                              uint64_t &total, unsigned &max_hops) {
     flo_ctx *c = b->ctx;
-    if (!b->synced) return fail(c, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (b->mode != FLO_MODE_LOSSY) return batch_decode_lossless(b, dst, dst_cap, offsets);
     if (b->h_frame_size.size() != b->total_frames) {
         b->h_frame_size.assign(b->total_frames, 0);
         if (b->total_frames)
             HIPCHK(c, hipMemcpy(b->h_frame_size.data(), b->d_frame_size, b->total_frames * 4, hipMemcpyDeviceToHost));
     }
-    std::vector<unsigned long long> blob_off(b->total_frames), c0(b->n_clips), co(b->n_clips);
-    std::vector<unsigned int> blob_len(b->total_frames), cn(b->n_clips);
-    uint64_t total = 0;
-    unsigned max_hops = 0;
+    blob_off.assign(b->total_frames, 0);
+    blob_len.assign(b->total_frames, 0);
+    c0.assign(b->n_clips, 0);
+    cn.assign(b->n_clips, 0);
+    co.assign(b->n_clips, 0);
+    total = 0;
+    max_hops = 0;
     for (size_t i = 0; i < b->n_clips; i++) {
         uint64_t off = b->out_off[i];
         for (uint32_t h = 0; h < b->hops[i]; h++) {
@@ -1720,14 +1757,67 @@ extern "C" int flo_batch_decode(flo_batch *b, float *dst, size_t dst_cap, uint64
         c0[i] = b->clip_frame0[i];
         cn[i] = b->hops[i];
         co[i] = total;
-        offsets[i] = total;
         total += b->hops[i] > 1 ? (uint64_t)(b->hops[i] - 1) * 1024 * b->ch : 0;
         if (b->hops[i] > max_hops) max_hops = b->hops[i];
     }
+    return FLO_OK;
+}
+
+// Decode every clip of an encoded batch from its device bitstreams (no host round trip of the payload).
+extern "C" int flo_batch_decode(flo_batch *b, float *dst, size_t dst_cap, uint64_t *offsets) {
+    if (!b || !offsets || (!dst && dst_cap)) return FLO_ERR_ARG;
+    flo_ctx *c = b->ctx;
+    if (!b->synced) return fail(c, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (b->mode != FLO_MODE_LOSSY) return batch_decode_lossless(b, dst, dst_cap, offsets);
+    std::vector<unsigned long long> blob_off, c0, co;
+    std::vector<unsigned int> blob_len, cn;
+    uint64_t total = 0;
+    unsigned max_hops = 0;
+    const int rc = batch_lossy_tables(b, blob_off, blob_len, c0, cn, co, total, max_hops);
+    if (rc != FLO_OK) return rc;
+    for (size_t i = 0; i < b->n_clips; i++) offsets[i] = co[i];
     if (total > dst_cap) return fail(c, FLO_ERR_ARG, "destination too small for the decoded batch");
     if (!total) return FLO_OK;
     // (dst needs no clearing: the decode kernel writes every sample of every output block exactly once)
     return lossy_decode_whole(c, b->ts, b->d_out, b->ch, blob_off, blob_len, c0, cn, co, max_hops, dst);
+}
+
+// ---- fidelity reports (fidelity.cpp): a synced batch as the comparison sees it, and its fused lossy pass -------------
+int batch_fidelity_view(flo_batch *b, FidBatchView &v) {
+    if (!b) return FLO_ERR_ARG;
+    flo_ctx *c = b->ctx;
+    if (!b->synced) return fail(c, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
+    v.ctx = c;
+    v.lossy = b->mode == FLO_MODE_LOSSY;
+    v.channels = b->ch;
+    v.pcm = b->d_pcm;
+    v.src_off.assign(b->clip_off.begin(), b->clip_off.end());
+    v.src_frames.assign(b->clip_nsf.begin(), b->clip_nsf.end());
+    v.dec_frames.assign(b->n_clips, 0);
+    if (v.lossy) {
+        for (size_t i = 0; i < b->n_clips; i++) v.dec_frames[i] = b->hops[i] > 1 ? (uint64_t)(b->hops[i] - 1) * 1024 : 0;
+        return FLO_OK;
+    }
+    std::vector<LosslessFrameInfo> fr;
+    std::vector<LosslessWrapperInfo> wr;
+    const uint8_t *base = nullptr;
+    std::string err;
+    if (lossless_describe(b->ll, fr, wr, &base, err) != 0) return fail(c, FLO_ERR_STATE, err);
+    for (const LosslessFrameInfo &f : fr)
+        if (f.clip < b->n_clips) v.dec_frames[f.clip] += f.samples;
+    return FLO_OK;
+}
+int batch_lossy_compare(flo_batch *b, const LossyCmpArgs &cmp) {
+    flo_ctx *c = b->ctx;
+    std::vector<unsigned long long> blob_off, c0, co;
+    std::vector<unsigned int> blob_len, cn;
+    uint64_t total = 0;
+    unsigned max_hops = 0;
+    const int rc = batch_lossy_tables(b, blob_off, blob_len, c0, cn, co, total, max_hops);
+    if (rc != FLO_OK) return rc;
+    if (!total) return FLO_OK;
+    return lossy_decode_whole(c, b->ts, b->d_out, b->ch, blob_off, blob_len, c0, cn, co, max_hops, nullptr, &cmp);
 }
 
 extern "C" int flo_decode(flo_ctx *c, const uint8_t *flo, size_t len, float **pcm, size_t *n_interleaved,

@@ -13,6 +13,8 @@
  *                            libflo/src/lib.rs:296-352, lossless/decoder.rs:14-72, lossy/decoder.rs:29-188
  *   flo_free              <- drop of the returned Vec<u8> / Vec<f32>
  *   error codes + flo_last_error <- FloResult<T> = Result<T, String>   (core/types.rs:281)
+ *   flo_batch_fidelity / flo_compare <- no counterpart: the "compare original vs encoded" of the reference's TODO,
+ *                            decoded audio against its source measured on the device (fidelity reports, below)
  *
  * Conventions mirror the reference: inputs are interleaved f32 PCM in [-1,1], length
  * n_interleaved = sample_frames * channels (a trailing partial sample-frame is ignored, as the reference's
@@ -409,6 +411,51 @@ int flo_fpindex_topk(flo_fpindex *ix, const flo_fingerprint *q, size_t n_q, uint
 int flo_fpindex_topk_self(flo_fpindex *ix, uint32_t k, uint32_t *idx, float *score);
 int flo_fpindex_pairs(flo_fpindex *ix, float threshold, uint64_t cap, uint32_t *i, uint32_t *j, float *score,
                       uint64_t *n_pairs);
+
+/* ---- fidelity reports: decoded audio against its source, on the device (the "compare original vs encoded" of the
+ * reference's TODO) ------------------------------------------------------------------------------------------------------
+ * x is the source, y what flo_decode returns for the clip's file, both interleaved f32 with `channels` channels. Only whole
+ * sample-frames are compared, decoded frame t against source frame t (the 1024-frame pre-roll is dropped, encoder.rs:176-179,
+ * lib.rs:338-341). compared = min(source_frames, decoded_frames); a lossy clip of n frames decodes to ceil(n / 1024) * 1024
+ * frames, a tail of fewer than 1024 frames past the source's end.
+ * Block b covers frames [1024 b, 1024 (b + 1)) of the compared range: n_blocks = ceil(compared / 1024). Per block and
+ * channel, all arithmetic in f64 without contraction:
+ *   signal = sum x^2, error = sum (y - x)^2 (the difference taken in f64), peak_error = max |y - x| rounded to f32 once,
+ *   peak_out = max |y|, clipped = the count of |y| > 1, n = the compared frames of the block.
+ * Summation order: lane l of 64 holds the block positions j = l + 64 k, k = 0 .. 15, and adds its terms in k ascending from
+ * its k = 0 term; positions past the block's compared part add 0; the lanes then combine by an xor butterfly over offsets
+ * 32, 16, 8, 4, 2, 1 (v[l] = v[l] + v[l ^ o]).
+ * Per clip and channel: signal and error are the sequential f64 sums of the block values in block order, from 0.0;
+ * tail_energy is sum y^2 over the decoded frames past `compared`, per block of the same grid in the same lane order, the
+ * blocks then summed in order from 0.0; peak_error, peak_out and clipped are taken over all blocks.
+ *   snr_db = 10 log10(signal / error): +inf when error = 0 (silence included), -inf when signal = 0 < error.
+ *   seg_snr_db = the mean (sequential sum in block order, then / seg_blocks) over the blocks with signal / n >= 1e-10 of
+ *   clamp(10 log10(signal_b / error_b), -10, 60), an error_b of 0 counting as 60; NaN when no block qualifies.
+ * No float atomics: two calls return identical bits, whatever the split of the work.
+ * flo_batch_fidelity, after flo_batch_sync: out[n_clips * channels], clip-major; clip i's block records at
+ * blocks[(block_off[i] + b) * channels + c], block_off (n_clips + 1 entries) the running sum of n_blocks; blocks_cap counts
+ * records. out == NULL: the sizing call, only block_off is filled. blocks == NULL: the per-clip records only. A lossy batch
+ * is decoded and compared in one pass that writes no PCM; a lossless batch is decoded into device scratch and compared behind
+ * it (FLO_FIDELITY_UNFUSED=1, read per call, does the same for a lossy batch). The source is the batch's device copy.
+ * flo_compare: one .flo file against n_interleaved floats of host PCM with the file's channel count. out[channels];
+ * blocks (may be NULL) receives the clip's n_blocks * channels records, block-major (n_blocks <= ceil(source frames /
+ * 1024)); *n_blocks (may be NULL) is the clip's block count.
+ * Errors: FLO_ERR_STATE before sync; FLO_ERR_FORMAT for an unreadable file or a transform frame that does not deserialise,
+ * with flo_decode's message; FLO_ERR_ARG for null or short buffers. */
+typedef struct flo_fidelity_block {
+    double signal, error;
+    float peak_error, peak_out;
+    uint32_t clipped, n;
+} flo_fidelity_block;
+typedef struct flo_fidelity {   /* one channel of one clip */
+    double signal, error, tail_energy, snr_db, seg_snr_db;
+    float peak_error, peak_out;
+    uint64_t clipped, compared_frames, source_frames, decoded_frames;
+    uint32_t n_blocks, seg_blocks;
+} flo_fidelity;
+int flo_batch_fidelity(flo_batch *b, flo_fidelity *out, flo_fidelity_block *blocks, size_t blocks_cap, uint64_t *block_off);
+int flo_compare(flo_ctx *ctx, const float *pcm, size_t n_interleaved, const uint8_t *flo, size_t len, flo_fidelity *out,
+                flo_fidelity_block *blocks, size_t blocks_cap, size_t *n_blocks);
 
 /* ---- streaming encoder: StreamingEncoder of libflo/src/streaming/encoder.rs:6-257 -----------------------------
  * Samples are pushed (interleaved f32); every complete one-second frame is encoded losslessly - all frames a push
