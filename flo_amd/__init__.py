@@ -8,6 +8,7 @@ from .api import (Batch, Context, Decoder, EncodedFrame, Encoder, LossyEncoder, 
                   TransformEncoder, default_context, decode, encode, encode_lossy, encode_with_bitrate, probe_container)
 from .api import Corpus, SeekResult, TocEntry, decode_frame_at, get_toc, seek_to_time  # noqa: F401
 from .api import DecoderState, StreamingAudioInfo, StreamingDecoder, decode_streams  # noqa: F401
+from .api import EncodeStreamsResult, LossyStreamingEncoder, encode_streams  # noqa: F401
 from .api import encode_lossy_many, encode_many, encode_with_bitrate_many  # noqa: F401
 from .api import (FINGERPRINT_DTYPE, FingerprintIndex, extract_dominant_frequencies, fingerprint_array,  # noqa: F401
                   fingerprints_from_files, spectral_similarity)

@@ -29,6 +29,7 @@ EXPORTS = [
     "flo_dist_table_submit", "flo_dist_table_flush", "flo_dist_table_result",
     "flo_stream_create", "flo_stream_destroy", "flo_stream_push", "flo_stream_pending_samples", "flo_stream_pending_frames",
     "flo_stream_next_frame", "flo_stream_flush", "flo_stream_finalize",
+    "flo_stream_create_lossy", "flo_stream_append", "flo_stream_encode_ready",
     "flo_analyze", "flo_analysis_metadata", "flo_batch_analysis_metadata", "flo_batch_set_bit_depth",
     "flo_batch_analyze_all", "flo_batch_analysis_metadata_all", "flo_batch_clip_device_data",
     "flo_get_toc", "flo_seek_to_time", "flo_decode_frame_at",
@@ -189,6 +190,9 @@ def lib():
     L.flo_stream_next_frame.argtypes = [vp, u32p, u32p, u32p, C.POINTER(vp), C.POINTER(sz)]
     L.flo_stream_flush.argtypes = L.flo_stream_next_frame.argtypes
     L.flo_stream_finalize.argtypes = [vp, C.c_char_p, sz, C.POINTER(vp), C.POINTER(sz)]
+    L.flo_stream_create_lossy.argtypes = [vp, C.c_uint32, C.c_uint8, C.c_float, C.POINTER(vp)]
+    L.flo_stream_append.argtypes = [vp, vp, sz]
+    L.flo_stream_encode_ready.argtypes = [vp, sz, vp, vp]
     L.flo_analyze.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint8, C.c_uint32, vp, sz, C.POINTER(Analysis)]
     L.flo_analysis_metadata.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
     L.flo_decode.argtypes = [vp, C.c_char_p, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]

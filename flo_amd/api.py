@@ -598,6 +598,11 @@ class StreamingEncoder:
         p = _f32(samples)
         self._ctx._chk(self._L.flo_stream_push(self._h, p.ctypes.data, p.size))
 
+    def append_samples(self, samples):
+        """buffer samples without encoding anything: encode_streams encodes what is complete"""
+        p = _f32(samples)
+        self._ctx._chk(self._L.flo_stream_append(self._h, p.ctypes.data, p.size))
+
     def _pull(self, fn):
         idx, ts, ns = C.c_uint32(), C.c_uint32(), C.c_uint32()
         data, n = C.c_void_p(), C.c_size_t()
@@ -629,6 +634,53 @@ class StreamingEncoder:
             self.close()
         except Exception:
             pass
+
+
+class LossyStreamingEncoder(StreamingEncoder):
+    """The lossy encoder (TransformEncoder::encode_to_flo, lossy/encoder.rs:167-239) frame by frame, over
+    flo_stream_create_lossy: frame h comes out once (h + 1) * 1024 sample-frames have been pushed, byte for byte the
+    offline file's frame h; finalize() after pulling nothing is encode_lossy's file. flush() ends the input (the trailing
+    frames join the queue) and returns the queue's front."""
+
+    def __init__(self, sample_rate: int, channels: int, quality, ctx: Context = None):
+        if isinstance(quality, QualityPreset):
+            quality = quality.as_f32()
+        self.sample_rate, self.channels, self.quality = sample_rate, channels, float(quality)
+        self._ctx = ctx or default_context()
+        self._L = self._ctx._L
+        self._h = None
+        h = C.c_void_p()
+        self._ctx._chk(self._L.flo_stream_create_lossy(self._ctx._h, self.sample_rate, self.channels, self.quality, C.byref(h)))
+        self._h = h
+
+    def with_compression(self, level: int):
+        raise FloError("a lossy stream has no compression level")
+
+
+class EncodeStreamsResult(NamedTuple):
+    status: np.ndarray   # [n] int32: 0, or the stream's FLO_ERR_* code
+    errors: list         # [n] messages ("" where status is 0)
+
+
+def encode_streams(encoders, ctx: Context = None) -> EncodeStreamsResult:
+    """flo_stream_encode_ready: every complete frame of every encoder (LossyStreamingEncoder or StreamingEncoder) is
+    encoded and queued - per (sample rate, channels, quality) of the lossy ones one upload, one set of launches and one
+    read-back, the call synchronising once. The frames land in each encoder's queue (next_frame / finalize)."""
+    encoders = list(encoders)
+    if any(getattr(e, "_h", None) is None for e in encoders):
+        raise FloError("encode_streams: an encoder is closed")
+    if ctx is None:
+        ctx = encoders[0]._ctx if encoders else default_context()
+    n = len(encoders)
+    hs = (C.c_void_p * max(n, 1))(*[e._h.value for e in encoders])
+    st = np.zeros(max(n, 1), np.int32)
+    rc = ctx._L.flo_stream_encode_ready(ctx._h, n, C.cast(hs, C.c_void_p), st.ctypes.data)
+    st = st[:n].copy()
+    if rc != 0 and not st.any():   # the call itself was refused (a null or repeated encoder)
+        raise FloError(ctx._L.flo_last_error(ctx._h).decode())
+    msg = ctx._L.flo_last_error(ctx._h).decode() if st.any() else ""
+    errors = [("belongs to another context" if encoders[i]._ctx is not ctx else msg) if st[i] else "" for i in range(n)]
+    return EncodeStreamsResult(st, errors)
 
 
 def probe_container(data: bytes):

@@ -48,11 +48,40 @@ struct flo_ctx {
     AnalysisSide an_side;   // side streams of the analysis (made on first use)
     bool an_side_ready = false;
     struct SdecWork *sdec = nullptr;   // flo_sdec_decode_ready's staging slots and scratch (sdec.cpp; made on first use)
+    struct LstreamWork *lstream = nullptr;   // flo_stream_encode_ready's device scratch (lstream.cpp; made on first use)
 };
 
 int fail(flo_ctx *c, int code, const std::string &msg);
 // releases flo_ctx::sdec (sdec.cpp)
 void sdec_work_free(flo_ctx *c);
+// releases flo_ctx::lstream (lstream.cpp)
+void lstream_work_free(flo_ctx *c);
+
+// ---- streaming encoder (flo_stream_*: flo_api.cpp, the lossy stream step and flo_stream_encode_ready: lstream.cpp) --------
+struct StreamFrame {
+    uint32_t index, timestamp_ms, samples;
+    std::vector<uint8_t> data;
+};
+struct flo_stream {
+    flo_ctx *ctx = nullptr;
+    uint32_t sr = 0;
+    uint8_t ch = 0, bit_depth = 16, level = 5;
+    std::vector<float> buf;   // pushed samples not yet encoded (lossy: not yet the second half of an encoded frame)
+    std::vector<StreamFrame> pending;
+    uint64_t total_samples = 0;
+    uint32_t frame_index = 0;
+    // lossy stream (flo_stream_create_lossy): the state the encoder carries from frame to frame
+    bool lossy = false;
+    bool flushed = false;      // flush / finalize ended the input
+    float quality = 0.f;       // clamped to [0, 1]
+    std::vector<float> carry;  // [1024 * ch]: the last 1024 sample-frames of the input seen (zeros: the pre-roll)
+    std::vector<float> mask;   // [ch * 25]: temporal masking level after the last encoded frame
+};
+// the lossless frames of many streams of one (sample rate, channels, bit depth, level): stream items[i].first's next
+// items[i].second complete seconds, in one lossless batch; frames come back in item order (flo_api.cpp)
+int stream_encode_lossless(flo_ctx *c, const std::vector<std::pair<flo_stream *, size_t>> &items, std::vector<std::vector<uint8_t>> &frames);
+// queue the frames stream_encode_lossless made for `count` seconds of s and drop those seconds from its buffer
+void stream_queue_lossless(flo_stream *s, std::vector<std::vector<uint8_t>> &frames, size_t first, size_t count);
 #define HIPCHK(ctx, expr)                                                                               \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \

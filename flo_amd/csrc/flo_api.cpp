@@ -109,6 +109,7 @@ extern "C" void flo_ctx_destroy(flo_ctx *c) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     sdec_work_free(c);
+    lstream_work_free(c);
     for (auto *t : c->tables) {
         if (t->blob) hipFree(t->blob);
         delete t;
@@ -2249,21 +2250,8 @@ extern "C" int flo_ctx_reserved_cus(flo_ctx *c) { return c ? (c->reserve_cus > 0
 // frames are encoded (all frames a push completes go through ONE device batch, where the reference encodes them one
 // after the other through temporary files), frames are pulled or assembled into a file. Frame bytes follow the
 // reference's encode_frame_data / serialize_channel (encoder.rs:215-257) exactly, including its channel layout
-// [rice_parameter][coefficients][residuals], which is not the container writer's.
-struct StreamFrame {
-    uint32_t index, timestamp_ms, samples;
-    std::vector<uint8_t> data;
-};
-struct flo_stream {
-    flo_ctx *ctx = nullptr;
-    uint32_t sr = 0;
-    uint8_t ch = 0, bit_depth = 16, level = 5;
-    std::vector<float> buf;
-    std::vector<StreamFrame> pending;
-    uint64_t total_samples = 0;
-    uint32_t frame_index = 0;
-};
-
+// [rice_parameter][coefficients][residuals], which is not the container writer's. flo_stream_create_lossy makes the lossy
+// counterpart (lstream.cpp): frames of encode_to_flo as they complete. struct flo_stream: ctx_internal.hpp.
 extern "C" int flo_stream_create(flo_ctx *c, uint32_t sample_rate, uint8_t channels, uint8_t bit_depth, uint8_t level,
                                  flo_stream **out) {
     if (!c || !out) return FLO_ERR_ARG;
@@ -2282,19 +2270,21 @@ extern "C" void flo_stream_destroy(flo_stream *s) { delete s; }
 extern "C" size_t flo_stream_pending_samples(const flo_stream *s) { return s ? s->buf.size() / s->ch : 0; }
 extern "C" size_t flo_stream_pending_frames(const flo_stream *s) { return s ? s->pending.size() : 0; }
 
-// encode_frame_data for `count` chunks of `per` interleaved samples starting at `src` (encoder.rs:215-241): one
-// lossless batch, then every one-frame file is parsed like Reader::read and its first frame re-serialised
-static int stream_encode_chunks(flo_stream *s, const float *src, size_t count, size_t per, std::vector<std::vector<uint8_t>> &frames) {
-    flo_ctx *c = s->ctx;
+// encode_frame_data for chunks of interleaved samples (encoder.rs:215-241) of streams of cfg's (sample rate, channels, bit
+// depth, level): one lossless batch, then every one-frame file is parsed like Reader::read and its first frame re-serialised
+static int stream_encode_chunks(flo_ctx *c, const std::vector<std::pair<const float *, size_t>> &chunks, const flo_stream *cfg,
+                                std::vector<std::vector<uint8_t>> &frames) {
     frames.clear();
+    const size_t count = chunks.size();
     if (!count) return FLO_OK;
-    std::vector<size_t> n_il(count, per);
+    std::vector<size_t> n_il(count);
+    for (size_t i = 0; i < count; i++) n_il[i] = chunks[i].second;
     flo_batch *b = nullptr;
-    int rc = flo_batch_create(c, FLO_MODE_LOSSLESS, count, n_il.data(), s->sr, s->ch, (float)s->level, &b);
+    int rc = flo_batch_create(c, FLO_MODE_LOSSLESS, count, n_il.data(), cfg->sr, cfg->ch, (float)cfg->level, &b);
     if (rc != FLO_OK) return rc;
-    b->bit_depth = s->bit_depth;
+    b->bit_depth = cfg->bit_depth;
     std::vector<const float *> ptrs(count);
-    for (size_t i = 0; i < count; i++) ptrs[i] = src + i * per;
+    for (size_t i = 0; i < count; i++) ptrs[i] = chunks[i].first;
     rc = batch_upload_all(b, ptrs.data());
     if (rc == FLO_OK) rc = flo_batch_encode(b, 0);
     if (rc == FLO_OK) rc = flo_batch_sync(b);
@@ -2344,26 +2334,44 @@ static int stream_encode_chunks(flo_stream *s, const float *src, size_t count, s
     return rc;
 }
 
-extern "C" int flo_stream_push(flo_stream *s, const float *samples, size_t n) {
-    if (!s || (n && !samples)) return FLO_ERR_ARG;
-    s->buf.insert(s->buf.end(), samples, samples + n);
+int stream_encode_lossless(flo_ctx *c, const std::vector<std::pair<flo_stream *, size_t>> &items, std::vector<std::vector<uint8_t>> &frames) {
+    frames.clear();
+    if (items.empty()) return FLO_OK;
+    const flo_stream *cfg = items[0].first;
+    const size_t per = (size_t)cfg->sr * cfg->ch;
+    std::vector<std::pair<const float *, size_t>> chunks;
+    for (const auto &it : items)
+        for (size_t i = 0; i < it.second; i++) chunks.push_back({it.first->buf.data() + i * per, per});
+    return stream_encode_chunks(c, chunks, cfg, frames);
+}
+
+void stream_queue_lossless(flo_stream *s, std::vector<std::vector<uint8_t>> &frames, size_t first, size_t count) {
     const size_t per = (size_t)s->sr * s->ch;
-    const size_t count = s->buf.size() / per;
-    if (!count) return FLO_OK;
-    std::vector<std::vector<uint8_t>> frames;
-    int rc = stream_encode_chunks(s, s->buf.data(), count, per, frames);
-    if (rc != FLO_OK) return rc;
     for (size_t i = 0; i < count; i++) {
         StreamFrame f;
         f.index = s->frame_index;
         f.timestamp_ms = (uint32_t)((double)s->total_samples / (double)s->sr * 1000.0);
         f.samples = s->sr;
-        f.data = std::move(frames[i]);
+        f.data = std::move(frames[first + i]);
         s->pending.push_back(std::move(f));
         s->total_samples += s->sr;
         s->frame_index++;
     }
     s->buf.erase(s->buf.begin(), s->buf.begin() + count * per);
+}
+
+int lossy_stream_push(flo_stream *s, const float *samples, size_t n);   // lstream.cpp
+extern "C" int flo_stream_push(flo_stream *s, const float *samples, size_t n) {
+    if (!s || (n && !samples)) return FLO_ERR_ARG;
+    if (s->lossy) return lossy_stream_push(s, samples, n);
+    s->buf.insert(s->buf.end(), samples, samples + n);
+    const size_t per = (size_t)s->sr * s->ch;
+    const size_t count = s->buf.size() / per;
+    if (!count) return FLO_OK;
+    std::vector<std::vector<uint8_t>> frames;
+    int rc = stream_encode_lossless(s->ctx, {{s, count}}, frames);
+    if (rc != FLO_OK) return rc;
+    stream_queue_lossless(s, frames, 0, count);
     return FLO_OK;
 }
 
@@ -2391,7 +2399,7 @@ extern "C" int flo_stream_next_frame(flo_stream *s, uint32_t *index, uint32_t *t
 static int stream_flush_frame(flo_stream *s, StreamFrame &f) {   // 1 produced, 0 nothing buffered, < 0 error code negated
     if (s->buf.empty()) return 0;
     std::vector<std::vector<uint8_t>> frames;
-    int rc = stream_encode_chunks(s, s->buf.data(), 1, s->buf.size(), frames);
+    int rc = stream_encode_chunks(s->ctx, {{s->buf.data(), s->buf.size()}}, s, frames);
     if (rc != FLO_OK) return -rc;
     const size_t spc = s->buf.size() / s->ch;
     f.index = s->frame_index;
@@ -2405,8 +2413,13 @@ static int stream_flush_frame(flo_stream *s, StreamFrame &f) {   // 1 produced, 
 }
 
 // flush (encoder.rs:88-110): the buffered remainder as one (partial) frame, returned, not queued. 1 / 0 as next_frame
+int lossy_stream_end(flo_stream *s);   // lstream.cpp
 extern "C" int flo_stream_flush(flo_stream *s, uint32_t *index, uint32_t *timestamp_ms, uint32_t *samples, uint8_t **data, size_t *len) {
     if (!s || !data || !len) return -1;
+    if (s->lossy) {   // the end of the input: the trailing frames join the queue, whose front comes out
+        if (lossy_stream_end(s) != FLO_OK) return -1;
+        return flo_stream_next_frame(s, index, timestamp_ms, samples, data, len);
+    }
     StreamFrame f;
     int r = stream_flush_frame(s, f);
     if (r != 1) return r < 0 ? -1 : 0;
@@ -2416,7 +2429,10 @@ extern "C" int flo_stream_flush(flo_stream *s, uint32_t *index, uint32_t *timest
 // finalize (encoder.rs:113-185): a complete .flo file from the frames that have not been pulled
 extern "C" int flo_stream_finalize(flo_stream *s, const uint8_t *meta, size_t meta_len, uint8_t **out, size_t *out_len) {
     if (!s || !out || !out_len || (meta_len && !meta)) return FLO_ERR_ARG;
-    {
+    if (s->lossy) {
+        int rc = lossy_stream_end(s);
+        if (rc != FLO_OK) return rc;
+    } else {
         StreamFrame f;
         int r = stream_flush_frame(s, f);
         if (r < 0) return -r;
@@ -2437,12 +2453,20 @@ extern "C" int flo_stream_finalize(flo_stream *s, const uint8_t *meta, size_t me
         data.insert(data.end(), f.data.begin(), f.data.end());
         total += f.samples;
     }
+    // a lossy stream's header is encode_to_flo's (encoder.rs:229-238): lossy flag and quality level, 16 bits, level 5
     std::vector<uint8_t> o = {'F', 'L', 'O', '!', 1, 2, 0, 0};
+    if (s->lossy) {
+        TableSet *ts = nullptr;
+        int rc = get_tables(s->ctx, s->sr, s->quality, &ts);
+        if (rc != FLO_OK) return rc;
+        o[6] = 0x01;
+        o[7] = ts->host.q_level;
+    }
     put(o, s->sr, 4);
     o.push_back(s->ch);
-    o.push_back(s->bit_depth);
+    o.push_back(s->lossy ? 16 : s->bit_depth);
     put(o, total, 8);
-    o.push_back(s->level);
+    o.push_back(s->lossy ? 5 : s->level);
     put(o, 0, 3);
     put(o, host_crc32(data.data(), data.size()), 4);
     put(o, 66, 8);

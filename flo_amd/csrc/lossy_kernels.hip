@@ -995,8 +995,14 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
 
 // ---------------------------------------------------------------------------------------------- frame-parallel
 // PASS 1: a_t only. PASS 2: full frame into slot gframe. One wave per frame, CH = all channels in lock-step.
-template <int CH, int PASS, bool EXACT>
+// STEP = PASS, or PASS | kStreamStep for the stream step's instantiations (flo_stream_encode_ready, see lossy_kernels.hpp):
+// there clip `clip` is a stream's window - the 1024 sample-frames it carried over, then its new ones - and h counts the
+// step's frames from the stream's first new one, whose first half is the carried block. The loads start one block later
+// than a clip's, and no frame of a step is a pre-roll frame.
+template <int CH, int STEP, bool EXACT>
 __global__ __launch_bounds__(64) void lossy_frame_kernel(LossyArgs A) {
+    constexpr int PASS = STEP & ~kStreamStep;
+    constexpr bool STREAM = (STEP & kStreamStep) != 0;
     __shared__ WaveLds<CH> lds;
     __shared__ __attribute__((aligned(16))) uint8_t stage[kFrameCap + 64 + 256];
     const int lane = lane_id();
@@ -1021,8 +1027,8 @@ __global__ __launch_bounds__(64) void lossy_frame_kernel(LossyArgs A) {
         load_coeffs<CH>(lane, c, A, gframe, 0);
     } else {
         float ae[CH][8], ao[CH][8], be[CH][8], bo[CH][8];
-        load_half<CH>(lane, pcm, n_sf, A.nch, 0, (long long)h * 1024 - 1024, ae, ao);
-        load_half<CH>(lane, pcm, n_sf, A.nch, 0, (long long)h * 1024, be, bo);
+        load_half<CH>(lane, pcm, n_sf, A.nch, 0, (long long)(h + STREAM) * 1024 - 1024, ae, ao);
+        load_half<CH>(lane, pcm, n_sf, A.nch, 0, (long long)(h + STREAM) * 1024, be, bo);
         mdct_frame<CH>(lane, ae, ao, be, bo, lds, A.T, c);
     }
     FrameState<CH> st;
@@ -1062,8 +1068,10 @@ struct QuantOnlyLds {
     float4 ts[32];
     uint32_t qh[2][512];
 };
-template <int PASS, bool FROMCOEF = false>
+template <int STEP, bool FROMCOEF = false>   // STEP: as lossy_frame_kernel's
 __global__ __launch_bounds__(64) void lossy_frame2x_kernel(LossyArgs A) {
+    constexpr int PASS = STEP & ~kStreamStep;
+    constexpr bool STREAM = (STEP & kStreamStep) != 0;
     constexpr bool kSmall = PASS == 2 && FROMCOEF;
     __shared__ typename std::conditional<kSmall, QuantOnlyLds, StereoLds>::type lds;
     __shared__ __attribute__((aligned(16))) uint8_t stage[PASS == 2 ? kFrameCap + 64 + 256 : 16];
@@ -1104,13 +1112,13 @@ __global__ __launch_bounds__(64) void lossy_frame2x_kernel(LossyArgs A) {
         }
     } else {
         v2f ae[8], ao[8], be[8], bo[8];
-        if (h == 0) {   // pre-roll: 1024 zeros (encoder.rs:177)
+        if (!STREAM && h == 0) {   // pre-roll: 1024 zeros (encoder.rs:177)
 #pragma unroll
             for (int r = 0; r < 8; r++) ae[r] = ao[r] = splat2(0.f);
         } else {
-            load_half_fast_2(lane, pcm, (long long)h * 1024 - 1024, ae, ao);
+            load_half_fast_2(lane, pcm, (long long)(h + STREAM) * 1024 - 1024, ae, ao);
         }
-        load_half_fast_2(lane, pcm, (long long)h * 1024, be, bo);   // the batch pads every clip: no bounds to check
+        load_half_fast_2(lane, pcm, (long long)(h + STREAM) * 1024, be, bo);   // the batch pads every clip: no bounds to check
         v2f zr[8], zi[8];
         fold_2(lane, ae, ao, be, bo, zr, zi, T);
         fft512_2(lane, zr, zi, lds.u.xch4, T);
@@ -1269,8 +1277,10 @@ __global__ __launch_bounds__(64) void lossy_frame2x_kernel(LossyArgs A) {
 // Any channel count up to kMaxLossyChannels: one wave per frame walks the channels one after the other with the
 // single-channel device functions. Pass 2 parks every channel's integers (i16) in LDS because the byte position of a
 // channel's sparse blob depends on the sizes of the channels before it, then plans again and emits in channel order.
-template <int PASS, bool EXACT>
+template <int STEP, bool EXACT>   // STEP: as lossy_frame_kernel's
 __global__ __launch_bounds__(64) void lossy_frame_n_kernel(LossyArgs A) {
+    constexpr int PASS = STEP & ~kStreamStep;
+    constexpr bool STREAM = (STEP & kStreamStep) != 0;
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];   // stage[slot_bytes + 256] | park[nch][1024] i16
     __shared__ WaveLds<1> lds;
     __shared__ uint32_t s_tot[kMaxLossyChannels], s_sfw[kMaxLossyChannels][32];
@@ -1299,8 +1309,8 @@ __global__ __launch_bounds__(64) void lossy_frame_n_kernel(LossyArgs A) {
             load_coeffs<1>(lane, c, A, gframe, ch);
         } else {
             float ae[1][8], ao[1][8], be[1][8], bo[1][8];
-            load_half<1>(lane, pcm, n_sf, nch, ch, (long long)h * 1024 - 1024, ae, ao);
-            load_half<1>(lane, pcm, n_sf, nch, ch, (long long)h * 1024, be, bo);
+            load_half<1>(lane, pcm, n_sf, nch, ch, (long long)(h + STREAM) * 1024 - 1024, ae, ao);
+            load_half<1>(lane, pcm, n_sf, nch, ch, (long long)(h + STREAM) * 1024, be, bo);
             mdct_frame<1>(lane, ae, ao, be, bo, lds, A.T, c);
         }
         FrameState<1> st;
@@ -1379,6 +1389,43 @@ __global__ void lossy_scan_kernel(LossyArgs A) {
             }
         }
     }
+}
+
+// The temporal recurrence over a stream step's frames (flo_stream_encode_ready), seeded per (stream, channel, band) from
+// the level the stream carried over: seed[(i * nch + ch) * 25 + band]. Blocks of kScanBlock frames as in lossy_scan_kernel;
+// the first two blocks run from the seed, which is the sequential chain, a later block is warmed up from 0 over the 64
+// frames in front of it, which gives the same thresholds (see there). The thread of a stream's last block leaves the level
+// after the stream's last frame in level_out (same layout): the state the stream carries into its next step.
+__global__ void lossy_stream_scan_kernel(LossyArgs A, const float *seed, float *level_out) {
+    const unsigned clip = blockIdx.x;
+    if (clip >= (unsigned)A.n_clips) return;
+    const unsigned hops = A.clip_hops[clip];
+    const unsigned fs = blockIdx.y * kScanBlock;
+    if (fs >= hops) return;
+    const unsigned ch = threadIdx.x >> 5, band = threadIdx.x & 31u;
+    if (ch >= (unsigned)A.nch || band >= 25) return;
+    const unsigned long long f0 = A.clip_frame0[clip];
+    const unsigned fw = fs >= 2 * kScanBlock ? fs - kScanBlock : 0;
+    const unsigned fe = fs + kScanBlock < hops ? fs + kScanBlock : hops;
+    const unsigned lvl = (clip * (unsigned)A.nch + ch) * 25u + band;
+    float s = fw == 0 ? seed[lvl] : 0.f;
+    const unsigned long long stride = (unsigned long long)A.nch * 32;
+    const float *at = A.a_t + (f0 * A.nch + ch) * 32 + band;
+    float *sp = A.s_prev_out + (f0 * A.nch + ch) * 32 + band;
+    for (unsigned h0 = fw; h0 < fe; h0 += 16) {
+        float a[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) a[j] = h0 + j < fe ? at[(unsigned long long)(h0 + j) * stride] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const unsigned h = h0 + j;
+            if (h < fe) {
+                if (h >= fs) sp[(unsigned long long)h * stride] = s;
+                s = fmaxf(a[j], s * 0.7f);
+            }
+        }
+    }
+    if (fe == hops) level_out[lvl] = s;
 }
 
 // pack the fixed-size slots of one clip into its DATA chunk: one workgroup per frame
@@ -1788,6 +1835,32 @@ int launch_lossy_frames_pass(const LossyArgs &A, FrameKernel k, hipStream_t s) {
     case FrameKernel::Multi2Exact: hipLaunchKernelGGL((lossy_frame_n_kernel<2, true>), g, b, dynb, s, A); break;
     default: return -1;
     }
+    FLO_LAUNCH_CHECK();
+    return 0;
+}
+int launch_lossy_stream_pass(const LossyArgs &A, int pass, hipStream_t s) {
+    dim3 g((unsigned)A.total_frames), b(64);
+    const size_t dynb = (size_t)A.slot_bytes + 256 + (size_t)A.nch * 2048;   // lossy_frame_n_kernel
+    constexpr int S1 = 1 | kStreamStep, S2 = 2 | kStreamStep;
+    if (A.nch == 1) {
+        if (pass == 1) hipLaunchKernelGGL((lossy_frame_kernel<1, S1, false>), g, b, 0, s, A);
+        else hipLaunchKernelGGL((lossy_frame_kernel<1, S2, false>), g, b, 0, s, A);
+    } else if (A.nch == 2) {
+        if (pass == 1) hipLaunchKernelGGL((lossy_frame2x_kernel<S1>), g, b, 0, s, A);
+        else hipLaunchKernelGGL((lossy_frame2x_kernel<S2>), g, b, 0, s, A);
+    } else if (A.nch <= kMaxLossyChannels) {
+        if (pass == 1) hipLaunchKernelGGL((lossy_frame_n_kernel<S1, false>), g, b, dynb, s, A);
+        else hipLaunchKernelGGL((lossy_frame_n_kernel<S2, false>), g, b, dynb, s, A);
+    } else {
+        return -1;
+    }
+    FLO_LAUNCH_CHECK();
+    return 0;
+}
+int launch_lossy_stream_scan(const LossyArgs &A, const float *seed, float *level_out, hipStream_t s) {
+    const unsigned max_hops = (unsigned)A.max_hops;
+    hipLaunchKernelGGL(lossy_stream_scan_kernel, dim3(A.n_clips, (max_hops + kScanBlock - 1) / kScanBlock), dim3(32 * A.nch), 0, s, A,
+                       seed, level_out);
     FLO_LAUNCH_CHECK();
     return 0;
 }

@@ -70,6 +70,16 @@ inline unsigned int lossy_slot_bytes(int nch) {
 constexpr int kMaxLossyChannels = 8;      // more channels than two take the generic frame-parallel kernel
 int launch_lossy_scan(const LossyArgs &A, hipStream_t s);
 int launch_lossy_compact(const LossyArgs &A, CompactKernel k, hipStream_t s);
+// Stream step (flo_stream_encode_ready, lstream.cpp): the frame-parallel passes over streams' windows are the instantiations
+// of the frame kernels with PASS | kStreamStep (lossy_frame_kernel<1, .>, lossy_frame2x_kernel, lossy_frame_n_kernel by
+// A.nch); the temporal scan is seeded from the streams' carried levels and leaves their new ones.
+constexpr int kStreamStep = 4;
+int launch_lossy_stream_pass(const LossyArgs &A, int pass, hipStream_t s);
+int launch_lossy_stream_scan(const LossyArgs &A, const float *seed, float *level_out, hipStream_t s);
+// stream step (flo_stream_encode_ready, lstream.cpp): pass 1 or 2 of the frame-parallel form over streams' windows (the
+// kernel by A.nch: 1, 2, 3..8 channels), and the temporal scan seeded from the streams' carried levels
+int launch_lossy_stream_pass(const LossyArgs &A, int pass, hipStream_t s);
+int launch_lossy_stream_scan(const LossyArgs &A, const float *seed, float *level_out, hipStream_t s);
 int launch_mdct_only(const LossyDevTables &T, const float *frames, unsigned long long n, float *out, hipStream_t s);
 int launch_quantise_smr(const LossyDevTables &T, const float *coeffs, const float *smr, unsigned long long n, short *q, float *sf,
                         hipStream_t s);

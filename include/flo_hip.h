@@ -479,6 +479,32 @@ int flo_stream_flush(flo_stream *s, uint32_t *index, uint32_t *timestamp_ms, uin
                      size_t *len);
 int flo_stream_finalize(flo_stream *s, const uint8_t *meta, size_t meta_len, uint8_t **out, size_t *out_len);
 
+/* ---- lossy streaming encoder: encode_to_flo (libflo/src/lossy/encoder.rs:167-239) frame by frame, many streams per pass ----
+ * A lossy stream is a flo_stream: pending_*, push, next_frame, flush, finalize and destroy apply to it.
+ *   - Byte identity: samples pushed in any pieces (a piece may split a sample-frame), nothing pulled, then finalize(meta)
+ *     gives byte for byte flo_encode_lossy(ctx, x, sr, ch, quality, meta), the empty signal included; a trailing partial
+ *     sample-frame is dropped as the offline encoder drops it.
+ *   - Frame h (0: the pre-roll frame) is encoded and queued once (h + 1) * 1024 sample-frames have been pushed; its
+ *     (index, timestamp_ms, samples = 1024, data) are the offline file's TOC entry h and frame bytes. How the input is
+ *     cut into pushes, and how many frames each stream brings to a flo_stream_encode_ready call, change no byte.
+ *   - flush ends the input: the one or two trailing frames that the offline encoder makes from its zero padding join the
+ *     queue, then it returns the queue's front like next_frame (1 / 0). Afterwards push and append return FLO_ERR_STATE.
+ *     finalize flushes if that has not happened, then writes a file of the frames not pulled yet (META verbatim).
+ *   - pending_samples: sample-frames pushed but not yet the second half of an encoded frame (0 .. 1023 after a push).
+ * flo_stream_create_lossy: quality clamped to [0, 1] (TransformEncoder::new); channels 1 .. 8, FLO_ERR_ARG otherwise.
+ * flo_stream_append (either kind of stream): buffers the samples, encodes nothing.
+ * flo_stream_encode_ready: every complete frame of every listed stream is encoded and queued; status[i] is FLO_OK or the
+ *   stream's error (FLO_ERR_ARG for a stream of another context); returns FLO_OK or the first error. Lossy streams of any
+ *   mix of (sample rate, channels, quality): per distinct configuration one upload (the streams' windows - the 1024
+ *   sample-frames each carried over and its new ones - with their carried masking levels), one set of launches and one
+ *   read-back; the call synchronises once. A stream's carried state stays on the host: streams own no device memory.
+ *   Lossless streams: their complete seconds in one lossless batch per (sample rate, channels, bit depth, level), frames
+ *   as flo_stream_push makes them. Streams with nothing complete contribute nothing. On a lossy stream flo_stream_push is
+ *   append + encode_ready(ctx, 1, &s); on a lossless stream it is what it was. */
+int flo_stream_create_lossy(flo_ctx *ctx, uint32_t sample_rate, uint8_t channels, float quality, flo_stream **out);
+int flo_stream_append(flo_stream *s, const float *samples, size_t n_interleaved);
+int flo_stream_encode_ready(flo_ctx *ctx, size_t n, flo_stream *const *streams, int *status);
+
 /* ---- measurement hooks ----------------------------------------------------------------------------- */
 /* When enabled, every launch of a named kernel on the ctx stream is bracketed by hipEvents on that stream. */
 int flo_ctx_profile_enable(flo_ctx *ctx, int on);
