@@ -532,10 +532,12 @@ extern "C" int flo_batch_fill_synthetic(flo_batch *b, uint32_t seed, uint64_t cl
 
 // the batch's lossy plan for flo_batch_encode's `which` (encode_plan.hpp); the diagnostic switches are read here, once
 // (FLO_TAIL_CRC=0: every CRC from finish_files, the tests compare both; FLO_CHAIN2X_CLIPS: clips per workgroup)
+// A launch at quality >= 0.99 runs the exact-threshold instantiations: only those hold the reference's "-100 dB" branch
+// for |c| <= 1e-10, which at that quality alone keeps coefficients (lossy_exact, lossy_kernels.hpp).
 static LossyPlan lossy_plan(const flo_batch *b, int which, int force_path) {
     const char *tc = getenv("FLO_TAIL_CRC"), *clips = getenv("FLO_CHAIN2X_CLIPS");
     return plan_lossy({.which = which, .force_path = force_path, .ch = b->ch, .n_clips = b->n_clips, .total_frames = b->total_frames,
-                       .exact = b->exact != 0, .in_coeffs = b->d_in_coeffs != nullptr, .debug = b->d_dbg_coeffs || b->d_dbg_q || b->d_dbg_sfw,
+                       .exact = lossy_exact(b->exact != 0, b->ts->dev), .in_coeffs = b->d_in_coeffs != nullptr, .debug = b->d_dbg_coeffs || b->d_dbg_q || b->d_dbg_sfw,
                        .dirty = b->ts->dev.dirty, .tail_crc = !(tc && tc[0] == '0'), .chain2q_clips = clips ? atoi(clips) : 0});
 }
 // scratch of the frame-parallel form: per-frame masking levels, fixed-size frame slots, frame offsets
@@ -582,7 +584,7 @@ static LossyArgs make_args(flo_batch *b) {
     A.dbg_q = b->d_dbg_q;
     A.dbg_sfw = b->d_dbg_sfw;
     A.in_coeffs = b->d_in_coeffs;
-    A.exact = b->exact;
+    A.exact = lossy_exact(b->exact != 0, b->ts->dev);
     A.dbg_stamps = b->d_stamps;
     A.next_clip = b->d_next;
     A.n_cus = b->ctx->prop.multiProcessorCount - (b->ctx->reserve_cus > 0 ? b->ctx->reserve_cus : 0);

@@ -1844,12 +1844,17 @@ int launch_lossy_stream_pass(const LossyArgs &A, int pass, hipStream_t s) {
     constexpr int S1 = 1 | kStreamStep, S2 = 2 | kStreamStep;
     if (A.nch == 1) {
         if (pass == 1) hipLaunchKernelGGL((lossy_frame_kernel<1, S1, false>), g, b, 0, s, A);
+        else if (A.exact) hipLaunchKernelGGL((lossy_frame_kernel<1, S2, true>), g, b, 0, s, A);
         else hipLaunchKernelGGL((lossy_frame_kernel<1, S2, false>), g, b, 0, s, A);
+    } else if (A.nch == 2 && A.exact) {   // (the lock-step pair kernels have no exact-threshold instantiation)
+        if (pass == 1) hipLaunchKernelGGL((lossy_frame_kernel<2, S1, false>), g, b, 0, s, A);
+        else hipLaunchKernelGGL((lossy_frame_kernel<2, S2, true>), g, b, 0, s, A);
     } else if (A.nch == 2) {
         if (pass == 1) hipLaunchKernelGGL((lossy_frame2x_kernel<S1>), g, b, 0, s, A);
         else hipLaunchKernelGGL((lossy_frame2x_kernel<S2>), g, b, 0, s, A);
     } else if (A.nch <= kMaxLossyChannels) {
         if (pass == 1) hipLaunchKernelGGL((lossy_frame_n_kernel<S1, false>), g, b, dynb, s, A);
+        else if (A.exact) hipLaunchKernelGGL((lossy_frame_n_kernel<S2, true>), g, b, dynb, s, A);
         else hipLaunchKernelGGL((lossy_frame_n_kernel<S2, false>), g, b, dynb, s, A);
     } else {
         return -1;

@@ -41,7 +41,8 @@ struct LossyArgs {
     unsigned short *dbg_sfw;                 // [total_frames][nch][25]
     const float *in_coeffs;                  // when set: skip the transform, quantise these spectra
     unsigned long long *dbg_stamps;          // diagnostic builds (FLO_STAMPS): per-wave phase cycle sums [wave][16]
-    int exact;                               // re-decide near-threshold coefficients with the reference's dB expression
+    int exact;                               // the exact-threshold instantiations run (lossy_exact): near-threshold coefficients
+                                             // and |c| <= 1e-10 are decided with the reference's dB expression
     unsigned int *next_clip;                 // lock-step stereo form: batch-wide counter of claimed clips (zero at launch), then
                                              // the done queue's tail and head counters (next_clip[1], [2]; zero at launch)
     // lock-step stereo form, CRC in the launch's idle tail (crc_ready null: none): a packer wave that finds the batch
@@ -56,6 +57,14 @@ struct LossyArgs {
     const unsigned int *crc_tab;             // crc_device_tables()
     int n_cus;                               // compute units of the device (persistent workgroups)
 };
+
+// Whether a launch runs the exact-threshold instantiations (quantise<., EXACT = true>): when the caller asks for the
+// yardstick, and always at quality >= 0.99. There the reference keeps a coefficient of |c| <= 1e-10 wherever its threshold is
+// below 0 dB (its level is pinned at -100 dB, the keep threshold's own value) and quantises it with 30000 / band_max: a
+// non-zero integer on fade and reverb tails whose band maximum is just above 1e-10. The amplitude-domain test
+// |c| > max(T_band, T_ath) of the shipped instantiations cannot express that (it is not monotone in |c|), and the flag is
+// uniform per launch: the choice is made here, on the host, and the kernels of every other quality stay as they are.
+inline bool lossy_exact(bool asked, const LossyDevTables &T) { return asked || T.q_transparent != 0; }
 
 // the launchers launch the kernels the plan names (encode_plan.hpp); they choose only the launch geometry
 int launch_lossy_chain(const LossyArgs &A, const LossyPlan &P, hipStream_t s);

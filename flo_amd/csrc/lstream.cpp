@@ -203,6 +203,7 @@ int enqueue_group(flo_ctx *c, LossyGroup &g) {
     A.slot_bytes = lossy_slot_bytes((int)nch);
     A.frame_off = (unsigned long long *)(d + g.o_foff);
     A.n_cus = c->prop.multiProcessorCount;
+    A.exact = lossy_exact(false, A.T);
     const float *d_seed = (const float *)(d + g.o_seed);
     float *d_lvl = (float *)(out + g.r_lvl);
     int rc;

@@ -90,6 +90,12 @@ size_t flo_o_lossy_analyze(const float *pcm, size_t n_interleaved, uint32_t samp
 size_t flo_o_lossy_analyze_f64mdct(const float *pcm, size_t n_interleaved, uint32_t sample_rate, uint8_t channels,
                                    float quality, float *coeffs, float *smr, int16_t *q, float *sf, uint16_t *sf_words);
 
+/* the psychoacoustic model, quantiser and scale words of that driver over caller-supplied spectra
+ * [hops][channels][1024] (temporal masking state carried per channel): smr/q [hops][channels][1024],
+ * sf/sf_words [hops][channels][25]. Any output pointer may be NULL. */
+void flo_o_lossy_quantize_frames(const float *coeffs, size_t hops, uint32_t sample_rate, uint8_t channels, float quality,
+                                 float *smr, int16_t *q, float *sf, uint16_t *sf_words);
+
 /* ---- top-level API (lossless/encoder.rs:32-45, lossy/encoder.rs:167-239, lib.rs:296-352) ---- */
 int flo_o_encode_lossless(const float *pcm, size_t n_interleaved, uint32_t sample_rate, uint8_t channels,
                           uint8_t bit_depth, uint8_t level, const uint8_t *meta, size_t meta_len,

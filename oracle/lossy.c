@@ -556,6 +556,35 @@ size_t flo_o_lossy_analyze_f64mdct(const float *pcm, size_t n, uint32_t sample_r
     return nf;
 }
 
+/* psychoacoustic model + quantiser + scale words over caller-supplied spectra [hops][channels][1024]: the same
+ * psy_calculate_smr and quantize_coefficients the clip driver calls per frame, one temporal state per channel.
+ * Gives the reference's f32 decisions for coefficients that never came out of its own transform (hand-made
+ * spectra, non-finite values). Any output pointer may be NULL. */
+void flo_o_lossy_quantize_frames(const float *coeffs, size_t hops, uint32_t sample_rate, uint8_t channels, float quality,
+                                 float *smr_out, int16_t *q_out, float *sf_out, uint16_t *sf_words) {
+    size_t ch = channels;
+    if (quality < 0.0f) quality = 0.0f; /* TransformEncoder::new: quality.clamp(0,1) */
+    if (quality > 1.0f) quality = 1.0f;
+    psy_model *psy = (psy_model *)calloc(ch ? ch : 1, sizeof(psy_model));
+    for (size_t c = 0; c < ch; c++) psy_init(&psy[c], sample_rate, 2048);
+    float smr[1024], sf[NUM_BARK_BANDS];
+    int16_t q[1024];
+    for (size_t hop = 0; hop < hops; hop++)
+        for (size_t c = 0; c < ch; c++) {
+            size_t o = hop * ch + c;
+            const float *cf = coeffs + o * 1024;
+            psy_calculate_smr(&psy[c], cf, smr);
+            quantize_coefficients(sample_rate, quality, cf, smr, q, sf);
+            if (smr_out) memcpy(smr_out + o * 1024, smr, sizeof smr);
+            if (q_out) memcpy(q_out + o * 1024, q, sizeof q);
+            if (sf_out) memcpy(sf_out + o * NUM_BARK_BANDS, sf, sizeof sf);
+            if (sf_words)
+                for (size_t b = 0; b < NUM_BARK_BANDS; b++) sf_words[o * NUM_BARK_BANDS + b] = flo_o_scale_factor_word(sf[b]);
+        }
+    for (size_t c = 0; c < ch; c++) psy_free(&psy[c]);
+    free(psy);
+}
+
 int flo_o_encode_lossy(const float *pcm, size_t n, uint32_t sample_rate, uint8_t channels, float quality,
                        const uint8_t *meta, size_t meta_len, uint8_t **out, size_t *out_len) {
     if (channels == 0 || sample_rate == 0) {

@@ -81,6 +81,9 @@ def lib():
         L.flo_o_lossy_analyze.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint8, C.c_float,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.flo_o_lossy_analyze_f64mdct.argtypes = L.flo_o_lossy_analyze.argtypes
+        L.flo_o_lossy_quantize_frames.restype = None
+        L.flo_o_lossy_quantize_frames.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint8, C.c_float,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.flo_o_encode_lossless.restype = C.c_int
         L.flo_o_encode_lossless.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint8,
                                             C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -241,6 +244,21 @@ def lossy_analyze(pcm, sample_rate, channels, quality, f64_mdct=False):
              smr.ctypes.data, q.ctypes.data, sf.ctypes.data, sfw.ctypes.data)
     assert got == nh
     return dict(coeffs=coeffs, smr=smr, q=q, sf=sf, sf_words=sfw)
+
+
+def lossy_quantize(coeffs, sample_rate, quality):
+    """The reference's psychoacoustic model + quantiser + scale words on caller-supplied spectra [hops][ch][1024]
+    (temporal state carried per channel) -> dict(coeffs, smr, q, sf, sf_words) shaped like lossy_analyze's."""
+    c = _f32(coeffs)
+    assert c.ndim == 3 and c.shape[2] == 1024
+    nh, channels = c.shape[0], c.shape[1]
+    smr = np.zeros((nh, channels, 1024), np.float32)
+    q = np.zeros((nh, channels, 1024), np.int16)
+    sf = np.zeros((nh, channels, 25), np.float32)
+    sfw = np.zeros((nh, channels, 25), np.uint16)
+    lib().flo_o_lossy_quantize_frames(c.ctypes.data, nh, sample_rate, channels, quality, smr.ctypes.data, q.ctypes.data,
+                                      sf.ctypes.data, sfw.ctypes.data)
+    return dict(coeffs=c, smr=smr, q=q, sf=sf, sf_words=sfw)
 
 
 def encode_lossless(pcm, sample_rate, channels, bit_depth=16, level=5, meta=b"") -> bytes:

@@ -6,7 +6,7 @@ import flofile
 import signals
 from conftest import example_bytes
 from fixtures_util import LOSSY_EXAMPLES, dequantise, lossy_source_pcm
-from gpu_util import compare_lossy_stage, ctx, same_structure, snr_db  # noqa: F401
+from gpu_util import compare_lossy_stage, ctx, explain_lossy_stage, same_structure, snr_db  # noqa: F401
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -161,6 +161,9 @@ def test_quantiser_fed_oracle_spectra(ctx, q, exact):
         assert mism <= 1e-4, mism
         assert np.abs(g["sf_words"].astype(int) - o["sf_words"].astype(int)).max() <= 1
         assert (g["sf_words"] != o["sf_words"]).mean() <= 1e-3
+        # and every coefficient and scale word accounted for against the f64 model, not only their rates
+        r = explain_lossy_stage(g, o["coeffs"], 44100, q, f"q={q} exact={exact} path={path}", oracle=o)
+        print(f"  explained: window {r['eps']:.2e} dB, largest |margin| of a disagreement {r['worst_disagreement']:.2e} dB")
 
 
 def test_shipped_quantiser_on_a_long_clip_reports_its_flip_rate(ctx):
@@ -473,6 +476,13 @@ def test_blocked_scan_matches_sequential_chain_on_long_decays(ctx):
     b = ctx.encode_lossy(x, sr, 2, 0.55)
     ctx.force_path(0)
     assert a == b and len(flofile.parse(a).frames) == (n + 1024 + 1023) // 1024
+    # the two forms agreeing says nothing about code they share: the decisions themselves, explained from the device's own
+    # coefficients (the frames where 0.7 x the previous level decides are most of this clip)
+    for path in (5, 2):
+        ctx.force_path(path)
+        g = ctx.lossy_analyze(x, sr, 2, 0.55)
+        ctx.force_path(0)
+        explain_lossy_stage(g, g["coeffs"], sr, 0.55, f"long decays path{path}")
 
 
 @pytest.mark.parametrize("ch", [3, 6, 8])
@@ -529,9 +539,14 @@ def test_api_misuse_is_reported_not_crashed(ctx):
 
 @pytest.mark.parametrize("amp", [1.0, 3000.0, 1e12])
 def test_kernel_forms_agree_on_loud_and_lopsided_stereo(ctx, amp):
-    """The lock-step forms put channel 1's bands on lanes 32..56 of the masking pass; far beyond full scale that pass
-    walks all 24 band distances (the rare branch of spread_threshold), and a silent or much quieter channel next to a
-    loud one is where a leak between the halves would show. Every form must give the same files."""
+    """The lock-step forms put channel 1's bands on lanes 32..56 of the masking pass, and a silent or much quieter channel
+    next to a loud one is where a leak between the halves would show. Every form must give the same files, and - the forms
+    share spread_threshold* and quantise* - a sample of the clips is explained against the f64 model of the reference.
+    What PCM can and cannot reach: far beyond full scale the masking pass RUNS the branch for band distances 9..24
+    (gmax >= 99 dB), but on a transformed signal its result is never observed. An f32 transform leaves a floor ~140 dB
+    below the frame maximum in every band, and 25 dB per band falls below that after about five bands, so a nearer band
+    always sets the level (tests/test_psy_ref_cpu.py asserts it). That branch deciding a level is exercised by the hand-made
+    spectra of tests/test_gpu_lossy_explained.py."""
     import flo_amd
     sr, ch = 44100, 2
     clips = []
@@ -553,6 +568,13 @@ def test_kernel_forms_agree_on_loud_and_lopsided_stereo(ctx, amp):
         b.close()
     for form in (1, 2):
         assert outs[form] == outs[5], form
+    ctx.force_path(5)
+    try:
+        for i in (0, 1, 5, 6, 15, 30):      # silent left, plain, both lopsided kinds, 60 dB down, all three at once
+            g = ctx.lossy_analyze(clips[i], sr, ch, 0.55)
+            explain_lossy_stage(g, g["coeffs"], sr, 0.55, f"amp {amp} clip {i}")
+    finally:
+        ctx.force_path(0)
 
 
 def test_transform_encoder_frame_methods(ctx):

@@ -48,6 +48,13 @@ for ch in (1, 2, 3):
     for level in (0, 5, 9):
         f = O.encode_lossless(pcm, 44100, ch, 16, level)
         O.decode(f)
+rq = np.random.default_rng(4)      # (its own generator: the damaged files below stay the ones they were)
+c = (rq.standard_normal((5, 3, 1024)) * 10.0 ** rq.uniform(-12, 12, (5, 3, 1))).astype(np.float32)
+c[1, 0, 3], c[2, 1, 900], c[3, 0, 0], c[3, 2, 500:504] = np.inf, np.nan, 3e38, 2e19      # ordinary data to the quantiser entry
+for sr in (8000, 44100, 384000):
+    for q in (0.0, 0.55, 1.0):
+        O.lossy_quantize(c, sr, q)
+O.lossy_quantize(c[:0], 44100, 0.55)
 ex = %r
 for name in sorted(os.listdir(ex)):
     if not name.endswith(".flo"):
