@@ -1,0 +1,857 @@
+// batch.cpp — device-resident batches (flo_batch_*), the pipeline of flo_encode_batch and the one-shot encodes: planning,
+// launches, .flo assembly. Host code only; the kernels live in lossy_kernels.hip / lossless_kernels.hip.
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "batch_internal.hpp"
+#include "container_kernels.hpp"
+#include "devpool.hpp"
+#include "lossy_kernels.hpp"
+
+static size_t lossy_max_frame_bytes(int ch) { return 12 + 50 * (size_t)ch + (size_t)ch * (4 + 2064); }
+
+// the batch's lossy plan for flo_batch_encode's `which` (encode_plan.hpp); the diagnostic switches are read here, once
+// (FLO_TAIL_CRC=0: every CRC from finish_files, the tests compare both; FLO_CHAIN2X_CLIPS: clips per workgroup)
+// A launch at quality >= 0.99 runs the exact-threshold instantiations: only those hold the reference's "-100 dB" branch
+// for |c| <= 1e-10, which at that quality alone keeps coefficients (lossy_exact, lossy_kernels.hpp).
+static LossyPlan lossy_plan(const flo_batch *b, int which, int force_path) {
+    const char *tc = getenv("FLO_TAIL_CRC"), *clips = getenv("FLO_CHAIN2X_CLIPS");
+    return plan_lossy({.which = which, .force_path = force_path, .ch = b->ch, .n_clips = b->n_clips, .total_frames = b->total_frames,
+                       .exact = lossy_exact(b->exact != 0, b->ts->dev), .in_coeffs = b->d_in_coeffs != nullptr, .debug = b->d_dbg_coeffs || b->d_dbg_q || b->d_dbg_sfw,
+                       .dirty = b->ts->dev.dirty, .tail_crc = !(tc && tc[0] == '0'), .chain2q_clips = clips ? atoi(clips) : 0});
+}
+// scratch of the frame-parallel form: per-frame masking levels, fixed-size frame slots, frame offsets
+static int alloc_frame_scratch(flo_batch *b, const LossyPlan &p) {
+    flo_ctx *c = b->ctx;
+    if (p.form != LossyForm::Frames || b->d_at || !b->total_frames) return FLO_OK;
+    const size_t n = (size_t)b->total_frames * b->ch * 32 * sizeof(float);
+    HIPCHK(c, pool_alloc(&b->d_at, n));
+    HIPCHK(c, pool_alloc(&b->d_sprev, n));
+    HIPCHK(c, pool_alloc(&b->d_bmax, n));
+    if (p.coef_handover) HIPCHK(c, pool_alloc(&b->d_coef, (size_t)b->total_frames * 8192));
+    HIPCHK(c, pool_alloc(&b->d_slots, (size_t)b->total_frames * lossy_slot_bytes(b->ch)));
+    HIPCHK(c, pool_alloc(&b->d_frame_off, (size_t)(b->total_frames + 1) * 8));
+    return FLO_OK;
+}
+
+extern "C" void flo_batch_destroy(flo_batch *b) {
+    if (!b) return;
+    hipSetDevice(b->ctx->device);
+    hipStreamSynchronize(b->ctx->stream);
+    void *ptrs[] = {b->d_pcm, b->d_plan, b->d_hops, b->d_out, b->d_frame_size, b->d_clip_bytes, b->d_crc, b->d_part, b->d_at,
+                    b->d_sprev, b->d_slots, b->d_frame_off, b->d_dbg_coeffs, b->d_dbg_q, b->d_dbg_sfw, b->d_pack_plan, b->d_next, b->d_bmax, b->d_coef,
+                    b->d_crc_ready, b->d_done_q};
+    for (void *p : ptrs)
+        if (p) pool_free(p);
+    if (b->ev_pack_plan) hipEventDestroy(b->ev_pack_plan);
+    if (b->pin_plan) stager_pinned_put(b->ctx->stager, b->pin_plan);
+    if (b->pin_sizes) stager_pinned_put(b->ctx->stager, b->pin_sizes);
+    if (b->ll) lossless_plan_destroy(b->ll);
+    delete b;
+}
+
+extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size_t *n_interleaved, uint32_t sr,
+                                uint8_t ch, float qol, flo_batch **out) {
+    if (!c || !out || (n_clips && !n_interleaved)) return FLO_ERR_ARG;
+    *out = nullptr;
+    if (ch == 0 || sr == 0) return fail(c, FLO_ERR_ARG, "sample_rate and channels must be non-zero");
+    if (mode != FLO_MODE_LOSSY && mode != FLO_MODE_LOSSLESS) return fail(c, FLO_ERR_ARG, "unknown mode");
+    if (mode == FLO_MODE_LOSSY && ch > kMaxLossyChannels)
+        return fail(c, FLO_ERR_ARG, "lossy encode on device supports 1 to 8 channels");
+    HIPCHK(c, hipSetDevice(c->device));
+    flo_batch *b = new flo_batch();
+    b->ctx = c;
+    b->mode = mode;
+    b->n_clips = n_clips;
+    b->sr = sr;
+    b->ch = ch;
+    b->qol = qol;
+    b->n_il.assign(n_interleaved, n_interleaved + n_clips);
+    b->clip_off.resize(n_clips);
+    b->clip_nsf.resize(n_clips);
+    uint64_t off = 0;
+    for (size_t i = 0; i < n_clips; i++) {
+        b->clip_off[i] = off;
+        b->clip_nsf[i] = n_interleaved[i] / ch;  // trailing partial sample-frame is dropped (encoder.rs:174)
+        uint64_t alloc = n_interleaved[i];
+        if (mode == FLO_MODE_LOSSY) {
+            // every frame's 1024 new sample-frames exist in memory: the clip is followed by zeros up to
+            // hops * 1024 sample-frames (the reference pads the same way, encoder.rs:177-185), so the chain kernels
+            // load whole half-frames without bounds checks; one more half-frame lets them prefetch unconditionally
+            // behind the last frame (the values are never used)
+            const uint64_t hops = (b->clip_nsf[i] + 1024 + 1023) / 1024;
+            alloc = (hops + 1) * 1024 * ch;
+            if (alloc < n_interleaved[i]) alloc = n_interleaved[i];
+        }
+        off += (alloc + 3) & ~(uint64_t)3;
+    }
+    b->total_floats = off;
+    int rc = FLO_OK;
+    auto bail = [&](int code) {
+        flo_batch_destroy(b);
+        return code;
+    };
+#define BCHK(expr)                                                                                  \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess) {                                                                     \
+            fail(c, e_ == hipErrorOutOfMemory ? FLO_ERR_NOMEM : FLO_ERR_DEVICE,                     \
+                 std::string(#expr) + ": " + hipGetErrorString(e_));                                \
+            return bail(e_ == hipErrorOutOfMemory ? FLO_ERR_NOMEM : FLO_ERR_DEVICE);                \
+        }                                                                                           \
+    } while (0)
+    BCHK(pool_alloc(&b->d_pcm, (b->total_floats + 4) * sizeof(float)));
+    if (mode == FLO_MODE_LOSSY) {   // the zero padding behind every clip (the clips themselves are written by the caller)
+        if (n_clips <= 8) {
+            for (size_t i = 0; i < n_clips; i++) {
+                const uint64_t used = b->clip_nsf[i] * ch;
+                const uint64_t end = (i + 1 < n_clips ? b->clip_off[i + 1] : b->total_floats) + (i + 1 < n_clips ? 0 : 4);
+                BCHK(hipMemsetAsync(b->d_pcm + b->clip_off[i] + used, 0, (end - b->clip_off[i] - used) * sizeof(float), c->stream));
+            }
+        } else {
+            BCHK(hipMemsetAsync(b->d_pcm, 0, (b->total_floats + 4) * sizeof(float), c->stream));
+        }
+    }
+    if (mode == FLO_MODE_LOSSY) {
+        rc = get_tables(c, sr, qol, &b->ts);
+        if (rc != FLO_OK) return bail(rc);
+        b->hops.resize(n_clips);
+        b->clip_frame0.resize(n_clips);
+        b->out_off.resize(n_clips);
+        b->out_cap.resize(n_clips);
+        b->file_off.resize(n_clips);
+        uint64_t f = 0, o = 0;
+        const size_t mfb = lossy_max_frame_bytes(ch);
+        for (size_t i = 0; i < n_clips; i++) {
+            uint64_t h = (b->clip_nsf[i] + 1024 + 1023) / 1024;  // encoder.rs:177-179
+            b->hops[i] = (uint32_t)h;
+            b->clip_frame0[i] = f;
+            f += h;
+            // header + TOC of the finished file sit right in front of the (16-byte aligned) DATA chunk
+            const uint64_t head = 74 + 20 * h;
+            o += (head + 15) & ~(uint64_t)15;
+            b->out_off[i] = o;
+            b->file_off[i] = o - head;
+            b->out_cap[i] = ((h * mfb + 64) + 15) & ~(uint64_t)15;
+            o += b->out_cap[i];
+        }
+        b->total_frames = f;
+        b->out_bytes = o;
+        std::vector<uint64_t> plan(4 * n_clips);
+        for (size_t i = 0; i < n_clips; i++) {
+            plan[i] = b->clip_off[i];
+            plan[n_clips + i] = b->clip_nsf[i];
+            plan[2 * n_clips + i] = b->clip_frame0[i];
+            plan[3 * n_clips + i] = b->out_off[i];
+        }
+        BCHK(pool_alloc(&b->d_plan, (plan.size() + 1) * 8));
+        BCHK(pool_alloc(&b->d_hops, (n_clips + 1) * 4));
+        BCHK(pool_alloc(&b->d_out, b->out_bytes + 64));
+        BCHK(pool_alloc(&b->d_frame_size, (b->total_frames + 1) * 4));
+        BCHK(pool_alloc(&b->d_clip_bytes, (n_clips + 1) * 8));
+        BCHK(pool_alloc(&b->d_crc, (n_clips + 1) * 4));
+        BCHK(pool_alloc(&b->d_next, 32));
+        BCHK(hipMemsetAsync(b->d_next, 0, 32, c->stream));   // once: every launch then zeroes its successor's counters
+        BCHK(pool_alloc(&b->d_part, (n_clips * finish_parts(n_clips) + 1) * 4));
+        if (n_clips) {
+            // from pinned memory on the context's stream, in front of everything that will use them: a synchronous (or
+            // pageable "asynchronous") copy would wait for whatever this context's other batches have in flight
+            std::string perr;
+            b->pin_plan = (uint64_t *)stager_pinned_get(c->stager, (8 * n_clips + 8) * 8, perr);
+            if (!b->pin_plan) {
+                fail(c, FLO_ERR_NOMEM, perr);
+                return bail(FLO_ERR_NOMEM);
+            }
+            memcpy(b->pin_plan, plan.data(), plan.size() * 8);
+            memcpy(b->pin_plan + 4 * n_clips, b->hops.data(), n_clips * 4);
+            BCHK(hipMemcpyAsync(b->d_plan, b->pin_plan, plan.size() * 8, hipMemcpyHostToDevice, c->stream));
+            BCHK(hipMemcpyAsync(b->d_hops, b->pin_plan + 4 * n_clips, n_clips * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        // the frame-parallel scratch up front when auto picks that form (a forced form allocates at its first encode)
+        if ((rc = alloc_frame_scratch(b, lossy_plan(b, 0, 0))) != FLO_OK) return bail(rc);
+    } else {
+        uint8_t level = qol < 0 ? 0 : (qol > 9 ? 9 : (uint8_t)qol);  // with_compression: level.min(9)
+        b->qol = level;
+        std::string err;
+        b->ll = lossless_plan_create(b->n_il, b->clip_off, sr, ch, level, b->d_pcm, err);
+        if (!b->ll) {
+            fail(c, FLO_ERR_NOMEM, "lossless plan: " + err);
+            return bail(FLO_ERR_NOMEM);
+        }
+    }
+#undef BCHK
+    *out = b;
+    return FLO_OK;
+}
+
+extern "C" float *flo_batch_clip_device_ptr(flo_batch *b, size_t clip) {
+    if (!b || clip >= b->n_clips) return nullptr;
+    if (clip < b->tail.size()) b->tail[clip].clear();   // (the caller writes the clip: it is analysed as the device holds it)
+    return b->d_pcm + b->clip_off[clip];
+}
+
+// the same address for reading only: the clip's kept tail (flo_batch_analyze_all) stays
+extern "C" const float *flo_batch_clip_device_data(const flo_batch *b, size_t clip) {
+    if (!b || clip >= b->n_clips) return nullptr;
+    return b->d_pcm + b->clip_off[clip];
+}
+
+extern "C" int flo_batch_upload(flo_batch *b, size_t clip, const float *pcm) {
+    if (!b || clip >= b->n_clips || (!pcm && b->n_il[clip])) return FLO_ERR_ARG;
+    flo_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    // a trailing partial sample-frame is not part of the clip (encoder.rs:174): it must not land in the zero padding
+    const uint64_t n_copy = b->mode == FLO_MODE_LOSSY ? b->clip_nsf[clip] * b->ch : b->n_il[clip];
+    if (n_copy)
+        HIPCHK(c, hipMemcpyAsync(b->d_pcm + b->clip_off[clip], pcm, n_copy * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    b->keep_tail(clip, pcm);
+    b->encoded = b->synced = b->encode_failed = false;
+    return FLO_OK;
+}
+
+extern "C" int flo_batch_fill_synthetic(flo_batch *b, uint32_t seed, uint64_t clip_id0) {
+    if (!b) return FLO_ERR_ARG;
+    flo_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!b->n_clips) return FLO_OK;
+    // plan arrays needed on device: clip_off, clip_nsf
+    uint64_t *d_off = nullptr;
+    std::vector<uint64_t> tmp(2 * b->n_clips);
+    for (size_t i = 0; i < b->n_clips; i++) {
+        tmp[i] = b->clip_off[i];
+        tmp[b->n_clips + i] = b->clip_nsf[i];
+    }
+    HIPCHK(c, hipMalloc(&d_off, tmp.size() * 8));
+    hipError_t e = hipMemcpyAsync(d_off, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice, c->stream);
+    int rc = 0;
+    if (e == hipSuccess)
+        rc = launch_synth_fill(b->d_pcm, (const unsigned long long *)d_off, (const unsigned long long *)d_off + b->n_clips, (int)b->n_clips, b->ch, seed, clip_id0, c->stream);
+    hipStreamSynchronize(c->stream);
+    hipFree(d_off);
+    b->tail.clear();
+    if (e != hipSuccess || rc != 0) return fail(c, FLO_ERR_DEVICE, "synthetic fill failed");
+    b->encoded = b->synced = b->encode_failed = false;
+    return FLO_OK;
+}
+
+static LossyArgs make_args(flo_batch *b) {
+    LossyArgs A{};
+    A.T = b->ts->dev;
+    A.pcm = b->d_pcm;
+    const unsigned long long *plan = (const unsigned long long *)b->d_plan;
+    A.clip_off = plan;
+    A.clip_nsf = plan + b->n_clips;
+    A.clip_frame0 = plan + 2 * b->n_clips;
+    A.out_off = plan + 3 * b->n_clips;
+    A.clip_hops = b->d_hops;
+    A.nch = b->ch;
+    A.n_clips = (int)b->n_clips;
+    A.total_frames = b->total_frames;
+    A.max_hops = 0;
+    for (auto h : b->hops) A.max_hops = h > A.max_hops ? h : A.max_hops;
+    A.out = b->d_out;
+    A.frame_size = b->d_frame_size;
+    A.clip_bytes = (unsigned long long *)b->d_clip_bytes;
+    A.a_t = b->d_at;
+    A.bmax_t = b->d_bmax;
+    A.coef_t = (float4 *)b->d_coef;
+    A.s_prev_out = b->d_sprev;
+    A.s_prev = b->d_sprev;
+    A.slots = b->d_slots;
+    A.slot_bytes = lossy_slot_bytes(b->ch);
+    A.frame_off = (unsigned long long *)b->d_frame_off;
+    A.dbg_coeffs = b->d_dbg_coeffs;
+    A.dbg_q = b->d_dbg_q;
+    A.dbg_sfw = b->d_dbg_sfw;
+    A.in_coeffs = b->d_in_coeffs;
+    A.exact = lossy_exact(b->exact != 0, b->ts->dev);
+    A.dbg_stamps = b->d_stamps;
+    A.next_clip = b->d_next;
+    A.n_cus = b->ctx->prop.multiProcessorCount - (b->ctx->reserve_cus > 0 ? b->ctx->reserve_cus : 0);
+    return A;
+}
+
+static int batch_encode_launch(flo_batch *b) {
+    flo_ctx *c = b->ctx;
+    if (!b->n_clips) return FLO_OK;
+    if (b->mode == FLO_MODE_LOSSLESS) {
+        std::string err;
+        int rc = lossless_encode_launch(b->ll, c->stream, c->profile ? 1 : 0, err);
+        return rc == 0 ? FLO_OK : fail(c, FLO_ERR_DEVICE, "lossless encode: " + err);
+    }
+    if (!b->total_frames) return FLO_OK;
+    // a caller who wrote all n_interleaved floats through flo_batch_clip_device_ptr left a partial sample-frame in the
+    // zero padding behind the clip: it is not part of the clip (encoder.rs:174)
+    for (size_t i = 0; i < b->n_clips; i++) {
+        const uint64_t part = b->n_il[i] % b->ch;
+        if (part) HIPCHK(c, hipMemsetAsync(b->d_pcm + b->clip_off[i] + b->clip_nsf[i] * b->ch, 0, part * sizeof(float), c->stream));
+    }
+    const LossyPlan &P = b->plan;
+    unsigned max_frames = 0;
+    for (auto h : b->hops) max_frames = h > max_frames ? h : max_frames;
+    const FinishPlan fin = plan_finish(b->n_clips, max_frames, P.crc_ready);
+    int rc;
+    b->sizes_queued = false;
+    if (P.form == LossyForm::Chain2q) {   // stereo: one lock-step transform wave + one quantiser-and-packer wave per clip
+#ifdef FLO_STAMPS
+        if (!b->d_stamps) HIPCHK(c, pool_alloc(&b->d_stamps, b->n_clips * b->ch * 16 * 8));
+#endif
+        LossyArgs A = make_args(b);
+        // The batch-wide counters of the persistent workgroups live in the set of this launch's epoch parity, zeroed by
+        // the launch before (or at creation). Many clips: the CRC in the launch's idle tail (lossy_kernels.hip,
+        // tail_crc), which finish_files then takes.
+        const uint32_t epoch = b->epoch + 1 ? b->epoch + 1 : 2;   // (never 0; the parity alternates)
+        A.next_clip = b->d_next + 4 * (epoch & 1u);
+        A.clear_next = b->d_next + 4 * ((epoch & 1u) ^ 1u);
+        A.epoch = epoch;
+        if (P.crc_ready) {
+            const size_t n = b->n_clips;
+            if (!b->d_crc_ready) {
+                HIPCHK(c, pool_alloc(&b->d_crc_ready, n * 4));
+                HIPCHK(c, hipMemsetAsync(b->d_crc_ready, 0, n * 4, c->stream));
+            }
+            if (!b->d_done_q) {
+                HIPCHK(c, pool_alloc(&b->d_done_q, n * 8));
+                HIPCHK(c, hipMemsetAsync(b->d_done_q, 0, n * 8, c->stream));
+            }
+            if (!(A.crc_tab = crc_device_tables())) return fail(c, FLO_ERR_DEVICE, "CRC tables");
+            if (P.tail_crc) A.crc_ready = b->d_crc_ready;
+            A.done_q = b->d_done_q;
+            A.part_reg = b->d_part;
+            A.parts = fin.parts;
+        }
+        rc = timed_launch(c, "lossy_chain2q", [&] { return launch_lossy_chain2q(A, P, c->stream); });
+        if (rc == FLO_OK) b->epoch = epoch;   // (a launch that did not run zeroed nothing: its epoch is used again)
+    } else if (P.form == LossyForm::Chain) {
+#ifdef FLO_STAMPS
+        if (!b->d_stamps) HIPCHK(c, pool_alloc(&b->d_stamps, b->n_clips * b->ch * 16 * 8));
+#endif
+        LossyArgs A = make_args(b);
+        rc = timed_launch(c, "lossy_chain", [&] { return launch_lossy_chain(A, P, c->stream); });
+    } else {   // frame-parallel form
+        // allocated by flo_batch_create when this form is what auto selects; only a forced form allocates here
+        int arc = alloc_frame_scratch(b, P);
+        if (arc != FLO_OK) return arc;
+        LossyArgs A = make_args(b);
+        if ((rc = timed_launch(c, "lossy_bands", [&] { return launch_lossy_frames_pass(A, P.pass1, c->stream); })) != FLO_OK) return rc;
+        if (P.scan() && (rc = timed_launch(c, "lossy_scan", [&] { return launch_lossy_scan(A, c->stream); })) != FLO_OK) return rc;
+        if ((rc = timed_launch(c, "lossy_frames", [&] { return launch_lossy_frames_pass(A, P.pass2, c->stream); })) != FLO_OK) return rc;
+        rc = timed_launch(c, "lossy_compact", [&] { return launch_lossy_compact(A, P.compact, c->stream); });
+    }
+    if (rc != FLO_OK) return rc;
+    // header, TOC and CRC32 of every clip, in front of its DATA chunk (writer.rs:132-224; encoder.rs:229-238 parameters)
+    FinishArgs F{};
+    F.out = b->d_out;
+    F.data_off = (const unsigned long long *)(b->d_plan + 3 * b->n_clips);
+    F.clip_bytes = (const unsigned long long *)b->d_clip_bytes;
+    F.clip_frame0 = (const unsigned long long *)(b->d_plan + 2 * b->n_clips);
+    F.clip_frames = b->d_hops;
+    F.frame_size = b->d_frame_size;
+    F.frame_samples = nullptr;
+    F.const_samples = 1024;
+    F.sample_rate = b->sr;
+    F.flags = (unsigned short)(0x01 | ((unsigned)b->ts->host.q_level << 8));
+    F.channels = b->ch;
+    F.bit_depth = 16;
+    F.level = 5;
+    F.n_clips = (int)b->n_clips;
+    F.crc_out = b->d_crc;
+    F.part_reg = b->d_part;
+    if (P.crc_ready) {
+        F.crc_ready = b->d_crc_ready;
+        F.epoch = b->epoch;
+    }
+    F.max_frames = max_frames;
+    if ((rc = timed_launch(c, "finish_files", [&] { return launch_finish_files(F, fin, c->stream); })) != FLO_OK) return rc;
+    if (P.crc_ready) {   // the sizes come back behind finish_files: flo_batch_sync waits once and copies nothing from the device
+        if (!b->pin_sizes) {
+            std::string perr;
+            if (!(b->pin_sizes = (uint64_t *)stager_pinned_get(c->stager, b->n_clips * 8, perr))) return fail(c, FLO_ERR_NOMEM, perr);
+        }
+        HIPCHK(c, hipMemcpyAsync(b->pin_sizes, b->d_clip_bytes, b->n_clips * 8, hipMemcpyDeviceToHost, c->stream));
+        b->sizes_queued = true;
+    }
+    return FLO_OK;
+}
+
+extern "C" int flo_batch_encode(flo_batch *b, int which) {
+    if (!b) return FLO_ERR_ARG;
+    flo_ctx *c = b->ctx;
+    if (which < 0 || which > 5) return fail(c, FLO_ERR_ARG, "unknown kernel form");
+    HIPCHK(c, hipSetDevice(c->device));
+    // "encoded" is set only once every launch of this call has been accepted: after a failed encode, sync / fetch /
+    // pack refuse with FLO_ERR_STATE instead of handing out stale or partial bytes
+    b->encoded = false;
+    b->synced = false;
+    if (b->mode == FLO_MODE_LOSSY) b->plan = lossy_plan(b, which, c->force_path);
+    int erc = batch_encode_launch(b);
+    b->encoded = erc == FLO_OK;
+    b->encode_failed = erc != FLO_OK;
+    return erc;
+}
+
+// done = nullptr: wait for the context's stream; else wait for that event only (recorded behind the batch's encode):
+// the pipeline of flo_encode_batch must not wait for the NEXT chunk's work that is already queued on the stream
+static int batch_sync_impl(flo_batch *b, hipEvent_t done) {
+    flo_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (done) HIPCHK(c, hipEventSynchronize(done));
+    else HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!b->encoded && b->encode_failed) return fail(c, FLO_ERR_STATE, "the last flo_batch_encode on this batch failed");
+    if (b->encoded && !b->synced) {
+        if (b->mode == FLO_MODE_LOSSY) {
+            // only the per-clip sizes come back; frame sizes stay on the device (the TOC is written there) and are
+            // fetched on demand by the few host paths that want them
+            b->h_clip_bytes.assign(b->n_clips, 0);
+            b->h_frame_size.clear();
+            if (b->sizes_queued) {   // (copied behind finish_files, on the stream this call has waited for)
+                memcpy(b->h_clip_bytes.data(), b->pin_sizes, b->n_clips * 8);
+            } else if (b->n_clips && b->total_frames) {
+                if (done && c->down_stream) {   // pipeline: other streams are busy, a synchronous copy would queue behind them
+                    HIPCHK(c, hipMemcpyAsync(b->h_clip_bytes.data(), b->d_clip_bytes, b->n_clips * 8, hipMemcpyDeviceToHost, c->down_stream));
+                    HIPCHK(c, hipStreamSynchronize(c->down_stream));
+                } else {
+                    HIPCHK(c, hipMemcpy(b->h_clip_bytes.data(), b->d_clip_bytes, b->n_clips * 8, hipMemcpyDeviceToHost));
+                }
+            }
+            for (size_t i = 0; i < b->n_clips; i++)
+                if (b->h_clip_bytes[i] > b->out_cap[i]) return fail(c, FLO_ERR_DEVICE, "bitstream overran its buffer");
+#ifdef FLO_TAIL_STATS   // diagnostic builds: how many clips' CRC the chain encode's tail computed, how many finish_files did
+            if (b->sizes_queued) {
+                std::vector<uint32_t> ready(b->n_clips);
+                HIPCHK(c, hipMemcpy(ready.data(), b->d_crc_ready, b->n_clips * 4, hipMemcpyDeviceToHost));
+                size_t tail = 0;
+                for (uint32_t v : ready) tail += v == b->epoch;
+                fprintf(stderr, "[tail] clips %zu: CRC in the encode's tail %zu, in finish_files %zu\n", b->n_clips, tail, b->n_clips - tail);
+            }
+#endif
+#ifdef FLO_STAMPS
+            if (b->d_stamps) {
+                std::vector<unsigned long long> st(b->n_clips * b->ch * 16);
+                HIPCHK(c, hipMemcpy(st.data(), b->d_stamps, st.size() * 8, hipMemcpyDeviceToHost));
+                double sum[14] = {0};
+                for (size_t w = 0; w < b->n_clips * b->ch; w++)
+                    for (int i = 0; i < 14; i++) sum[i] += (double)st[w * 16 + i];
+                double frames = (double)b->total_frames * b->ch;
+                if (b->plan.form == LossyForm::Chain2q) {   // lock-step form: wave 0 = transform, wave 1 = packer
+                    double t[14] = {0}, p[14] = {0};
+                    for (size_t k = 0; k < b->n_clips; k++)
+                        for (int i = 0; i < 14; i++) { t[i] += (double)st[(2 * k) * 16 + i]; p[i] += (double)st[(2 * k + 1) * 16 + i]; }
+                    static const char *tn[] = {"fold", "prefetch", "fft", "postrot", "bandstats", "mask", "quant", "wait-consumed", "handover"};
+                    static const char *pn[] = {"wait-ready", "read/quant", "pack0", "pack1", "flush", "wait-ts"};
+                    fprintf(stderr, "[stamps2x] ticks (10 ns) per stereo frame | T:");
+                    double tt = 0, pt = 0;
+                    for (int i = 0; i < 9; i++) { fprintf(stderr, " %s=%.1f", tn[i], t[i] / b->total_frames); tt += t[i]; }
+                    fprintf(stderr, " total=%.1f | P:", tt / b->total_frames);
+                    for (int i = 0; i < 6; i++) { fprintf(stderr, " %s=%.1f", pn[i], p[i] / b->total_frames); pt += p[i]; }
+                    fprintf(stderr, " total=%.1f item-form declined %.4f of channel-frames", pt / b->total_frames, p[6] / (2.0 * b->total_frames));
+                    fprintf(stderr, " | T waits>1000: %.2f%% of frames, %.0f cyc/frame avg; >5000: %.2f%%, %.0f | P busy>12000: %.2f%%, %.0f; >20000: %.2f%%, %.0f\n",
+                            100 * t[10] / b->total_frames, t[9] / b->total_frames, 100 * t[12] / b->total_frames, t[11] / b->total_frames,
+                            100 * p[10] / b->total_frames, p[9] / b->total_frames, 100 * p[12] / b->total_frames, p[11] / b->total_frames);
+                    // per clip: the packer's busy ticks per frame against the transform's (who waits for whom is a property
+                    // of the clip's content): deciles over the clips
+                    std::vector<double> pb(b->n_clips), tb(b->n_clips);
+                    for (size_t k = 0; k < b->n_clips; k++) {
+                        const double fr = (double)b->hops[k] > 0 ? (double)b->hops[k] : 1.0;
+                        double tq = 0, pq = 0;
+                        for (int i = 0; i < 9; i++) if (i != 7) tq += (double)st[(2 * k) * 16 + i];
+                        for (int i = 1; i < 5; i++) pq += (double)st[(2 * k + 1) * 16 + i];
+                        tb[k] = tq / fr; pb[k] = pq / fr;
+                    }
+                    if (const char *dump = getenv("FLO_STAMPS_DUMP")) {   // raw per-clip records for diag/stamps_clips.py
+                        if (FILE *fh = fopen(dump, "wb")) {
+                            fwrite(st.data(), 8, st.size(), fh);
+                            fclose(fh);
+                        }
+                    }
+                    std::vector<double> ps = pb, ts = tb;
+                    std::sort(ps.begin(), ps.end()); std::sort(ts.begin(), ts.end());
+                    fprintf(stderr, "[stamps2x] per-clip busy ticks per frame, deciles | P:");
+                    for (int d = 0; d <= 10; d++) fprintf(stderr, " %.0f", ps[std::min(b->n_clips - 1, (size_t)(d * (b->n_clips - 1) / 10))]);
+                    fprintf(stderr, " | T:");
+                    for (int d = 0; d <= 10; d++) fprintf(stderr, " %.0f", ts[std::min(b->n_clips - 1, (size_t)(d * (b->n_clips - 1) / 10))]);
+                    size_t pbound = 0;
+                    for (size_t k = 0; k < b->n_clips; k++) pbound += pb[k] > tb[k];
+                    fprintf(stderr, " | clips whose packer is busier than their transform: %.1f%%\n", 100.0 * pbound / b->n_clips);
+                }
+                static const char *nm[] = {"wait-loads+fold", "issue-loads", "fft", "postrot", "analyse(bands,psy,quant,plan)",
+                                           "sync-tot", "emit", "sync-emit", "flush", "sync-tail"};
+                fprintf(stderr, "[stamps] s_memtime ticks (100 MHz) per frame-channel:");
+                for (int i = 0; i < 10; i++) fprintf(stderr, " %s=%.0f", nm[i], sum[i] / frames);
+                fprintf(stderr, " | inside analyse: bands=%.0f psy=%.0f quantise=%.0f (plan = analyse rest)", sum[10] / frames, sum[11] / frames, sum[12] / frames);
+                fprintf(stderr, "\n");
+            }
+#endif
+        } else {
+            std::string err;
+            if (lossless_collect(b->ll, err) != 0) return fail(c, FLO_ERR_DEVICE, "lossless collect: " + err);
+        }
+        b->synced = true;
+    }
+    return FLO_OK;
+}
+
+extern "C" int flo_batch_sync(flo_batch *b) {
+    if (!b) return FLO_ERR_ARG;
+    return batch_sync_impl(b, nullptr);
+}
+
+extern "C" int flo_batch_data_bytes(flo_batch *b, uint64_t *total) {
+    if (!b || !total) return FLO_ERR_ARG;
+    if (!b->synced) return fail(b->ctx, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
+    uint64_t t = 0;
+    if (b->mode == FLO_MODE_LOSSY)
+        for (auto v : b->h_clip_bytes) t += v;
+    else
+        t = lossless_total_bytes(b->ll);
+    *total = t;
+    return FLO_OK;
+}
+
+extern "C" int flo_batch_device_streams(flo_batch *b, const uint8_t **base, const uint64_t **offsets,
+                                        const uint64_t **sizes) {
+    if (!b) return FLO_ERR_ARG;
+    if (!b->synced) return fail(b->ctx, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
+    if (b->mode == FLO_MODE_LOSSY) {
+        if (base) *base = b->d_out;
+        if (offsets) *offsets = b->out_off.data();
+        if (sizes) *sizes = b->h_clip_bytes.data();
+        return FLO_OK;
+    }
+    return lossless_device_streams(b->ll, base, offsets, sizes) == 0 ? FLO_OK : FLO_ERR_STATE;
+}
+
+// Finished files (header + TOC + DATA, no META) as they sit in HBM after flo_batch_sync.
+extern "C" int flo_batch_device_files(flo_batch *b, const uint8_t **base, const uint64_t **offsets, const uint64_t **sizes) {
+    if (!b) return FLO_ERR_ARG;
+    if (!b->synced) return fail(b->ctx, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
+    if (b->mode == FLO_MODE_LOSSY) {
+        if (b->h_file_bytes.size() != b->n_clips) b->h_file_bytes.resize(b->n_clips);
+        for (size_t i = 0; i < b->n_clips; i++) b->h_file_bytes[i] = 74 + 20 * (uint64_t)b->hops[i] + b->h_clip_bytes[i];
+        if (base) *base = b->d_out;
+        if (offsets) *offsets = b->file_off.data();
+        if (sizes) *sizes = b->h_file_bytes.data();
+        return FLO_OK;
+    }
+    return lossless_device_files(b->ll, base, offsets, sizes) == 0 ? FLO_OK : FLO_ERR_STATE;
+}
+
+// Pack every clip's DATA chunk (files = false) or finished .flo file without META (files = true) into dst (device
+// memory owned by the caller, e.g. a torch tensor), clip i at offsets[i] (16-byte aligned, offsets[n_clips] = total).
+// Asynchronous on the ctx stream.
+static int pack_impl(flo_batch *b, bool files, void *dst_device, size_t dst_cap, uint64_t *offsets) {
+    if (!b || !offsets || (!dst_device && dst_cap)) return FLO_ERR_ARG;
+    flo_ctx *c = b->ctx;
+    if (!b->synced) return fail(c, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint8_t *base;
+    const uint64_t *offs, *sizes;
+    int rc = files ? flo_batch_device_files(b, &base, &offs, &sizes) : flo_batch_device_streams(b, &base, &offs, &sizes);
+    if (rc != FLO_OK) return rc;
+    uint64_t pos = 0;
+    for (size_t i = 0; i < b->n_clips; i++) {
+        offsets[i] = pos;
+        pos += (sizes[i] + 15) & ~(uint64_t)15;
+    }
+    offsets[b->n_clips] = pos;
+    if (pos > dst_cap) return fail(c, FLO_ERR_ARG, "packed stream buffer too small");
+    if (!b->n_clips || !pos) return FLO_OK;
+    if (!b->d_pack_plan) {
+        HIPCHK(c, pool_alloc(&b->d_pack_plan, 3 * b->n_clips * 8));
+        HIPCHK(c, hipEventCreateWithFlags(&b->ev_pack_plan, hipEventDisableTiming));
+    } else {
+        HIPCHK(c, hipEventSynchronize(b->ev_pack_plan));   // the previous pack's copy has read the plan (long ago)
+    }
+    std::string perr;
+    if (!b->pin_plan && !(b->pin_plan = (uint64_t *)stager_pinned_get(c->stager, (8 * b->n_clips + 8) * 8, perr)))
+        return fail(c, FLO_ERR_NOMEM, perr);
+    uint64_t *plan = b->pin_plan + 5 * b->n_clips;   // behind the clip plan (4 n) and the hops (n u32)
+    for (size_t i = 0; i < b->n_clips; i++) {
+        plan[i] = offs[i];
+        plan[b->n_clips + i] = offsets[i];
+        plan[2 * b->n_clips + i] = sizes[i];
+    }
+    HIPCHK(c, hipMemcpyAsync(b->d_pack_plan, plan, 3 * b->n_clips * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(b->ev_pack_plan, c->stream));
+    const unsigned long long *dp = (const unsigned long long *)b->d_pack_plan;
+    return timed_launch(c, "pack_streams", [&] {
+        return launch_pack_streams(base, dp, dp + b->n_clips, dp + 2 * b->n_clips, (int)b->n_clips, (uint8_t *)dst_device, c->stream);
+    });
+}
+extern "C" int flo_batch_pack_streams(flo_batch *b, void *dst_device, size_t dst_cap, uint64_t *offsets) {
+    return pack_impl(b, false, dst_device, dst_cap, offsets);
+}
+extern "C" int flo_batch_pack_files(flo_batch *b, void *dst_device, size_t dst_cap, uint64_t *offsets) {
+    return pack_impl(b, true, dst_device, dst_cap, offsets);
+}
+
+extern "C" int flo_batch_fetch(flo_batch *b, size_t clip, const uint8_t *meta, size_t meta_len, uint8_t **out,
+                               size_t *out_len) {
+    if (!b || clip >= b->n_clips || !out || !out_len || (meta_len && !meta)) return FLO_ERR_ARG;
+    flo_ctx *c = b->ctx;
+    if (!b->synced) return fail(c, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (b->mode == FLO_MODE_LOSSLESS) {
+        std::string err;
+        int rc = lossless_fetch(b->ll, clip, b->bit_depth, meta, meta_len, out, out_len, err);
+        return rc == 0 ? FLO_OK : fail(c, FLO_ERR_DEVICE, "lossless fetch: " + err);
+    }
+    // the file was finished on the device: copy it, append META and patch meta_size (header bytes 62..69)
+    const size_t head = 74 + 20 * (size_t)b->hops[clip];
+    const size_t n = head + (size_t)b->h_clip_bytes[clip];
+    uint8_t *f = (uint8_t *)malloc(n + meta_len ? n + meta_len : 1);
+    if (!f) return fail(c, FLO_ERR_NOMEM, "malloc failed");
+    hipError_t e = hipMemcpy(f, b->d_out + b->file_off[clip], n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        free(f);
+        return fail(c, FLO_ERR_DEVICE, std::string("fetch: ") + hipGetErrorString(e));
+    }
+    if (meta_len) memcpy(f + n, meta, meta_len);
+    for (int i = 0; i < 8; i++) f[62 + i] = (uint8_t)((uint64_t)meta_len >> (8 * i));
+    *out = f;
+    *out_len = n + meta_len;
+    return FLO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ one-shot API
+int batch_upload_all(flo_batch *b, const float *const *pcm, hipStream_t stream) {
+    flo_ctx *c = b->ctx;
+    int rc = ctx_stager(c);
+    if (rc != FLO_OK) return rc;
+    std::vector<UploadSeg> segs;
+    segs.reserve(b->n_clips);
+    for (size_t i = 0; i < b->n_clips; i++) {
+        // a trailing partial sample-frame is not part of the clip (encoder.rs:174): it must not land in the zero padding
+        const uint64_t n_copy = b->mode == FLO_MODE_LOSSY ? b->clip_nsf[i] * b->ch : b->n_il[i];
+        if (n_copy) segs.push_back({b->d_pcm + b->clip_off[i], pcm[i], n_copy * sizeof(float)});
+        b->keep_tail(i, pcm[i]);
+    }
+    std::string err;
+    if (stager_upload(c->stager, segs, stream ? stream : c->stream, err) != 0) return fail(c, FLO_ERR_DEVICE, err);
+    b->encoded = b->synced = b->encode_failed = false;
+    return FLO_OK;
+}
+
+// The throughput entry point on host buffers, as a three-stage pipeline over chunks of clips: while chunk k is being
+// encoded, the copy threads and the upload stream bring in chunk k + 1 and the download stream takes the finished files
+// of chunk k - 1 out (one packed pinned transfer per chunk). The bytes are those of n_clips separate calls.
+extern "C" int flo_encode_batch(flo_ctx *c, int mode, size_t n_clips, const float *const *pcm, const size_t *n_il,
+                                uint32_t sr, uint8_t ch, float qol, uint8_t **outs, size_t *out_lens) {
+    if (!c || (n_clips && (!pcm || !n_il || !outs || !out_lens))) return FLO_ERR_ARG;
+    for (size_t i = 0; i < n_clips; i++)
+        if (n_il[i] && !pcm[i]) return FLO_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ctx_stager(c);
+    if (rc != FLO_OK) return rc;
+    for (size_t i = 0; i < n_clips; i++) outs[i] = nullptr;
+    const bool trace = getenv("FLO_TRACE") != nullptr;
+    auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = tnow();
+    // chunks of about 48 MB of PCM (at least one clip each)
+    struct Chunk {
+        size_t first = 0, count = 0;
+        flo_batch *b = nullptr;
+        uint8_t *d_packed = nullptr;
+        uint8_t *host = nullptr;
+        std::vector<uint64_t> po;
+        hipEvent_t up = nullptr, enc = nullptr;
+        bool encoded = false, taken = false;
+    };
+    std::vector<Chunk> chunks;
+    {
+        const uint64_t target = (uint64_t)48 << 20;
+        size_t i = 0;
+        while (i < n_clips) {
+            Chunk k;
+            k.first = i;
+            uint64_t bytes = 0;
+            while (i < n_clips && (k.count == 0 || bytes + n_il[i] * 4 <= target)) {
+                bytes += (uint64_t)n_il[i] * 4;
+                i++;
+                k.count++;
+            }
+            chunks.push_back(k);
+        }
+    }
+    auto cleanup = [&](int code) {
+        hipStreamSynchronize(c->up_stream);
+        hipStreamSynchronize(c->stream);
+        hipStreamSynchronize(c->down_stream);
+        for (Chunk &k : chunks) {
+            if (k.d_packed) pool_free(k.d_packed);
+            if (k.host) stager_pinned_put(c->stager, k.host);
+            if (k.up) hipEventDestroy(k.up);
+            if (k.enc) hipEventDestroy(k.enc);
+            if (k.b) flo_batch_destroy(k.b);
+        }
+        if (code != FLO_OK)
+            for (size_t i = 0; i < n_clips; i++) {
+                free(outs[i]);
+                outs[i] = nullptr;
+            }
+        return code;
+    };
+    // stage 3 for one chunk: sizes, pack, download (asynchronous on the download stream)
+    auto take = [&](Chunk &k) -> int {
+        int r = batch_sync_impl(k.b, mode == FLO_MODE_LOSSY ? k.enc : nullptr);
+        if (r != FLO_OK) return r;
+        const uint8_t *base;
+        const uint64_t *offs, *sizes;
+        if ((r = flo_batch_device_files(k.b, &base, &offs, &sizes)) != FLO_OK) return r;
+        uint64_t need = 16;
+        for (size_t i = 0; i < k.count; i++) need += (sizes[i] + 15) & ~(uint64_t)15;
+        if (pool_alloc(&k.d_packed, need) != hipSuccess) return fail(c, FLO_ERR_NOMEM, "packed output buffer");
+        k.po.resize(k.count + 1);
+        if ((r = flo_batch_pack_files(k.b, k.d_packed, need, k.po.data())) != FLO_OK) return r;
+        std::string err;
+        k.host = (uint8_t *)stager_pinned_get(c->stager, need, err);
+        if (!k.host) return fail(c, FLO_ERR_NOMEM, err);
+        HIPCHK(c, hipEventRecord(k.up, c->stream));   // (the upload event has served its purpose: reused for "packed")
+        HIPCHK(c, hipStreamWaitEvent(c->down_stream, k.up, 0));
+        HIPCHK(c, hipMemcpyAsync(k.host, k.d_packed, k.po[k.count], hipMemcpyDeviceToHost, c->down_stream));
+        for (size_t i = 0; i < k.count; i++) out_lens[k.first + i] = sizes[i];
+        k.taken = true;
+        return FLO_OK;
+    };
+    for (size_t ci = 0; ci < chunks.size(); ci++) {
+        Chunk &k = chunks[ci];
+        const double ta = tnow();
+        if ((rc = flo_batch_create(c, mode, k.count, n_il + k.first, sr, ch, qol, &k.b)) != FLO_OK) return cleanup(rc);
+        const double tb = tnow();
+        if (hipEventCreateWithFlags(&k.up, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&k.enc, hipEventDisableTiming) != hipSuccess)
+            return cleanup(fail(c, FLO_ERR_DEVICE, "hipEventCreate"));
+        // (errors leave through cleanup(): the chunks' batches, pinned blocks and events are released, outs[] stays empty)
+        auto ordered = [&](hipError_t e, const char *what) { return e == hipSuccess ? FLO_OK : fail(c, FLO_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
+        // the batch's padding memset ran on the ctx stream: the uploads must land behind it
+        if ((rc = ordered(hipEventRecord(k.enc, c->stream), "hipEventRecord")) != FLO_OK) return cleanup(rc);
+        if ((rc = ordered(hipStreamWaitEvent(c->up_stream, k.enc, 0), "hipStreamWaitEvent")) != FLO_OK) return cleanup(rc);
+        if ((rc = batch_upload_all(k.b, pcm + k.first, c->up_stream)) != FLO_OK) return cleanup(rc);
+        const double tc = tnow();
+        if ((rc = ordered(hipEventRecord(k.up, c->up_stream), "hipEventRecord")) != FLO_OK) return cleanup(rc);
+        if ((rc = ordered(hipStreamWaitEvent(c->stream, k.up, 0), "hipStreamWaitEvent")) != FLO_OK) return cleanup(rc);
+        if ((rc = flo_batch_encode(k.b, 0)) != FLO_OK) return cleanup(rc);
+        if ((rc = ordered(hipEventRecord(k.enc, c->stream), "hipEventRecord")) != FLO_OK) return cleanup(rc);   // this chunk's files are finished behind this point
+        k.encoded = true;
+        const double td = tnow();
+        if (ci > 0 && (rc = take(chunks[ci - 1])) != FLO_OK) return cleanup(rc);
+        if (trace) fprintf(stderr, "  chunk %zu: create %.3f upload %.3f encode-enqueue %.3f take(prev) %.3f ms\n", ci, (tb - ta) * 1e3, (tc - tb) * 1e3, (td - tc) * 1e3, (tnow() - td) * 1e3);
+    }
+    if (!chunks.empty() && (rc = take(chunks.back())) != FLO_OK) return cleanup(rc);
+    if (hipStreamSynchronize(c->down_stream) != hipSuccess) return cleanup(fail(c, FLO_ERR_DEVICE, "download of the finished files failed"));
+    const double t1 = tnow();
+    // cut the packed transfers into the per-clip buffers the caller owns (the copy threads share the work)
+    std::vector<UploadSeg> cuts;
+    cuts.reserve(n_clips);
+    for (Chunk &k : chunks)
+        for (size_t i = 0; i < k.count; i++) {
+            const size_t g = k.first + i;
+            outs[g] = (uint8_t *)malloc(out_lens[g] ? out_lens[g] : 1);
+            if (!outs[g]) return cleanup(fail(c, FLO_ERR_NOMEM, "malloc failed"));
+            cuts.push_back({outs[g], k.host + k.po[i], out_lens[g]});
+        }
+    stager_memcpy_many(c->stager, cuts);
+    if (trace) fprintf(stderr, "[flo_encode_batch] %zu chunks: pipeline %.3f ms, cut %.3f ms\n", chunks.size(), (t1 - t0) * 1e3, (tnow() - t1) * 1e3);
+    return cleanup(FLO_OK);
+}
+
+static int encode_one(flo_ctx *c, int mode, const float *pcm, size_t n, uint32_t sr, uint8_t ch, float qol,
+                      uint8_t bit_depth, const uint8_t *meta, size_t meta_len, uint8_t **out, size_t *out_len) {
+    if (!c || !out || !out_len || (n && !pcm) || (meta_len && !meta)) return FLO_ERR_ARG;
+    static const bool trace = getenv("FLO_TRACE") != nullptr;
+    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = trace ? now() : 0;
+    flo_batch *b = nullptr;
+    int rc = flo_batch_create(c, mode, 1, &n, sr, ch, qol, &b);
+    if (rc != FLO_OK) return rc;
+    b->bit_depth = bit_depth;
+    const double t1 = trace ? now() : 0;
+    {
+        const float *one[1] = {pcm};
+        rc = batch_upload_all(b, one);
+    }
+    const double t2 = trace ? now() : 0;
+    if (rc == FLO_OK) rc = flo_batch_encode(b, 0);
+    const double t3 = trace ? now() : 0;
+    double t4 = t3;
+    bool fetched = false;
+    if (rc == FLO_OK && mode == FLO_MODE_LOSSY && b->total_frames && c->stager) {
+        // ONE round trip behind the kernels instead of two (sizes, then the file): the size word and a generous guess of the
+        // file (768 bytes per frame; q = 0.55 makes about 420) come back together into pinned memory; a longer file fetches
+        // its remainder afterwards
+        const size_t head = 74 + 20 * (size_t)b->hops[0];
+        size_t est = head + 768 * (size_t)b->hops[0];
+        if (est > head + (size_t)b->out_cap[0]) est = head + (size_t)b->out_cap[0];
+        std::string err;
+        uint8_t *pin = (uint8_t *)stager_pinned_get(c->stager, 16 + est, err);
+        if (pin) {
+            hipError_t e = hipMemcpyAsync(pin, b->d_clip_bytes, 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(pin + 16, b->d_out + b->file_off[0], est, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            t4 = trace ? now() : 0;
+            if (e != hipSuccess) {
+                rc = fail(c, FLO_ERR_DEVICE, std::string("one-shot fetch: ") + hipGetErrorString(e));
+            } else if (!b->encoded) {
+                rc = fail(c, FLO_ERR_STATE, "the last flo_batch_encode on this batch failed");
+            } else {
+                uint64_t sz;
+                memcpy(&sz, pin, 8);
+                if (sz > b->out_cap[0]) {
+                    rc = fail(c, FLO_ERR_DEVICE, "bitstream overran its buffer");
+                } else {
+                    b->h_clip_bytes.assign(1, sz);
+                    b->h_frame_size.clear();
+                    b->synced = true;
+                    const size_t n = head + (size_t)sz;
+                    uint8_t *f = (uint8_t *)malloc(n + meta_len ? n + meta_len : 1);
+                    if (!f) {
+                        rc = fail(c, FLO_ERR_NOMEM, "malloc failed");
+                    } else {
+                        memcpy(f, pin + 16, n < est ? n : est);
+                        if (n > est) e = hipMemcpy(f + est, b->d_out + b->file_off[0] + est, n - est, hipMemcpyDeviceToHost);
+                        if (e != hipSuccess) {
+                            free(f);
+                            rc = fail(c, FLO_ERR_DEVICE, std::string("one-shot fetch: ") + hipGetErrorString(e));
+                        } else {
+                            if (meta_len) memcpy(f + n, meta, meta_len);
+                            for (int i = 0; i < 8; i++) f[62 + i] = (uint8_t)((uint64_t)meta_len >> (8 * i));   // meta_size
+                            *out = f;
+                            *out_len = n + meta_len;
+                        }
+                    }
+                }
+            }
+            stager_pinned_put(c->stager, pin);
+            fetched = true;
+        }
+    }
+    if (!fetched) {
+        if (rc == FLO_OK) rc = flo_batch_sync(b);
+        t4 = trace ? now() : 0;
+        if (rc == FLO_OK) rc = flo_batch_fetch(b, 0, meta, meta_len, out, out_len);
+    }
+    const double t5 = trace ? now() : 0;
+    flo_batch_destroy(b);
+    if (trace)
+        fprintf(stderr, "[encode_one] create %.1f upload %.1f encode %.1f sync %.1f fetch %.1f destroy %.1f us\n", t1 - t0, t2 - t1,
+                t3 - t2, t4 - t3, t5 - t4, now() - t5);
+    return rc;
+}
+
+extern "C" int flo_encode_lossy(flo_ctx *c, const float *pcm, size_t n, uint32_t sr, uint8_t ch, float quality,
+                                const uint8_t *meta, size_t meta_len, uint8_t **out, size_t *out_len) {
+    return encode_one(c, FLO_MODE_LOSSY, pcm, n, sr, ch, quality, 16, meta, meta_len, out, out_len);
+}
+extern "C" int flo_encode_lossless(flo_ctx *c, const float *pcm, size_t n, uint32_t sr, uint8_t ch, uint8_t bit_depth,
+                                   uint8_t level, const uint8_t *meta, size_t meta_len, uint8_t **out,
+                                   size_t *out_len) {
+    return encode_one(c, FLO_MODE_LOSSLESS, pcm, n, sr, ch, (float)level, bit_depth, meta, meta_len, out, out_len);
+}
+
+extern "C" int flo_batch_set_bit_depth(flo_batch *b, uint8_t bit_depth) {
+    if (!b) return FLO_ERR_ARG;
+    b->bit_depth = bit_depth;   // (echoed into the header like flo_encode_lossless's argument: writer.rs:146)
+    return FLO_OK;
+}

@@ -1,5 +1,6 @@
-// ctx_internal.hpp — the context object and the host helpers that the library's source files share (flo_api.cpp owns
-// the definitions; corpus.cpp uses them). Not part of the C ABI.
+// ctx_internal.hpp — the context object and the host helpers that the library's source files share; every declaration
+// names the file that defines it. Not part of the C ABI. (struct flo_batch: batch_internal.hpp; the scoped device blocks:
+// devmem.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -51,13 +52,16 @@ struct flo_ctx {
     struct LstreamWork *lstream = nullptr;   // flo_stream_encode_ready's device scratch (lstream.cpp; made on first use)
 };
 
+// sets the context's error text and returns `code` (context.cpp)
 int fail(flo_ctx *c, int code, const std::string &msg);
+// the text behind flo_last_create_error: failures that have no context to carry it (context.cpp)
+extern thread_local std::string g_create_err;
 // releases flo_ctx::sdec (sdec.cpp)
 void sdec_work_free(flo_ctx *c);
 // releases flo_ctx::lstream (lstream.cpp)
 void lstream_work_free(flo_ctx *c);
 
-// ---- streaming encoder (flo_stream_*: flo_api.cpp, the lossy stream step and flo_stream_encode_ready: lstream.cpp) --------
+// ---- streaming encoder (flo_stream_*: stream.cpp, the lossy stream step and flo_stream_encode_ready: lstream.cpp) ---------
 struct StreamFrame {
     uint32_t index, timestamp_ms, samples;
     std::vector<uint8_t> data;
@@ -78,42 +82,47 @@ struct flo_stream {
     std::vector<float> mask;   // [ch * 25]: temporal masking level after the last encoded frame
 };
 // the lossless frames of many streams of one (sample rate, channels, bit depth, level): stream items[i].first's next
-// items[i].second complete seconds, in one lossless batch; frames come back in item order (flo_api.cpp)
+// items[i].second complete seconds, in one lossless batch; frames come back in item order (stream.cpp)
 int stream_encode_lossless(flo_ctx *c, const std::vector<std::pair<flo_stream *, size_t>> &items, std::vector<std::vector<uint8_t>> &frames);
-// queue the frames stream_encode_lossless made for `count` seconds of s and drop those seconds from its buffer
+// queue the frames stream_encode_lossless made for `count` seconds of s and drop those seconds from its buffer (stream.cpp)
 void stream_queue_lossless(flo_stream *s, std::vector<std::vector<uint8_t>> &frames, size_t first, size_t count);
+// a lossy stream's share of flo_stream_push, and the end of its input: the trailing frames join the queue (lstream.cpp)
+int lossy_stream_push(flo_stream *s, const float *samples, size_t n);
+int lossy_stream_end(flo_stream *s);
 #define HIPCHK(ctx, expr)                                                                               \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess)                                                                           \
             return fail(ctx, FLO_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));        \
     } while (0)
+// folds every finished profiling bracket (wait: every bracket) into the per-kernel sums (context.cpp)
 int profile_drain(flo_ctx *c, bool wait);
-// the constant tables of one sample rate (made on first use, kept by the context)
+// the constant tables of one sample rate (made on first use, kept by the context; context.cpp)
 int get_tables(flo_ctx *c, uint32_t sr, float quality, TableSet **out);
-// the context's pinned staging ring and copy threads (made on first use)
+// the context's pinned staging ring and copy threads (made on first use; context.cpp)
 int ctx_stager(flo_ctx *c);
 
-// ---- fidelity reports (fidelity.cpp): what flo_api.cpp, which owns batches and the file decode paths, lends them --------
-// A synced batch as the comparison sees it: clip i's source is the batch's device copy, src_frames[i] whole frames at
-// pcm + src_off[i]; dec_frames[i] is what its file decodes to. FLO_ERR_STATE before sync.
-struct FidBatchView {
-    flo_ctx *ctx = nullptr;
-    bool lossy = false;
-    int channels = 0;
-    const float *pcm = nullptr;
-    std::vector<unsigned long long> src_off, src_frames, dec_frames;
-};
-int batch_fidelity_view(flo_batch *b, FidBatchView &v);
-// the fused pass over a synced lossy batch: lossy_decode_kernel<kDecCompare>, clip i against cmp's clip i (stream idle on return)
-int batch_lossy_compare(flo_batch *b, const LossyCmpArgs &cmp);
-// a parsed file whose bytes are at d_bytes: the fused pass of a transform file (one clip), the decode of a lossless one
-// into d_out (its frames' samples x channels floats); both leave the stream idle
+// ---- decode (decode.cpp): the device paths of flo_decode, which the fidelity reports (fidelity.cpp) run as well --------
 namespace flo {
 struct ParsedFile;
 }
-int file_lossy_compare(flo_ctx *c, const ParsedFile &f, const uint8_t *d_bytes, const LossyCmpArgs &cmp);
-int file_lossless_decode(flo_ctx *c, const ParsedFile &f, const uint8_t *d_bytes, float *d_out);
+struct LlWrapperList;   // decode_plan.hpp
+// the transform blobs of a parsed file, in order (decode_transform_file, lib.rs:325-352: frames without channels are skipped)
+void file_transform_blobs(const ParsedFile &f, std::vector<unsigned long long> &blob_off, std::vector<unsigned int> &blob_len);
+// the wrappers of every frame of a parsed lossless file, frame after frame in the output; returns the sample-frames in all
+uint64_t file_ll_wrappers(const ParsedFile &f, LlWrapperList &w);
+// Enqueue the decode of `w` (out_sf sample-frames) on the ctx stream: integers per wrapper into a scratch, then
+// mid/side, interleave and the 1/32767 scale into d_out (f32, nullable) / d_out_i32 (nullable), both out_sf * nch
+// elements. Returns when the kernels have run.
+int ll_decode_device(flo_ctx *c, const LlWrapperList &w, uint64_t out_sf, const uint8_t *d_bytes, int nch, float *d_out, int *d_out_i32);
+// lossy_decode_kernel<kDecWhole> over the clips whose bytes sit at `bytes`: the frame and clip tables and a cleared
+// error word go up, the kernel runs, the error word comes back (the ctx stream is idle on return). FLO_ERR_FORMAT when a
+// frame does not deserialise. With `cmp` (fidelity reports), lossy_decode_kernel<kDecCompare>: clip i is compared with
+// cmp's clip i and nothing is written to `out`.
+int lossy_decode_whole(flo_ctx *c, const TableSet *ts, const uint8_t *bytes, int channels, const std::vector<unsigned long long> &blob_off,
+                       const std::vector<unsigned int> &blob_len, const std::vector<unsigned long long> &clip_frame0,
+                       const std::vector<unsigned int> &clip_frames, const std::vector<unsigned long long> &clip_out,
+                       unsigned max_frames, float *out, const LossyCmpArgs *cmp = nullptr);
 
 // Launch through `launch` on the ctx stream; with profiling on, bracketed by events under `name`.
 template <typename F>

@@ -8,12 +8,12 @@
 // so that the transfer of step k overlaps the encode of step k + 1 and the host never waits for the device per step.
 //
 // The Backend supplies the mechanisms (queues, buffers, collectives). The product instantiates the engine with HIP
-// streams + RCCL (flo_api.cpp: RcclBackend); tests/native/dist_engine_test.cpp instantiates the SAME template with host
+// streams + RCCL (dist.cpp: RcclBackend); tests/native/dist_engine_test.cpp instantiates the SAME template with host
 // memory and sockets and runs it with several ranks on the CPU. Backend concept (all int returns: 0 = ok):
 //   struct Buffer;                                         a growable byte buffer the transfers can address
 //   int  reserve(Buffer &b, size_t need);                  grow b to >= need bytes (may wait for work still using the old one)
-//   int  pack(void *batch, Buffer &dst, uint64_t *bytes);  pack the batch's files into dst on the compute queue (async)
-//   int  payload_bytes(void *batch, uint64_t *need);       upper bound of what pack() writes
+//   int  pack(Batch *batch, Buffer &dst, uint64_t *bytes); pack the batch's files into dst on the compute queue (async)
+//   int  payload_bytes(Batch *batch, uint64_t *need);      upper bound of what pack() writes (Batch: what submit() is given)
 //   int  wait_moved_before_pack(int slot);                 compute queue waits for slot's last transfers (device-side)
 //   int  mark_packed(int slot);                            compute queue: "slot is packed"
 //   int  sizes_exchange(int slot, uint64_t mine);          comm queue: all-gather of one u64 per rank (async) ...
@@ -90,7 +90,8 @@ struct DistEngine {
         return 0;
     }
 
-    int submit(void *batch) {
+    template <class Batch>
+    int submit(Batch *batch) {
         const int s = (int)(submits & 1), prev = s ^ 1;
         // 1. this slot's previous transfers (two submits ago) were posted one submit ago; its send buffer is free once
         //    they have run: the pack waits for that on the device, the host does not

@@ -13,31 +13,16 @@
 #include <string>
 #include <vector>
 
+#include "batch_internal.hpp"
 #include "container.hpp"
-#include "ctx_internal.hpp"
-#include "devpool.hpp"
+#include "decode_plan.hpp"
+#include "devmem.hpp"
 #include "fidelity_kernels.hpp"
 
 static_assert(sizeof(FidTotal) == sizeof(flo_fidelity) && sizeof(FidPublicBlock) == sizeof(flo_fidelity_block),
               "device records mirror the C ABI's");
 
 namespace {
-
-template <class T>
-struct DevBuf {   // one pool block, released when the call returns
-    T *p = nullptr;
-    ~DevBuf() {
-        if (p) pool_free(p);
-    }
-    bool alloc(size_t n) { return pool_alloc(&p, (n ? n : 1) * sizeof(T)) == hipSuccess; }
-};
-// declared behind a call's DevBufs: the stream is idle before they go back to the pool, whichever way the call ends
-struct Quiesce {
-    flo_ctx *c;
-    ~Quiesce() {
-        if (c && c->stream) hipStreamSynchronize(c->stream);
-    }
-};
 
 // FLO_FIDELITY_UNFUSED=1 (read per call): lossy batches decode into scratch and compare behind the decode
 bool unfused() {
@@ -66,7 +51,7 @@ int finish(flo_ctx *c, const FidClipDev *d_cl, size_t n_clips, int ch, const Fid
            flo_fidelity *out, flo_fidelity_block *blocks) {
     DevBuf<FidTotal> d_out;
     DevBuf<FidPublicBlock> d_pub;
-    Quiesce q{c};
+    QuiesceOnExit q(c);
     const size_t n_out = n_clips * (size_t)ch;
     if (!d_out.alloc(n_out) || (blocks && !d_pub.alloc(n_pub * ch))) return fail(c, FLO_ERR_NOMEM, "fidelity records");
     FidTotalsArgs A{};
@@ -103,17 +88,27 @@ int compare_decoded(flo_ctx *c, const float *src, const float *dec, const FidCli
 
 extern "C" int flo_batch_fidelity(flo_batch *b, flo_fidelity *out, flo_fidelity_block *blocks, size_t blocks_cap, uint64_t *block_off) {
     if (!b || !block_off) return FLO_ERR_ARG;
-    FidBatchView v;
-    int rc = batch_fidelity_view(b, v);
-    if (rc != FLO_OK) return rc;
-    flo_ctx *c = v.ctx;
-    const size_t n = v.src_off.size();
-    const int ch = v.channels;
+    flo_ctx *c = b->ctx;
+    if (!b->synced) return fail(c, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
+    // clip i's source is the batch's device copy, clip_nsf[i] whole frames at d_pcm + clip_off[i]; dec_frames: what its file decodes to
+    const size_t n = b->n_clips;
+    const int ch = b->ch;
+    const bool lossy = b->mode == FLO_MODE_LOSSY;
+    int rc;
     std::vector<FidClipDev> cl(n);
     for (size_t i = 0; i < n; i++) {
-        cl[i].src = v.src_off[i];
-        cl[i].src_frames = v.src_frames[i];
-        cl[i].dec_frames = v.dec_frames[i];
+        cl[i].src = b->clip_off[i];
+        cl[i].src_frames = b->clip_nsf[i];
+        if (lossy) cl[i].dec_frames = b->hops[i] > 1 ? (uint64_t)(b->hops[i] - 1) * 1024 : 0;
+    }
+    if (!lossy) {
+        std::vector<LosslessFrameInfo> fr;
+        std::vector<LosslessWrapperInfo> wr;
+        const uint8_t *base = nullptr;
+        std::string err;
+        if (lossless_describe(b->ll, fr, wr, &base, err) != 0) return fail(c, FLO_ERR_STATE, err);
+        for (const LosslessFrameInfo &f : fr)
+            if (f.clip < n) cl[f.clip].dec_frames += f.samples;
     }
     uint64_t dec_blocks = 0;
     const uint64_t n_pub = plan_clips(cl, block_off, dec_blocks);
@@ -124,21 +119,26 @@ extern "C" int flo_batch_fidelity(flo_batch *b, flo_fidelity *out, flo_fidelity_
     DevBuf<FidClipDev> d_cl;
     DevBuf<FidBlockDev> d_blk;
     DevBuf<float> d_dec;
-    Quiesce q{c};
+    QuiesceOnExit q(c);
     if (!d_cl.alloc(n) || !d_blk.alloc(dec_blocks * ch)) return fail(c, FLO_ERR_NOMEM, "fidelity records");
-    if (v.lossy && !unfused()) {
+    if (lossy && !unfused()) {   // the fused pass: lossy_decode_kernel<kDecCompare>, clip i against cmp's clip i
         HIPCHK(c, hipMemcpyAsync(d_cl.p, cl.data(), n * sizeof(FidClipDev), hipMemcpyHostToDevice, c->stream));
-        LossyCmpArgs cmp{v.pcm, d_cl.p, d_blk.p};
-        if ((rc = batch_lossy_compare(b, cmp)) != FLO_OK) return rc;
+        const LossyCmpArgs cmp{b->d_pcm, d_cl.p, d_blk.p};
+        std::vector<unsigned long long> blob_off, c0, co;
+        std::vector<unsigned int> blob_len, cn;
+        uint64_t total = 0;
+        unsigned max_hops = 0;
+        if ((rc = batch_lossy_tables(b, blob_off, blob_len, c0, cn, co, total, max_hops)) != FLO_OK) return rc;
+        if (total && (rc = lossy_decode_whole(c, b->ts, b->d_out, ch, blob_off, blob_len, c0, cn, co, max_hops, nullptr, &cmp)) != FLO_OK) return rc;
     } else {
         uint64_t total = 0;
-        for (size_t i = 0; i < n; i++) total += v.dec_frames[i] * (uint64_t)ch;
+        for (size_t i = 0; i < n; i++) total += cl[i].dec_frames * (uint64_t)ch;
         if (!d_dec.alloc(total)) return fail(c, FLO_ERR_NOMEM, "fidelity decode scratch");
         std::vector<uint64_t> offs(n);
         if ((rc = flo_batch_decode(b, d_dec.p, total, offs.data())) != FLO_OK) return rc;
         for (size_t i = 0; i < n; i++) cl[i].dec = offs[i];
         HIPCHK(c, hipMemcpyAsync(d_cl.p, cl.data(), n * sizeof(FidClipDev), hipMemcpyHostToDevice, c->stream));
-        if ((rc = compare_decoded(c, v.pcm, d_dec.p, d_cl.p, n, ch, d_blk.p, dec_blocks)) != FLO_OK) return rc;
+        if ((rc = compare_decoded(c, b->d_pcm, d_dec.p, d_cl.p, n, ch, d_blk.p, dec_blocks)) != FLO_OK) return rc;
     }
     return finish(c, d_cl.p, n, ch, d_blk.p, n_pub, out, blocks);
 }
@@ -155,10 +155,11 @@ extern "C" int flo_compare(flo_ctx *c, const float *pcm, size_t n_interleaved, c
     if (ch == 0) return fail(c, FLO_ERR_FORMAT, "Failed to deserialize transform frame");
     std::vector<FidClipDev> cl(1);
     cl[0].src_frames = n_interleaved / (size_t)ch;
+    std::vector<unsigned long long> blob_off;
+    std::vector<unsigned int> blob_len;
     if (f.is_transform) {
-        uint64_t nf = 0;
-        for (const FrameDesc &fr : f.frames) nf += fr.n_channels ? 1 : 0;
-        cl[0].dec_frames = nf > 1 ? (nf - 1) * 1024 : 0;
+        file_transform_blobs(f, blob_off, blob_len);
+        cl[0].dec_frames = blob_off.size() > 1 ? (uint64_t)(blob_off.size() - 1) * 1024 : 0;
     } else {
         for (const FrameDesc &fr : f.frames) cl[0].dec_frames += fr.samples;
     }
@@ -170,7 +171,7 @@ extern "C" int flo_compare(flo_ctx *c, const float *pcm, size_t n_interleaved, c
     DevBuf<float> d_src, d_dec;
     DevBuf<FidClipDev> d_cl;
     DevBuf<FidBlockDev> d_blk;
-    Quiesce q{c};
+    QuiesceOnExit q(c);
     const size_t n_src = cl[0].src_frames * (size_t)ch;
     if (!d_bytes.alloc(len + 32) || !d_src.alloc(n_src) || !d_cl.alloc(1) || !d_blk.alloc(dec_blocks * ch))
         return fail(c, FLO_ERR_NOMEM, "fidelity buffers");
@@ -184,12 +185,20 @@ extern "C" int flo_compare(flo_ctx *c, const float *pcm, size_t n_interleaved, c
     }
     if (f.is_transform) {
         HIPCHK(c, hipMemcpyAsync(d_cl.p, cl.data(), sizeof(FidClipDev), hipMemcpyHostToDevice, c->stream));
-        LossyCmpArgs cmp{d_src.p, d_cl.p, d_blk.p};
-        if ((rc = file_lossy_compare(c, f, d_bytes.p, cmp)) != FLO_OK) return rc;
+        const LossyCmpArgs cmp{d_src.p, d_cl.p, d_blk.p};
+        if (const unsigned nf = (unsigned)blob_off.size()) {   // the fused pass over the file's one clip
+            TableSet *ts;
+            if ((rc = get_tables(c, f.sample_rate, 0.5f, &ts)) != FLO_OK) return rc;
+            if ((rc = lossy_decode_whole(c, ts, d_bytes.p, ch, blob_off, blob_len, {0}, {nf}, {0}, nf, nullptr, &cmp)) != FLO_OK) return rc;
+        }
     } else {
         const uint64_t n_dec = cl[0].dec_frames * (uint64_t)ch;
         if (!d_dec.alloc(n_dec)) return fail(c, FLO_ERR_NOMEM, "fidelity decode scratch");
-        if (n_dec && (rc = file_lossless_decode(c, f, d_bytes.p, d_dec.p)) != FLO_OK) return rc;
+        if (n_dec) {
+            LlWrapperList w;
+            const uint64_t out_sf = file_ll_wrappers(f, w);
+            if ((rc = ll_decode_device(c, w, out_sf, d_bytes.p, ch, d_dec.p, nullptr)) != FLO_OK) return rc;
+        }
         HIPCHK(c, hipMemcpyAsync(d_cl.p, cl.data(), sizeof(FidClipDev), hipMemcpyHostToDevice, c->stream));
         if ((rc = compare_decoded(c, d_src.p, d_dec.p, d_cl.p, 1, ch, d_blk.p, dec_blocks)) != FLO_OK) return rc;
     }

@@ -1,5 +1,5 @@
 // seeking.cpp — the host half of libflo's seeking API (libflo/src/seeking.rs): the TOC and the time -> frame search. Both
-// are pure container reads; flo_decode_frame_at (flo_api.cpp) decodes on the device.
+// are pure container reads; flo_decode_frame_at (decode.cpp) decodes on the device.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>

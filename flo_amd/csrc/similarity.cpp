@@ -17,8 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "ctx_internal.hpp"
-#include "devpool.hpp"
+#include "devmem.hpp"
 #include "similarity_kernels.hpp"
 
 namespace flo {
@@ -52,15 +51,6 @@ void pack_profile(const flo_fingerprint &f, uint32_t *w) {
 }
 
 uint64_t fmt_key(const flo_fingerprint &f) { return (uint64_t)f.sample_rate << 8 | f.channels; }
-
-template <class T>
-struct DevBuf {   // one pool block, released when the call returns (every call ends with a stream synchronise)
-    T *p = nullptr;
-    ~DevBuf() {
-        if (p) pool_free(p);
-    }
-    bool alloc(size_t n) { return pool_alloc(&p, (n ? n : 1) * sizeof(T)) == hipSuccess; }
-};
 
 }  // namespace
 
@@ -168,6 +158,7 @@ static int topk_run(flo_fpindex *ix, const FpRec *d_q, uint32_t n_q, uint32_t k,
     const uint32_t nc = (ix->n + chunk - 1) / chunk;
     DevBuf<uint32_t> oi, pi, si;
     DevBuf<float> os, ps, ss;
+    QuiesceOnExit quiesce(ctx);
     if (!oi.alloc(n_out) || !os.alloc(n_out)) return fail(ctx, FLO_ERR_NOMEM, "top-k results");
     if (nc > 1 && (!pi.alloc(n_out * nc) || !ps.alloc(n_out * nc) || !si.alloc(n_out * ((nc + 1) / 2)) ||
                    !ss.alloc(n_out * ((nc + 1) / 2))))
@@ -202,11 +193,10 @@ extern "C" int flo_fpindex_topk(flo_fpindex *ix, const flo_fingerprint *q, size_
     std::vector<FpRec> rec(n_q);
     for (size_t i = 0; i < n_q; i++) rec[i] = make_rec(ix, q[i]);
     DevBuf<FpRec> dq;
+    QuiesceOnExit quiesce(ctx);
     if (!dq.alloc(n_q)) return fail(ctx, FLO_ERR_NOMEM, "queries");
     HIPCHK(ctx, hipMemcpyAsync(dq.p, rec.data(), n_q * sizeof(FpRec), hipMemcpyHostToDevice, ctx->stream));
-    int rc = topk_run(ix, dq.p, (uint32_t)n_q, k, false, idx, score);
-    if (rc != FLO_OK) hipStreamSynchronize(ctx->stream);   // dq is released on return
-    return rc;
+    return topk_run(ix, dq.p, (uint32_t)n_q, k, false, idx, score);
 }
 
 extern "C" int flo_fpindex_topk_self(flo_fpindex *ix, uint32_t k, uint32_t *idx, float *score) {
@@ -232,7 +222,10 @@ extern "C" int flo_fpindex_pairs(flo_fpindex *ix, float threshold, uint64_t cap,
     const uint32_t chunk = choose_chunk(ix, n, n, kFpTile, 0);
     const uint32_t nc = (n + chunk - 1) / chunk;
     const size_t cells = (size_t)n * nc;
-    DevBuf<uint32_t> dcount;
+    DevBuf<uint32_t> dcount, di, dj;
+    DevBuf<unsigned long long> doff;
+    DevBuf<float> ds;
+    QuiesceOnExit quiesce(ctx);
     if (!dcount.alloc(cells)) return fail(ctx, FLO_ERR_NOMEM, "pair counts");
     FpPairsArgs a{};
     a.rec = ix->d_rec;
@@ -257,9 +250,6 @@ extern "C" int flo_fpindex_pairs(flo_fpindex *ix, float threshold, uint64_t cap,
         return fail(ctx, FLO_ERR_NOMEM, std::to_string(total) + " pairs at or above the threshold, room for " + std::to_string(cap));
     if (!total) return FLO_OK;
     if (!i || !j || !score) return fail(ctx, FLO_ERR_ARG, "null argument");
-    DevBuf<unsigned long long> doff;
-    DevBuf<uint32_t> di, dj;
-    DevBuf<float> ds;
     if (!doff.alloc(cells) || !di.alloc(total) || !dj.alloc(total) || !ds.alloc(total))
         return fail(ctx, FLO_ERR_NOMEM, "pair output");
     HIPCHK(ctx, hipMemcpyAsync(doff.p, off.data(), cells * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
@@ -270,10 +260,7 @@ extern "C" int flo_fpindex_pairs(flo_fpindex *ix, float threshold, uint64_t cap,
     a.pj = dj.p;
     a.ps = ds.p;
     rc = timed_launch(ctx, "fp_pairs_write", [&] { return launch_fp_pairs_write(a, ctx->stream); });
-    if (rc != FLO_OK) {
-        hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
+    if (rc != FLO_OK) return rc;
     HIPCHK(ctx, hipMemcpyAsync(i, di.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(j, dj.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(score, ds.p, total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
