@@ -122,7 +122,7 @@ int ll_decode_device(flo_ctx *c, const LlWrapperList &w, uint64_t out_sf, const 
 int lossy_decode_whole(flo_ctx *c, const TableSet *ts, const uint8_t *bytes, int channels, const std::vector<unsigned long long> &blob_off,
                        const std::vector<unsigned int> &blob_len, const std::vector<unsigned long long> &clip_frame0,
                        const std::vector<unsigned int> &clip_frames, const std::vector<unsigned long long> &clip_out,
-                       unsigned max_frames, float *out, const LossyCmpArgs *cmp = nullptr);
+                       unsigned max_frames, float *out, const LossyCmpArgs *cmp = nullptr, unsigned lead = 0);
 
 // Launch through `launch` on the ctx stream; with profiling on, bracketed by events under `name`.
 template <typename F>

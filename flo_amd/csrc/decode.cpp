@@ -198,7 +198,7 @@ int ll_decode_device(flo_ctx *c, const LlWrapperList &w, uint64_t out_sf, const 
 int lossy_decode_whole(flo_ctx *c, const TableSet *ts, const uint8_t *bytes, int channels, const std::vector<unsigned long long> &blob_off,
                        const std::vector<unsigned int> &blob_len, const std::vector<unsigned long long> &clip_frame0,
                        const std::vector<unsigned int> &clip_frames, const std::vector<unsigned long long> &clip_out,
-                       unsigned max_frames, float *out, const LossyCmpArgs *cmp) {
+                       unsigned max_frames, float *out, const LossyCmpArgs *cmp, unsigned lead) {
     DevMem d_off, d_len, d_c0, d_cn, d_co, d_err;
     QuiesceOnExit quiesce_d_off(c);
     const std::vector<int> zero{0};
@@ -219,6 +219,7 @@ int lossy_decode_whole(flo_ctx *c, const TableSet *ts, const uint8_t *bytes, int
     A.channels = channels;
     A.out = out;
     A.error = d_err.as<int>();
+    A.lead = lead;
     if (cmp) {
         A.cmp = *cmp;
         if ((rc = timed_launch(c, "fidelity", [&] { return launch_lossy_compare(A, max_frames, c->stream); })) != FLO_OK) return rc;
@@ -473,21 +474,25 @@ extern "C" int flo_decode_frame_at(flo_ctx *c, const uint8_t *flo, size_t len, u
     }
     if (!fr.n_channels) return fail(c, FLO_ERR_FORMAT, "Transform frame has no channel data");
     if (nch == 0) return fail(c, FLO_ERR_FORMAT, "Failed to deserialize transform frame");
-    // the two blobs: the last earlier frame with channels (or the empty stand-in behind the file's bytes), then frame i
+    // A clip of two blobs: the last earlier frame with channels (or the empty stand-in behind the file's bytes), then frame
+    // i. The file's frames before them stay in front of the clip in the list (`lead` of them): a channel the predecessor does
+    // not carry overlaps with the last earlier frame that does (seeking.rs:189-200 runs every earlier frame through the decoder)
     static const uint8_t kNoChannels[2] = {0, 0};   // deserialize_frame: Long block, zero channels
-    std::vector<unsigned long long> blob_off(2);
-    std::vector<unsigned int> blob_len(2);
-    blob_off[0] = len;
-    blob_len[0] = 2;
-    for (size_t j = frame_index; j-- > 0;)
+    std::vector<unsigned long long> blob_off;
+    std::vector<unsigned int> blob_len;
+    for (size_t j = 0; j < (size_t)frame_index; j++)
         if (f.frames[j].n_channels) {
             const ChannelDesc &cd = f.channels_desc[f.frames[j].first_channel];
-            blob_off[0] = cd.off;
-            blob_len[0] = cd.len;
-            break;
+            blob_off.push_back(cd.off);
+            blob_len.push_back(cd.len);
         }
-    blob_off[1] = f.channels_desc[fr.first_channel].off;
-    blob_len[1] = f.channels_desc[fr.first_channel].len;
+    if (blob_off.empty()) {
+        blob_off.push_back(len);
+        blob_len.push_back(2);
+    }
+    const unsigned lead = (unsigned)(blob_off.size() - 1);
+    blob_off.push_back(f.channels_desc[fr.first_channel].off);
+    blob_len.push_back(f.channels_desc[fr.first_channel].len);
     HIPCHK(c, hipMemcpyAsync(d_bytes.as<uint8_t>() + len, kNoChannels, 2, hipMemcpyHostToDevice, c->stream));
     TableSet *ts;
     int rc = get_tables(c, f.sample_rate, 0.5f, &ts);
@@ -496,7 +501,7 @@ extern "C" int flo_decode_frame_at(flo_ctx *c, const uint8_t *flo, size_t len, u
     DevMem d_out;
     QuiesceOnExit quiesce_d_out(c);
     HIPCHK(c, pool_alloc(&d_out.p, n_out * sizeof(float)));
-    if ((rc = lossy_decode_whole(c, ts, d_bytes.as<uint8_t>(), nch, blob_off, blob_len, {0}, {2u}, {0}, 2u, d_out.as<float>())) != FLO_OK) return rc;
+    if ((rc = lossy_decode_whole(c, ts, d_bytes.as<uint8_t>(), nch, blob_off, blob_len, {(unsigned long long)lead}, {2u}, {0}, 2u, d_out.as<float>(), nullptr, lead)) != FLO_OK) return rc;
     HostResult host(malloc(n_out * sizeof(float)), free);
     if (!host) return fail(c, FLO_ERR_NOMEM, "out of host memory");
     if ((rc = download(c, host.get(), d_out.p, n_out * sizeof(float))) != FLO_OK) return rc;

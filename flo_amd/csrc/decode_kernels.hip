@@ -90,6 +90,7 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     unsigned long long wfirst = 0, wend = 0, frame0 = 0;   // (WIN) the window's samples [wfirst, wend), its file's first frame
     float *st = nullptr;    // (STRM) the stream's overlap state
     unsigned sflags = 0;    // (STRM) kRun*
+    unsigned back = 0;      // frames in front of frame h0 in the frame list that belong to the same file or stream
     const float *csrc = nullptr;                           // (CMP) the clip's source
     unsigned long long cmp_frames = 0, cmp_blk0 = 0;       // (CMP) its compared frames, its first block record
     if constexpr (MODE == kDecWhole || CMP) {
@@ -100,6 +101,7 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     h0 = (unsigned)(P / (unsigned)D.n_clips) * run;   // first frame of the run = first output block
     if (nframes < 2 || h0 + 1 >= nframes) return;
     h1 = h0 + run < nframes - 1 ? h0 + run : nframes - 1;   // last frame of the run
+    back = h0 + D.lead;
     if constexpr (CMP) {
         out = nullptr;
         const FidClipDev cd = D.cmp.clip[clip];
@@ -128,6 +130,7 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
         if (h0 > b1) return;
         h1 = h0 + run < b1 + 1 ? h0 + run : b1 + 1;
         frame0 = wd.frame0;
+        back = h0;
         out = D.out + wd.dst;
     } else {
         // run P of the call's runs: frames frame0 .. frame0 + n_frames - 1 of the call's frame list
@@ -142,27 +145,16 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
         out = D.out + rd.dst;
         st = rd.state;
         sflags = rd.flags;
+        back = rd.back;
     }
     const float scale = 2.0f / 1024.0f;
     // loop invariants of the run, in registers
-    float wn[8][2];        // window x 2/1024 (a power of two: exact) at the positions row r of this lane writes: four positions,
-                           // two values - the other two are their mirror images n <-> 2047 - n, and the window is symmetric
-                           // (the table's two halves agree to the last ulp or two of f32: 1e-7 of the 2e-6 the decode is held to)
     uint32_t bnd[8];       // 4 x band of coefficient 2 i (low half) and of 1023 - 2 i (high half), i = lane + 64 r
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const int idx = lane + 64 * r;
         const int ke = 2 * idx, ko = 1023 - 2 * idx;
         bnd[r] = 4u * (uint32_t)D.T.band[ke] | (4u * (uint32_t)D.T.band[ko]) << 16;
-        const float *win = D.window;
-        if (idx < 256) {
-            const int fi = 2 * idx, ri = 511 - 2 * idx;
-            wn[r][0] = scale * win[ri]; wn[r][1] = scale * win[512 + fi];      // = win[1536 + fi], win[1024 + ri]
-        } else {
-            const int i2 = idx - 256;
-            const int fi = 2 * i2, ri = 511 - 2 * i2;
-            wn[r][0] = scale * win[fi]; wn[r][1] = scale * win[512 + ri];      // = win[1536 + ri], win[1024 + fi]
-        }
     }
     float pv[16];          // second half of the previous frame of the channel being walked: positions lane + 64 k
 #ifdef FLO_DEC_STAMPS
@@ -175,12 +167,11 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
     // header bytes once per run and channel. The walk over the frames then stages nothing but the bytes of the channel
     // it is decoding (a whole frame - both channels' bytes - was staged and its header walked again for every channel:
     // a fifth of a channel-frame's time). False: a frame of the run is malformed.
-    auto index_run = [&](const uint32_t c) -> bool {
-        wave_sync();
-        if ((unsigned)lane <= h1 - h0) {
-            unsigned long long f;
-            if constexpr (WIN || STRM) f = frame0 + h0 + (unsigned)lane;
-            else f = D.clip_frame0[clip] + h0 + (unsigned)lane;
+    unsigned long long fbase;   // frame h0 in the frame list
+    if constexpr (WIN || STRM) fbase = frame0 + h0;
+    else fbase = D.clip_frame0[clip] + h0;
+    auto index_frame = [&](const unsigned long long f, const uint32_t c, const unsigned slot) {
+        {
             const unsigned long long foff = D.blob_off[f];
             const uint32_t flen = D.blob_len[f];
             const uint8_t *g = D.bytes + foff;
@@ -205,11 +196,15 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
                 }
                 if (k < c) pos += blen;
             }
-            s_foff[lane] = foff;
-            s_boff[lane] = foff + pos;
-            s_blen[lane] = blen;
-            s_flag[lane] = bad ? 2u : (c < nch ? 1u : 0u);   // 1: the frame carries channel c (one with fewer channels leaves the others silent)
+            s_foff[slot] = foff;
+            s_boff[slot] = foff + pos;
+            s_blen[slot] = blen;
+            s_flag[slot] = bad ? 2u : (c < nch ? 1u : 0u);   // 1: the frame carries channel c (one with fewer channels leaves the others silent)
         }
+    };
+    auto index_run = [&](const uint32_t c) -> bool {
+        wave_sync();
+        if ((unsigned)lane <= h1 - h0) index_frame(fbase + (unsigned)lane, c, (unsigned)lane);
         wave_sync();
         bool any_bad = false;
         for (unsigned i = 0; i <= h1 - h0; i++) any_bad = any_bad || s_flag[i] == 2u;   // (uniform)
@@ -512,28 +507,44 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
                     zi[0][r] = odd * w.x + even * w.y;
                 }
                 DSTAMP(6);
+                // the window at the four positions each row of this lane writes (the pack's window rows: the forward
+                // transform's layout is this one). All four are read: the f32 table is NOT symmetric - its second half
+                // is up to 3e-7 away from the mirrored first half (the sine's argument is rounded more coarsely there), and
+                // the reference windows position n with entry n. Sixteen registers held the first half across frames
+                // before; now eight 16-byte loads from the CU's L1 per channel-frame, in flight behind the FFT (the
+                // compare instantiation, at its register limit, issues them after it). +0.9 % on the batch decode.
+                float4 wv[8];
+                if constexpr (!CMP) {
+#pragma unroll
+                    for (int r = 0; r < 8; r++) wv[r] = D.T.pack[(kRowWin + r) * 64 + ln];
+                }
                 fft512_w(ln, zr[0], zi[0], xch[0], wf1, wf2);
                 DSTAMP(7);
+                if constexpr (CMP) {
+#pragma unroll
+                    for (int r = 0; r < 8; r++) wv[r] = D.T.pack[(kRowWin + r) * 64 + ln];
+                }
                 // post-rotation, scale 2 / 1024 and window (mdct.rs:252-287); every position is written exactly once
 #pragma unroll
                 for (int r = 0; r < 8; r++) {
                     const int idx = ln + 64 * r;
                     const float2 w = (r & 1) ? make_float2(wtw[r >> 1].z, wtw[r >> 1].w) : make_float2(wtw[r >> 1].x, wtw[r >> 1].y);
-                    const float val_re = w.x * zr[0][r] + w.y * zi[0][r];
-                    const float val_im = w.y * zr[0][r] - w.x * zi[0][r];
-                    if (r < 4) {   // idx < 256
+                    const float val_re = scale * (w.x * zr[0][r] + w.y * zi[0][r]);
+                    const float val_im = scale * (w.y * zr[0][r] - w.x * zi[0][r]);
+                    // (the scale 2 / 1024 is a power of two: where it is applied changes no rounding)
+                    if (r < 4) {   // idx < 256: wv = window[512 + fi], [ri], [1536 + fi], [1024 + ri]
                         const int fi = 2 * idx, ri = 511 - 2 * idx;
-                        recon[ri] = -val_im * wn[r][0];
-                        recon[512 + fi] = val_im * wn[r][1];
-                        recon[1024 + ri] = val_re * wn[r][1];
-                        recon[1536 + fi] = val_re * wn[r][0];
-                    } else {
+                        recon[ri] = -val_im * wv[r].y;
+                        recon[512 + fi] = val_im * wv[r].x;
+                        recon[1024 + ri] = val_re * wv[r].w;
+                        recon[1536 + fi] = val_re * wv[r].z;
+                    } else {       // wv = window[fi], [512 + ri], [1024 + fi], [1536 + ri]
                         const int i2 = idx - 256;
                         const int fi = 2 * i2, ri = 511 - 2 * i2;
-                        recon[fi] = -val_re * wn[r][0];
-                        recon[512 + ri] = val_re * wn[r][1];
-                        recon[1024 + fi] = val_im * wn[r][1];
-                        recon[1536 + ri] = val_im * wn[r][0];
+                        recon[fi] = -val_re * wv[r].x;
+                        recon[512 + ri] = val_re * wv[r].y;
+                        recon[1024 + fi] = val_im * wv[r].z;
+                        recon[1536 + ri] = val_im * wv[r].w;
                     }
                 }
                 wave_sync();
@@ -602,6 +613,39 @@ __global__ __launch_bounds__(64, 3) void lossy_decode_kernel(LossyDecArgs D) {
             }
         }
         if (!index_run(c)) return;
+        // A run starts from the second half of frame h0, decoded again for it. If frame h0 does not carry the channel, the
+        // overlap is older: a frame with fewer channels than the file leaves the others' overlap as it was (the rule of
+        // the overlap-add below), so it is the second half of the last earlier frame that carries the channel. That
+        // frame, looked for 64 frames per step, takes frame h0's place in the run's index: the first frame of a run
+        // writes no block, and frame h0 itself would have added nothing. A stream whose call holds no such frame
+        // starts from its stored state; anything else from silence.
+        if (s_flag[0] == 0u && !(STRM && (sflags & kRunLoad))) {
+            unsigned found = ~0u;
+            for (unsigned t0 = 0; t0 < back && found == ~0u; t0 += 64u) {
+                const unsigned t = t0 + (unsigned)lane;
+                bool has = false;
+                if (t < back) {
+                    const unsigned long long f = fbase - 1ull - t;
+                    const uint8_t *g = D.bytes + D.blob_off[f];
+                    has = D.blob_len[f] >= 2u && g[0] == 0 && (uint32_t)g[1] > c && (uint32_t)g[1] <= (uint32_t)D.channels;
+                }
+                const unsigned long long m = __ballot(has);
+                if (m) found = t0 + (unsigned)__ffsll((long long)m) - 1u;
+            }
+            if (found != ~0u) {
+                if (lane == 0) index_frame(fbase - 1ull - found, c, 0u);
+                wave_sync();
+                if (s_flag[0] == 2u) {   // (uniform)
+                    if (lane == 0) atomicExch(D.error, 1);
+                    return;
+                }
+            } else if constexpr (STRM) {
+                if (sflags & kRunBackLoad) {
+#pragma unroll
+                    for (int k = 0; k < 16; k++) pv[k] = st[((sflags & kRunOdd) ? nc * 1024u : 0u) + c * 1024u + (unsigned)lane + 64u * (unsigned)k];
+                }
+            }
+        }
         fetch(c, h0);
         for (unsigned h = h0; h <= h1; h++) {
             const uint32_t blen = s_blen[h - h0];

@@ -30,12 +30,15 @@ constexpr unsigned kRunLoad = 1u;         // start from the stream's overlap sta
 constexpr unsigned kRunStore = 2u;        // store the run's final overlap into the other half of the state
 constexpr unsigned kRunWriteFirst = 4u;   // the first frame writes a block (else it is a lead frame or the pre-roll)
 constexpr unsigned kRunOdd = 8u;          // the call's parity: which half of the state is read
+constexpr unsigned kRunBackLoad = 16u;    // a channel none of the `back` frames carries starts from the stream's overlap state
 struct LossyRunDev {
     unsigned long long frame0;        // first frame of the run in the call's frame list (blob_off / blob_len)
     unsigned long long dst;           // float offset in `out` of the first block the run writes
     float *state;                     // [2][channels][1024] the stream's overlap, read half and written half (kRunOdd)
     unsigned int n_frames;            // frames of the run, 1 .. kDecRunLong + 1 (16 at most with kRunWriteFirst)
     unsigned int flags;               // kRun*
+    unsigned int back;                // the stream's frames in front of frame0 in the call's frame list: where the overlap of a
+    unsigned int pad;                 // channel that frame0 does not carry is looked for (the last of them that carries it)
 };
 struct LossyStreamArgs {
     const LossyRunDev *runs;
@@ -62,6 +65,8 @@ struct LossyDecArgs {
     int *error;                       // set to 1 when a frame cannot be deserialised
     int run;                          // output blocks per wavefront (set by the launcher)
     unsigned int n_runs;              // runs per clip (set by the launcher)
+    unsigned int lead;                // frames in front of every clip's first frame in the frame list that belong to its file
+                                      // (decode_frame_at: the file's earlier frames, for a channel its predecessor lacks)
     unsigned long long *dbg;          // FLO_DEC_STAMPS builds only: phase tick sums (set by the launcher)
     LossyWinArgs win;                 // corpus windows only (set by launch_lossy_window)
     LossyStreamArgs strm;             // streaming decoders only (set by launch_lossy_stream)

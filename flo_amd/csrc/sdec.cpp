@@ -482,6 +482,10 @@ int launch_plans(flo_ctx *ctx, SdecWork *w, size_t n, flo_sdec *const *decs, con
                 } else {
                     r.frame0 = first + a - 1;
                     r.n_frames = (unsigned)(b - a + 1);
+                    // a channel the lead frame does not carry keeps an older overlap: the kernel looks for it in the
+                    // call's earlier frames of this stream, then in the stored state (the pre-roll has nothing before it)
+                    r.back = (unsigned)(a - 1);
+                    if (ws == 0) r.flags |= kRunBackLoad;
                 }
                 r.dst = off[i] + (a - ws) * blk;
                 r.state = d->d_state;

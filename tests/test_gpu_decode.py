@@ -3,12 +3,14 @@
 Lossless files: the decoded integers are compared bit for bit, the floats bit for bit as well (one multiply by the
 f32 constant 1/32767). Transform files: the inverse MDCT runs a different FFT than the oracle's, so PCM is compared
 within 2e-6 absolute on full-scale audio (the encoder-side coefficient tolerance is 1e-5 relative RMS) and the file
-geometry exactly. All calls go through the C ABI. Needs an MI355X."""
+geometry exactly; the hand-made files also against the exact f64 decode (tests/tdec_ref.py; test_gpu_tdecode.py is the
+full account). All calls go through the C ABI. Needs an MI355X."""
 import numpy as np
 import pytest
 
 import flofile
 import signals
+import tdec_ref
 from conftest import example_bytes
 from fixtures_util import LOSSLESS_EXAMPLES, LOSSY_EXAMPLES
 from gpu_util import ctx, snr_db  # noqa: F401
@@ -172,6 +174,7 @@ def test_hand_made_record_chains_decode_like_the_oracle(ctx, n_rec):
     assert np.max(np.abs(got - want)) <= LOSSY_TOL * max(1.0, float(np.max(np.abs(want))))
     if n_rec:
         assert float(np.max(np.abs(want))) > 0
+    tdec_ref.assert_tight(f"record_chain_{n_rec}", flo, got)      # and against the exact f64 decode, in units of the oracle's error
 
 
 def test_hand_made_odd_record_headers_decode_like_the_oracle(ctx):
@@ -199,6 +202,8 @@ def test_hand_made_odd_record_headers_decode_like_the_oracle(ctx):
         got = ctx.decode(flo)
         assert got.shape == want.shape, i
         assert np.max(np.abs(got - want), initial=0.0) <= LOSSY_TOL * max(1.0, float(np.max(np.abs(want), initial=0.0))), i
+        assert np.isfinite(want).all(), i
+        tdec_ref.assert_tight(f"odd_record_headers_{i}", flo, got)
 
 
 def test_empty_and_tiny_files(ctx):
