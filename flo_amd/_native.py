@@ -40,6 +40,7 @@ EXPORTS = [
     "flo_sdec_buffered_bytes", "flo_sdec_next_frame", "flo_sdec_decode_available", "flo_sdec_reset", "flo_sdec_decode_ready",
     "flo_spectral_similarity", "flo_fpindex_create", "flo_fpindex_destroy", "flo_fpindex_topk", "flo_fpindex_topk_self",
     "flo_fpindex_pairs", "flo_batch_fidelity", "flo_compare",
+    "flo_batch_size_curve", "flo_batch_set_quality", "flo_rate_pick", "flo_encode_batch_to_size",
 ]
 
 
@@ -236,5 +237,10 @@ def lib():
     L.flo_fpindex_pairs.argtypes = [vp, C.c_float, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]
     L.flo_batch_fidelity.argtypes = [vp, vp, vp, sz, vp]
     L.flo_compare.argtypes = [vp, vp, sz, C.c_char_p, sz, vp, vp, sz, C.POINTER(sz)]
+    L.flo_batch_size_curve.argtypes = [vp, sz, vp, vp]
+    L.flo_batch_set_quality.argtypes = [vp, C.c_float]
+    L.flo_rate_pick.argtypes = [sz, vp, vp, C.c_uint64, u32p, C.POINTER(C.c_int)]
+    L.flo_encode_batch_to_size.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.c_uint32, C.c_uint8, sz, vp, vp, C.POINTER(vp),
+                                           C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), vp, vp]
     _LIB = L
     return L

@@ -178,6 +178,35 @@ class Context:
             self._L.flo_free(outs[i])
         return res
 
+    def encode_batch_to_size(self, clips, sample_rate, channels, qualities, target_bytes, metadata=None):
+        """flo_encode_batch_to_size: (files, chosen, fits) - every clip at the best candidate quality whose whole file,
+        META included, fits target_bytes[i]; one upload, one size curve, one encode per clip"""
+        arrs = [_f32(c) for c in clips]
+        k = len(arrs)
+        q = np.ascontiguousarray(qualities, dtype=np.float32).reshape(-1)
+        tb = np.ascontiguousarray(target_bytes, dtype=np.uint64).reshape(-1)
+        if tb.size != k:
+            raise ValueError(f"{tb.size} targets for {k} clips")
+        ptrs = (C.c_void_p * k)(*[a.ctypes.data for a in arrs])
+        lens = (C.c_size_t * k)(*[a.size for a in arrs])
+        mp = ml = None
+        if metadata is not None:
+            metas = [bytes(m or b"") for m in metadata]
+            if len(metas) != k:
+                raise ValueError(f"metadata has {len(metas)} entries for {k} clips")
+            keep = [C.create_string_buffer(m, len(m)) if m else None for m in metas]
+            mp = (C.c_void_p * k)(*[C.addressof(x) if x is not None else None for x in keep])
+            ml = (C.c_size_t * k)(*[len(m) for m in metas])
+        outs, olens = (C.c_void_p * k)(), (C.c_size_t * k)()
+        chosen, fits = np.zeros(max(k, 1), np.uint32), np.zeros(max(k, 1), np.int32)
+        self._chk(self._L.flo_encode_batch_to_size(self._h, k, ptrs, lens, sample_rate, channels, q.size, q.ctypes.data, tb.ctypes.data,
+                                                   mp, ml, outs, olens, chosen.ctypes.data, fits.ctypes.data))
+        res = []
+        for i in range(k):
+            res.append(C.string_at(outs[i], olens[i]) if outs[i] else b"")
+            self._L.flo_free(outs[i])
+        return res, [int(x) for x in chosen[:k]], [bool(x) for x in fits[:k]]
+
     def decode(self, flo: bytes, with_info=False):
         """libflo::decode (lib.rs:296-315): interleaved f32 PCM of a .flo file, decoded on the device."""
         return self._decode(self._L.flo_decode, np.float32, flo, with_info)
@@ -407,6 +436,18 @@ class Batch:
 
     def set_bit_depth(self, bit_depth: int):
         self.ctx._chk(self._L.flo_batch_set_bit_depth(self._h, bit_depth))
+
+    def size_curve(self, qualities) -> np.ndarray:
+        """flo_batch_size_curve: [n_clips, K] uint64, the exact length of the file (empty META) an encode of this lossy batch
+        at qualities[j] produces, from one device pass over the PCM the batch holds; the batch's results are untouched"""
+        q = np.ascontiguousarray(qualities, dtype=np.float32).reshape(-1)
+        out = np.zeros((self.n_clips, q.size), np.uint64)
+        self.ctx._chk(self._L.flo_batch_size_curve(self._h, q.size, q.ctypes.data, out.ctypes.data))
+        return out
+
+    def set_quality(self, quality: float):
+        """re-point a lossy batch at another quality; results of an earlier encode are dropped"""
+        self.ctx._chk(self._L.flo_batch_set_quality(self._h, quality))
 
     def fetch(self, clip, metadata=b"") -> bytes:
         out, n = C.c_void_p(), C.c_size_t()
@@ -1116,6 +1157,132 @@ def encode_with_bitrate_many(clips, sample_rate, channels, _bit_depth, target_bi
     """encode_with_bitrate (libflo::encode_with_bitrate) of every clip, the analysis of all of them in one device pass"""
     q = QualityPreset.from_bitrate(target_bitrate_kbps, sample_rate, channels).as_f32()
     return _encode_analysed_many(MODE_LOSSY, clips, sample_rate, channels, q, 16, metadata)
+
+
+# -- size curves and the rate-targeted encode ---------------------------------------------------------------------------
+DEFAULT_RATE_GRID = tuple(i / 16 for i in range(17))   # 0, 1/16, ..., 15/16, 1.0
+
+
+def rate_pick(qualities, sizes, budget):
+    """flo_rate_pick: (index, fits) of the candidate of the largest quality value whose size is <= budget (every candidate
+    is looked at; equal qualities: the lower index); when none fits, the candidate of the smallest quality, fits False"""
+    q = np.ascontiguousarray(qualities, dtype=np.float32).reshape(-1)
+    z = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    if q.size != z.size:
+        raise ValueError(f"{q.size} qualities for {z.size} sizes")
+    idx, fits = C.c_uint32(), C.c_int()
+    rc = _native.lib().flo_rate_pick(q.size, q.ctypes.data, z.ctypes.data, int(budget), C.byref(idx), C.byref(fits))
+    if rc != _native.OK:
+        raise FloError("flo_rate_pick: 1 to 32 candidates")
+    return idx.value, bool(fits.value)
+
+
+def size_curve(samples, sample_rate, channels, qualities=DEFAULT_RATE_GRID) -> np.ndarray:
+    """the K file sizes (bytes, empty META) of one clip encoded at each candidate quality, measured on the device"""
+    p = _f32(samples)
+    b = Batch(default_context(), MODE_LOSSY, [p.size], sample_rate, channels, 0.0)
+    try:
+        b.upload(0, p)
+        return b.size_curve(qualities)[0]
+    finally:
+        b.close()
+
+
+def _target_bytes(target_kbps, sample_frames, sample_rate) -> int:
+    """kbps over the clip's duration, for the whole file: floor(kbps * 125 * sample_frames / sample_rate)"""
+    from fractions import Fraction
+    return int(Fraction(target_kbps) * 125 * sample_frames / sample_rate)
+
+
+def _rate_info(q, idx, fits, size, target):
+    return {"quality": float(q[idx]), "index": int(idx), "fits": bool(fits), "file_bytes": int(size), "target_bytes": int(target)}
+
+
+def encode_to_bitrate(samples, sample_rate, channels, target_kbps, qualities=DEFAULT_RATE_GRID, metadata=None, with_info=False,
+                      _analysis=True):
+    """Like encode_with_bitrate (analysis META merged), but the quality is MEASURED: the best candidate quality whose whole
+    file, META included, is at most floor(target_kbps * 125 * sample_frames / sample_rate) bytes. One batch: upload,
+    analysis, size curve, set_quality, encode. with_info adds {"quality", "index", "fits", "file_bytes", "target_bytes"}"""
+    from . import meta as _meta
+    p = _f32(samples)
+    q = np.ascontiguousarray(qualities, dtype=np.float32).reshape(-1)
+    b = Batch(default_context(), MODE_LOSSY, [p.size], sample_rate, channels, float(q[0]))
+    try:
+        b.upload(0, p)
+        m = _meta.merge_analysis(metadata or b"", b.analysis_metadata(0, 50)) if _analysis else bytes(metadata or b"")
+        sizes = b.size_curve(q)[0]
+        target = _target_bytes(target_kbps, p.size // channels, sample_rate)
+        idx, fits = rate_pick(q, sizes, max(target - len(m), 0))
+        b.set_quality(float(q[idx]))
+        b.encode(0)
+        b.sync()
+        f = b.fetch(0, m)
+        return (f, _rate_info(q, idx, fits, len(f), target)) if with_info else f
+    finally:
+        b.close()
+
+
+def encode_to_bitrate_many(clips, sample_rate, channels, target_kbps, qualities=DEFAULT_RATE_GRID, metadata=None, with_info=False):
+    """encode_to_bitrate of every clip: one upload, ONE batched analysis, one size curve, then every clip encoded once at
+    its own chosen quality (a batch per chosen candidate, filled on the device). target_kbps: one number or one per clip;
+    metadata: None, one bytes for every clip, or one entry per clip. Returns the files, with_info: (files, infos)"""
+    from . import meta as _meta
+    ps = [_f32(x) for x in clips]
+    n = len(ps)
+    if metadata is None or isinstance(metadata, (bytes, bytearray)):
+        user = [bytes(metadata or b"")] * n
+    else:
+        user = [bytes(m or b"") for m in metadata]
+        if len(user) != n:
+            raise ValueError(f"metadata has {len(user)} entries for {n} clips")
+    kbps = list(target_kbps) if np.ndim(target_kbps) else [target_kbps] * n
+    if len(kbps) != n:
+        raise ValueError(f"target_kbps has {len(kbps)} entries for {n} clips")
+    if not ps:
+        return ([], []) if with_info else []
+    q = np.ascontiguousarray(qualities, dtype=np.float32).reshape(-1)
+    ctx = default_context()
+    b = Batch(ctx, MODE_LOSSY, [p.size for p in ps], sample_rate, channels, float(q[0]))
+    kids = []
+    try:
+        for i, p in enumerate(ps):
+            ctx._chk(b._L.flo_batch_upload(b._h, i, p.ctypes.data))
+        b.sync()   # (the copies have read ps)
+        metas = [_meta.merge_analysis(user[i], m) for i, m in enumerate(b.analysis_metadata_all(50))]
+        sizes = b.size_curve(q)
+        targets = [_target_bytes(kbps[i], ps[i].size // channels, sample_rate) for i in range(n)]
+        picks = [rate_pick(q, sizes[i], max(targets[i] - len(metas[i]), 0)) for i in range(n)]
+        files = [None] * n
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        for j in sorted(set(idx for idx, _ in picks)):
+            members = [i for i in range(n) if picks[i][0] == j]
+            if len(members) == n:
+                e = b
+                e.set_quality(float(q[j]))
+            else:   # the chosen candidate's clips, copied device to device, nothing re-uploaded
+                e = Batch(ctx, MODE_LOSSY, [ps[i].size for i in members], sample_rate, channels, float(q[j]))
+                kids.append(e)
+                e.sync()   # (the new batch's zero padding is written on the context's stream; the copies are not)
+                for k, i in enumerate(members):
+                    nb = (ps[i].size // channels) * channels * 4
+                    if nb and hip.hipMemcpy(e.clip_device_ptr(k), b._L.flo_batch_clip_device_data(b._h, i), nb, 3) != 0:
+                        raise FloError("hipMemcpy (device to device) failed")
+                if hip.hipDeviceSynchronize() != 0:   # (the encode runs on the context's stream: behind the copies)
+                    raise FloError("hipDeviceSynchronize failed")
+            e.encode(0)
+            e.sync()
+            for k, i in enumerate(members):
+                files[i] = e.fetch(i if e is b else k, metas[i])
+            if e is not b:
+                e.close()
+        if with_info:
+            return files, [_rate_info(q, picks[i][0], picks[i][1], len(files[i]), targets[i]) for i in range(n)]
+        return files
+    finally:
+        for e in kids:
+            e.close()
+        b.close()
 
 
 # -- spectral similarity (core/analysis.rs:359-437) -----------------------------------------------------------------------

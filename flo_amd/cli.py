@@ -3,7 +3,8 @@
 Mirrors the reference CLI (reflo/src/main.rs:19-93, 218-420): the same sub-commands, options, quality names and
 printed fields for the parts that sit on this repository's path -
     encode  <in.wav> <out.flo> [--level N] [--lossy | --transform] [--quality low|medium|high|veryhigh|transparent]
-                               [--bitrate KBPS]
+                               [--bitrate KBPS] [--target-kbps KBPS]
+    curve   <in.wav> [--json]
     decode  <in.flo> <out.wav>
     info    <in.flo>
     validate <in.flo>
@@ -23,6 +24,9 @@ waveform peaks at 60 per second and the spectral fingerprint (core/analysis.rs).
 `compare` (not in reflo; the reference's TODO lists it as "compare original vs encoded") measures on the device how far
 the file's decoded audio lies from the source WAV: SNR, segmental SNR, peak error, clipped samples and the energy of the
 decoded tail past the source's end, per channel (flo_compare, include/flo_hip.h).
+`encode --lossy --target-kbps N` and `curve` (not in reflo) measure instead of mapping: the size of the file at every quality
+of a grid comes from one device pass over the audio (flo_batch_size_curve), and the encode takes the best quality whose whole
+file, META included, stays within N kbps over the clip's duration.
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
 """
@@ -68,6 +72,23 @@ def encode_from_audio(audio_bytes: bytes, level=5, lossy=False, quality=0.6, bit
         q = api.QualityPreset.from_bitrate(bitrate, sr, ch).as_f32() if bitrate is not None else quality
         return api.TransformEncoder(sr, ch, q, c).encode_to_flo(samples, mb)
     return api.Encoder(sr, ch, 16, c).with_compression(level).encode(samples, mb)
+
+
+def encode_to_target(audio_bytes: bytes, target_kbps, title=None, artist=None, album=None, encoding_time=None):
+    """(file, info): the WAV encoded at the best quality of api.DEFAULT_RATE_GRID whose whole file fits target_kbps"""
+    samples, sr, ch = read_wav_bytes(audio_bytes)
+    shown = int(target_kbps) if float(target_kbps).is_integer() else target_kbps
+    mb = meta.cli_metadata(samples.size, sr, ch, _wav_source_format(audio_bytes), True, 0.0, shown, 5, title, artist, album,
+                           encoding_time)
+    return api.encode_to_bitrate(samples, sr, ch, target_kbps, metadata=mb, with_info=True, _analysis=False)
+
+
+def curve_report(audio_bytes: bytes, qualities=api.DEFAULT_RATE_GRID) -> list:
+    """one row per candidate quality: the size of the file (empty META) and its bitrate over the clip's duration"""
+    samples, sr, ch = read_wav_bytes(audio_bytes)
+    sizes = api.size_curve(samples, sr, ch, qualities)
+    secs = samples.size / ch / sr
+    return [{"quality": float(q), "bytes": int(b), "kbps": (int(b) * 8 / 1000 / secs) if secs else 0.0} for q, b in zip(qualities, sizes)]
 
 
 def get_metadata(flo_bytes: bytes):
@@ -199,6 +220,7 @@ def main(argv=None) -> int:
     e.add_argument("--transform", action="store_true", help="Use transform-based lossy")
     e.add_argument("--quality", default="high", help="Lossy quality level (low, medium, high, veryhigh, transparent)")
     e.add_argument("--bitrate", type=int, default=None, help="Target bitrate in kbps (alternative to quality)")
+    e.add_argument("--target-kbps", type=float, default=None, help="Lossy: the best measured quality whose file stays within this bitrate")
     e.add_argument("--title", default=None, help="Title metadata")
     e.add_argument("--artist", default=None, help="Artist metadata")
     e.add_argument("--album", default=None, help="Album metadata")
@@ -228,6 +250,9 @@ def main(argv=None) -> int:
     cp.add_argument("input")
     cp.add_argument("--json", action="store_true", help="Output as JSON")
     cp.add_argument("--blocks", action="store_true", help="Also print the SNR of every 1024-frame block")
+    cu = sub.add_parser("curve", help="File size at every quality of a grid, measured on the device")
+    cu.add_argument("input")
+    cu.add_argument("--json", action="store_true", help="Output as JSON")
     a = ap.parse_args(argv)
     try:
         if a.command == "encode":
@@ -238,7 +263,13 @@ def main(argv=None) -> int:
             print(f"  Channels: {ch}")
             print(f"  Duration: {samples.size / ch / sr:.2f}s")
             lossy = a.lossy or a.transform
-            if lossy or a.bitrate is not None:
+            if a.target_kbps is not None:
+                print(f"Encoding to flo (lossy, at most {a.target_kbps:g} kbps, measured)...")
+                flo, info = encode_to_target(audio, a.target_kbps, a.title, a.artist, a.album)
+                secs = samples.size / ch / sr
+                print(f"  Quality: {info['quality']:.4f} (candidate {info['index']}){'' if info['fits'] else ' - the target is below the smallest file'}")
+                print(f"  Achieved: {(len(flo) * 8 / 1000 / secs) if secs else 0.0:.1f} kbps ({len(flo)} of {info['target_bytes']} bytes)")
+            elif lossy or a.bitrate is not None:
                 if a.bitrate is not None:
                     print(f"Encoding to flo (lossy, ~{a.bitrate} kbps)...")
                     q = None
@@ -347,6 +378,14 @@ def main(argv=None) -> int:
                     print(f"  Average loudness:    {sp['average_loudness']}")
                     print(f"  Spectral hash (first 8 bytes):   {sp['spectral_hash_hex']}")
                     print()
+        elif a.command == "curve":
+            rows = curve_report(open(a.input, "rb").read())
+            if a.json:
+                print(json.dumps(rows, indent=2))
+            else:
+                print(f"{'quality':>8}  {'bytes':>12}  {'kbps':>9}")
+                for r in rows:
+                    print(f"{r['quality']:8.4f}  {r['bytes']:12d}  {r['kbps']:9.1f}")
         elif a.command == "similar":
             print(similar_report(a.inputs, a.k, a.threshold, a.json))
         elif a.command == "compare":

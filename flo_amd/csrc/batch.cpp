@@ -190,6 +190,7 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
 extern "C" float *flo_batch_clip_device_ptr(flo_batch *b, size_t clip) {
     if (!b || clip >= b->n_clips) return nullptr;
     if (clip < b->tail.size()) b->tail[clip].clear();   // (the caller writes the clip: it is analysed as the device holds it)
+    b->pcm_written = true;
     return b->d_pcm + b->clip_off[clip];
 }
 
@@ -208,6 +209,7 @@ extern "C" int flo_batch_upload(flo_batch *b, size_t clip, const float *pcm) {
     if (n_copy)
         HIPCHK(c, hipMemcpyAsync(b->d_pcm + b->clip_off[clip], pcm, n_copy * sizeof(float), hipMemcpyHostToDevice, c->stream));
     b->keep_tail(clip, pcm);
+    b->pcm_written = true;
     b->encoded = b->synced = b->encode_failed = false;
     return FLO_OK;
 }
@@ -233,6 +235,7 @@ extern "C" int flo_batch_fill_synthetic(flo_batch *b, uint32_t seed, uint64_t cl
     hipFree(d_off);
     b->tail.clear();
     if (e != hipSuccess || rc != 0) return fail(c, FLO_ERR_DEVICE, "synthetic fill failed");
+    b->pcm_written = true;
     b->encoded = b->synced = b->encode_failed = false;
     return FLO_OK;
 }
@@ -631,6 +634,7 @@ int batch_upload_all(flo_batch *b, const float *const *pcm, hipStream_t stream) 
     }
     std::string err;
     if (stager_upload(c->stager, segs, stream ? stream : c->stream, err) != 0) return fail(c, FLO_ERR_DEVICE, err);
+    b->pcm_written = true;
     b->encoded = b->synced = b->encode_failed = false;
     return FLO_OK;
 }

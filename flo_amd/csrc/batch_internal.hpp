@@ -1,6 +1,6 @@
 // batch_internal.hpp — the device-resident batch (flo_batch_*, include/flo_hip.h) as the library's source files see it:
-// batch.cpp makes, encodes and releases it; decode.cpp, fidelity.cpp, analysis.cpp, dist.cpp, stages.cpp and stream.cpp
-// read it. Not part of the C ABI.
+// batch.cpp makes, encodes and releases it; decode.cpp, fidelity.cpp, analysis.cpp, dist.cpp, stages.cpp, stream.cpp and
+// rate.cpp read it. Not part of the C ABI.
 #pragma once
 #include <vector>
 
@@ -55,6 +55,7 @@ struct flo_batch {
     LossyPlan plan;   // of the last lossy flo_batch_encode
     // results (host, valid after sync)
     bool encoded = false, synced = false, encode_failed = false;
+    bool pcm_written = false;   // an upload, a fill or a device pointer handed out: the batch holds PCM (flo_batch_size_curve)
     std::vector<uint64_t> h_clip_bytes;
     std::vector<uint32_t> h_frame_size;
     // lossless

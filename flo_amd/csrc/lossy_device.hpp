@@ -1434,6 +1434,42 @@ __device__ __forceinline__ void sparse_plan(const int lane, const int (&q)[16], 
     sparse_plan_m(lane, nonzero_mask16(q), P);
 }
 
+// The size-only cut of sparse_plan_m (lossy_curve_kernel): the bytes serialize_sparse makes of the 1024 values whose
+// non-zero mask is m (16 per lane), from the mask alone. Same record-start mask, same 255-cap continuations, same third
+// header byte of a zero run of 128 or more that leaves the lane; what the emitter alone needs (off0, cross_cnt, nz_end) is
+// not computed, and the lanes' byte counts meet in one wave reduction. Returns P.total of sparse_plan_m (uniform).
+__device__ __forceinline__ uint32_t sparse_size_m(const int lane, const uint32_t m) {
+    const uint32_t prev_m = (uint32_t)dpp_i<0x138>(0, (int)m);  // mask of lane - 1 (0 for lane 0)
+    const uint32_t prev_nz = (prev_m >> 15) & 1u;
+    uint32_t zs = ~m & ((m << 1) | prev_nz) & 0xFFFFu;
+    if (lane == 0 && !(m & 1u)) zs |= 1u;  // the walk starts with a zero run
+    const int base = 16 * lane;
+    const uint32_t inv = ~m & 0xFFFFu;
+    const int first_nz = m ? base + __builtin_ctz(m) : 1024;
+    const int last_z = inv ? base + 31 - __builtin_clz(inv) : -1;
+    const unsigned long long has_nz = __ballot(m != 0u), has_z = __ballot(inv != 0u);
+    const unsigned long long nz_above = (has_nz >> 1) >> lane;
+    const unsigned long long z_below = lane ? has_z << (64 - lane) : 0ull;
+    const int ln_nz = nz_above ? lane + 1 + __builtin_ctzll(nz_above) : lane;
+    const int ln_zb = z_below ? lane - 1 - __builtin_clzll(z_below) : lane;
+    const int f_nz = __shfl(first_nz, ln_nz), l_z = __shfl(last_z, ln_zb);
+    const int nn = nz_above ? f_nz : 1024;          // first non-zero behind this lane
+    const int lz_before = z_below ? l_z : -1;
+    const int t_in = base - 1 - lz_before;          // length of the non-zero run ending just before this lane
+    const int ln = inv ? __builtin_ctz(inv) : 16;
+    uint32_t hmask = zs;
+    if (t_in > 0) {   // 255-cap continuation
+        int x = (255 - (t_in % 255)) % 255;
+        if (x < ln) hmask |= 1u << x;
+    }
+    if (lane == 0 && (m & 1u)) hmask |= 1u;  // record that starts the walk on a non-zero
+    uint32_t bytes = 2u * (uint32_t)__builtin_popcount(m | (hmask << 16));
+    const int s_last = zs ? 31 - __builtin_clz(zs) : 0;
+    const bool crossing = zs && ((m >> s_last) == 0u);   // the lane's last zero run leaves it
+    if (crossing && nn - (base + s_last) >= 128) bytes += 1u;
+    return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_sum(bytes), 63);
+}
+
 // Emit this lane's part of the sparse blobs of CH channels (LDS bytes; blob c starts at dst[c][0]). Zero values and
 // the unused third header byte go to the lane's two private trash bytes of that channel (dst[c] + trash_off[c]).
 // With CH = 2 the two channels' record loops run merged (one trip handles one record of each) and so do the value

@@ -14,6 +14,8 @@
 //                            re-runs the transform and finishes each frame into a fixed slot; compact_kernel
 //                            packs the slots. lossy_frame2x_kernel is its stereo form built from the lock-step device
 //                            functions, lossy_frame_n_kernel<P> the same for 3 to 8 channels.
+//   lossy_curve_kernel       size curve: behind pass 1 and the scan, one wave per (frame, channel) prices every candidate
+//                            quality from one transform (keep masks -> sparse sizes, no packer).
 //   All forms produce identical bytes (tests compare them file by file).
 #include <assert.h>
 #include <stdlib.h>
@@ -1352,6 +1354,126 @@ __global__ __launch_bounds__(64) void lossy_frame_n_kernel(LossyArgs A) {
     for (uint32_t i = lane; i < n16; i += 64) dst[i] = src[i];
 }
 
+// ---------------------------------------------------------------------------------------------- size curve
+// The exact sparse bytes of one (frame, channel) at every candidate quality, from ONE transform: quality enters the
+// encoder only through the keep threshold smr_threshold(quality) of quantize_coefficients (encoder.rs:130-151) - the MDCT,
+// the band levels with their temporal chain, the scale factors and the integer round(c * sf) do not depend on it - so a
+// vector's size at quality q is a function of one 1024-bit keep mask. One wavefront per (frame, channel), any channel
+// count, with the single-channel device functions every other form is compared against; a_t / s_prev are what pass 1 and
+// lossy_scan_kernel of the frame-parallel form left. Per candidate: 25 band thresholds masking_amplitude(s, smr_thr_j)
+// (a table in LDS over the dead transposition buffer), the lane's 16 keep bits |c| > max(T_band_j, ath_lin_j[k]) - or, for
+// a candidate that encodes with the exact-threshold instantiations, quantise<1, true>'s re-decision (a uniform branch) -
+// and sparse_size_m. Candidate j's total ends on lane j; lanes 0 .. n_q - 1 add theirs to the clip's row (u64 integer
+// atomics: the sums do not depend on the order).
+__global__ __launch_bounds__(64) void lossy_curve_kernel(CurveArgs C, const float *__restrict__ pcm_all, const float *__restrict__ a_t,
+                                                         const float *__restrict__ s_prev, unsigned long long *__restrict__ sizes) {
+    __shared__ WaveLds<1> lds;
+    static_assert(kMaxCurveCandidates * 32 <= kXchFloats, "the threshold table fits the exchange buffer");
+    const LossyArgs &A = C.A;
+    const LossyDevTables &T = A.T;
+    const int lane = lane_id();
+    const int nch = A.nch;
+    const unsigned long long gframe = (unsigned long long)blockIdx.x / (unsigned)nch;
+    const int ch = (int)((unsigned long long)blockIdx.x - gframe * (unsigned)nch);
+    if (gframe >= A.total_frames) return;
+    int lo = 0, hi = A.n_clips - 1;
+    while (lo < hi) {
+        int mid = (lo + hi + 1) >> 1;
+        if (A.clip_frame0[mid] <= gframe) lo = mid; else hi = mid - 1;
+    }
+    const unsigned clip = (unsigned)lo;
+    const unsigned h = (unsigned)(gframe - A.clip_frame0[clip]);
+    const float *pcm = pcm_all + A.clip_off[clip];
+    const long long n_sf = (long long)A.clip_nsf[clip];
+
+    LaneConst L;
+    load_lane_const(lane, L, T);
+    if (lane == 0) lds.slots[0][kZeroSlot] = make_float2(0.f, 0.f);
+    float c[1][16];
+    {
+        float ae[1][8], ao[1][8], be[1][8], bo[1][8];
+        load_half<1>(lane, pcm, n_sf, nch, ch, (long long)h * 1024 - 1024, ae, ao);
+        load_half<1>(lane, pcm, n_sf, nch, ch, (long long)h * 1024, be, bo);
+        mdct_frame<1>(lane, ae, ao, be, bo, lds, T, c);
+    }
+    float energy[1], bmax[1];
+    band_stats<1>(lane, c, lds.slots, T, energy, bmax);
+    // temporal masking and scale factor as analyse_frame (lanes 0..24 = bands)
+    const unsigned long long fi = (gframe * (unsigned)nch + (unsigned)ch) * 32 + (unsigned)(lane < 25 ? lane : 0);
+    const float a = a_t[fi], prev = s_prev[fi];
+    const float s = max_raw(a, prev * 0.7f);
+    const float sf = bmax[0] > 1e-10f ? __fdiv_rn(30000.0f, bmax[0]) : 1.0f;
+    float *thr_tab = lds.u.xch[0];   // [n_q][32] amplitude thresholds (the transposition buffer is dead)
+    const int n_q = C.n_q;
+    if (lane < 25) {
+        lds.bandv[0][lane] = make_float2(0.f, sf);
+        lds.band_s[0][lane] = s;
+        for (int j = 0; j < n_q; j++) thr_tab[32 * j + lane] = masking_amplitude(s, C.smr_thr[j]);
+    }
+    wave_sync();
+    // the quantised integers (quality-independent) -> "rounds to non-zero"; |c| stays in c
+    uint32_t bo[16];
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const float4 bo4 = T.pack[(kRowBo + g) * 64 + lane];
+        bo[4 * g + 0] = __float_as_uint(bo4.x), bo[4 * g + 1] = __float_as_uint(bo4.y);
+        bo[4 * g + 2] = __float_as_uint(bo4.z), bo[4 * g + 3] = __float_as_uint(bo4.w);
+    }
+    uint32_t nz = 0;
+    float ax[16];
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+        const float sfe = reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(lds.bandv[0]) + bo[e])->y;
+        const float x = c[0][e];
+        const float xs = x * sfe;
+        const float half = __uint_as_float((__float_as_uint(xs) & 0x80000000u) | 0x3EFFFFFFu);
+        nz |= (cvt_rz(xs + half) != 0 ? 1u : 0u) << e;
+        ax[e] = fabsf(x);
+    }
+    unsigned long long mine = 0;
+    for (int j = 0; j < n_q; j++) {
+        float al[16], tb[16];
+        const float4 *ap = C.ath[j] + lane;
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const float4 al4 = ap[64 * g];
+            al[4 * g + 0] = al4.x, al[4 * g + 1] = al4.y, al[4 * g + 2] = al4.z, al[4 * g + 3] = al4.w;
+        }
+        const char *tj = reinterpret_cast<const char *>(thr_tab + 32 * j);
+#pragma unroll
+        for (int e = 0; e < 16; e++) tb[e] = *reinterpret_cast<const float *>(tj + (bo[e] >> 1));
+        uint32_t keep = 0;
+        if ((C.exact_mask >> j) & 1u) {   // uniform: quantise<1, true>'s decision
+            const bool qt = (C.qtrans_mask >> j) & 1u;
+            const float smr = C.smr_thr[j];
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+                const float thr = max_raw(tb[e], al[e]);
+                bool k = ax[e] > thr;
+                const bool near = fabsf(ax[e] - thr) <= 1e-5f * thr || (qt && !(ax[e] > 1e-10f));
+                if (near) {
+                    float signal_db = ax[e] > 1e-10f ? 20.0f * log10f(ax[e]) : -100.0f;
+                    float sdb = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(lds.band_s[0]) + (bo[e] >> 1));
+                    float t = fmaxf(sdb, T.ath_db[16 * lane + e]) - 10.0f;
+                    k = (signal_db - t) > smr;
+                }
+                keep |= (k ? 1u : 0u) << e;
+            }
+        } else {
+            // keep iff |c| > thr, as the sign of thr - |c| (quantise<1, false>'s mask), shifted into the mask from element 15
+            // down: three instructions per element. The ordered compare of the lock-step stereo quantisers decides the same
+            // wherever it matters: the two differ only for |c| = inf against thr = inf and for a NaN coefficient, and both
+            // have rounded to zero (a band that holds an inf has the scale factor 30000 / inf = 0).
+#pragma unroll
+            for (int e = 15; e >= 0; e--)
+                keep = __builtin_amdgcn_alignbit(keep, __float_as_uint(max_raw(tb[e], al[e]) - ax[e]), 31);
+        }
+        const uint32_t tot = sparse_size_m(lane, nz & keep);
+        if (lane == j) mine = tot;
+    }
+    if (lane < n_q) atomicAdd(&sizes[(unsigned long long)clip * (unsigned)n_q + (unsigned)lane], mine);
+}
+
 // temporal recurrence s_t = max(a_t, 0.7 s_{t-1}), s_{-1} = 0 (psychoacoustic.rs:198-203) for the frame-parallel
 // form: blocks of 64 frames, one thread per (clip, block, channel, band), each warmed up over the 64 frames before its
 // block. History older than 64 frames can only contribute 0.7^64 (1e-10) of its level; levels below 4.77e-7 (half an
@@ -1872,6 +1994,15 @@ int launch_lossy_stream_scan(const LossyArgs &A, const float *seed, float *level
 int launch_lossy_scan(const LossyArgs &A, hipStream_t s) {
     unsigned max_hops = (unsigned)A.max_hops;
     hipLaunchKernelGGL(lossy_scan_kernel, dim3(A.n_clips, (max_hops + kScanBlock - 1) / kScanBlock), dim3(32 * A.nch), 0, s, A);
+    FLO_LAUNCH_CHECK();
+    return 0;
+}
+int launch_lossy_curve(const CurveArgs &C, const float *a_t, const float *s_prev, unsigned long long *sizes, hipStream_t s) {
+    if (C.n_q < 1 || C.n_q > kMaxCurveCandidates || C.A.nch < 1) return -1;
+    const unsigned long long waves = C.A.total_frames * (unsigned long long)C.A.nch;
+    if (!waves) return 0;
+    if (waves > 0x7FFFFFFFull) return -1;
+    hipLaunchKernelGGL(lossy_curve_kernel, dim3((unsigned)waves), dim3(64), 0, s, C, C.A.pcm, a_t, s_prev, sizes);
     FLO_LAUNCH_CHECK();
     return 0;
 }

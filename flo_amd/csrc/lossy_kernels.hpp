@@ -89,6 +89,20 @@ int launch_lossy_stream_scan(const LossyArgs &A, const float *seed, float *level
 // kernel by A.nch: 1, 2, 3..8 channels), and the temporal scan seeded from the streams' carried levels
 int launch_lossy_stream_pass(const LossyArgs &A, int pass, hipStream_t s);
 int launch_lossy_stream_scan(const LossyArgs &A, const float *seed, float *level_out, hipStream_t s);
+// Size curve (flo_batch_size_curve, rate.cpp): behind pass 1 and the temporal scan of the frame-parallel form, whose levels
+// do not depend on quality, lossy_curve_kernel prices every candidate quality from one transform of each frame. The
+// per-candidate constants are the host's, exactly as an encode at that quality gets them (build_lossy_tables).
+constexpr int kMaxCurveCandidates = 32;
+struct CurveArgs {
+    LossyArgs A;                                  // T (of any quality), the clip tables, nch, n_clips, total_frames
+    int n_q;                                      // candidates, 1 .. kMaxCurveCandidates
+    unsigned int exact_mask;                      // bit j: candidate j runs the exact-threshold branch (lossy_exact)
+    unsigned int qtrans_mask;                     // bit j: LossyDevTables::q_transparent of candidate j
+    float smr_thr[kMaxCurveCandidates];           // LossyDevTables::smr_thr of candidate j
+    const float4 *ath[kMaxCurveCandidates];       // rows kRowAth .. kRowAth + 3 of candidate j's pack: ath_lin, [4][64] float4
+};
+// sizes[clip * n_q + j] += the sparse bytes of every (frame, channel) of the clip at candidate j (integer atomics)
+int launch_lossy_curve(const CurveArgs &C, const float *a_t, const float *s_prev, unsigned long long *sizes, hipStream_t s);
 int launch_mdct_only(const LossyDevTables &T, const float *frames, unsigned long long n, float *out, hipStream_t s);
 int launch_quantise_smr(const LossyDevTables &T, const float *coeffs, const float *smr, unsigned long long n, short *q, float *sf,
                         hipStream_t s);

@@ -15,6 +15,8 @@
  *   error codes + flo_last_error <- FloResult<T> = Result<T, String>   (core/types.rs:281)
  *   flo_batch_fidelity / flo_compare <- no counterpart: the "compare original vs encoded" of the reference's TODO,
  *                            decoded audio against its source measured on the device (fidelity reports, below)
+ *   flo_batch_size_curve / flo_encode_batch_to_size <- no counterpart: where QualityPreset::from_bitrate (lossy/mod.rs) maps a
+ *                            bitrate to a preset, the file size at every candidate quality measured in one device pass
  *
  * Conventions mirror the reference: inputs are interleaved f32 PCM in [-1,1], length
  * n_interleaved = sample_frames * channels (a trailing partial sample-frame is ignored, as the reference's
@@ -376,6 +378,34 @@ int flo_batch_analyze_all(flo_batch *b, uint32_t peaks_per_second, flo_analysis 
 int flo_batch_analysis_metadata_all(flo_batch *b, uint32_t peaks_per_second, uint8_t **out, uint64_t *off);
 /* the bit depth a lossless batch's files declare (16 unless set; flo_encode_lossless's argument) */
 int flo_batch_set_bit_depth(flo_batch *b, uint8_t bit_depth);
+
+/* ---- size curves and the rate-targeted lossy encode (no counterpart: the reference maps a bitrate to one of five presets
+ * by the raw-PCM ratio, QualityPreset::from_bitrate, and never looks at the audio) ----------------------------------------
+ * Quality enters TransformEncoder only through the keep threshold of quantize_coefficients (encoder.rs:130-151), so one
+ * transform of the PCM prices every candidate quality: the sizes below are the exact lengths of the files an encode of
+ * the batch at that quality produces, without running the packer.
+ * flo_batch_size_curve: a lossy batch holding PCM (uploaded or filled; encoded or not): file_bytes[clip * n_q + j] = length
+ *   of the finished file (empty META) an encode of this batch at qualities[j] produces: 74 + 20 frames + DATA. 1 <= n_q <= 32.
+ *   Synchronous. The batch's own quality plays no part; the batch's encode state and results are untouched. The device
+ *   scratch is taken per call and processed in groups of clips that stay under FLO_SIZE_CURVE_GROUP_BYTES (default 256 MiB,
+ *   read per call). FLO_ERR_ARG for a lossless batch, n_q of 0 or above 32 and null pointers; FLO_ERR_STATE before any PCM
+ *   was uploaded.
+ * flo_batch_set_quality: re-point a lossy batch at another quality (the tables of (sample_rate, quality)); results of an
+ *   earlier encode are dropped (encode + sync again).
+ * flo_rate_pick: the candidate of the largest quality value (clamped like the encoder's: NaN -> 0, [0, 1]) whose size is
+ *   <= budget; every candidate is looked at, sizes need not grow with quality; equal quality values: the lower index.
+ *   *fits = 1. When none fits: the candidate of the smallest quality value, *fits = 0. No context needed.
+ * flo_encode_batch_to_size: host buffers in, one finished .flo per clip out (malloc'ed, flo_free), each at the best
+ *   candidate quality whose whole file (META included) fits target_bytes[i]; chosen[i] = candidate index, fits[i] as
+ *   flo_rate_pick. meta / meta_lens may be NULL (both). One upload, one curve, then every clip is encoded once, at its
+ *   chosen quality, in a batch per chosen candidate filled by device-to-device copies. Lossy only, 1 to 8 channels. */
+int flo_batch_size_curve(flo_batch *b, size_t n_q, const float *qualities, uint64_t *file_bytes);
+int flo_batch_set_quality(flo_batch *b, float quality);
+int flo_rate_pick(size_t n_q, const float *qualities, const uint64_t *sizes, uint64_t budget, uint32_t *index, int *fits);
+int flo_encode_batch_to_size(flo_ctx *ctx, size_t n_clips, const float *const *pcm, const size_t *n_interleaved,
+                             uint32_t sample_rate, uint8_t channels, size_t n_q, const float *qualities,
+                             const uint64_t *target_bytes, const uint8_t *const *meta, const size_t *meta_lens,
+                             uint8_t **outs, size_t *out_lens, uint32_t *chosen, int *fits);
 
 /* ---- spectral similarity: spectral_similarity (core/analysis.rs:395-437, exported as spectral_similarity_score,
  * lib.rs:1357) over fingerprint sets ----------------------------------------------------------------------------------
