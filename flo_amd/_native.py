@@ -41,6 +41,8 @@ EXPORTS = [
     "flo_spectral_similarity", "flo_fpindex_create", "flo_fpindex_destroy", "flo_fpindex_topk", "flo_fpindex_topk_self",
     "flo_fpindex_pairs", "flo_batch_fidelity", "flo_compare",
     "flo_batch_size_curve", "flo_batch_set_quality", "flo_rate_pick", "flo_encode_batch_to_size",
+    "flo_batch_encode_ladder", "flo_ladder_shape", "flo_ladder_file_bytes", "flo_ladder_fetch", "flo_ladder_device_files",
+    "flo_ladder_destroy", "flo_encode_batch_ladder",
 ]
 
 
@@ -242,5 +244,14 @@ def lib():
     L.flo_rate_pick.argtypes = [sz, vp, vp, C.c_uint64, u32p, C.POINTER(C.c_int)]
     L.flo_encode_batch_to_size.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.c_uint32, C.c_uint8, sz, vp, vp, C.POINTER(vp),
                                            C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), vp, vp]
+    L.flo_batch_encode_ladder.argtypes = [vp, sz, vp, C.POINTER(vp)]
+    L.flo_ladder_shape.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+    L.flo_ladder_file_bytes.argtypes = [vp, vp]
+    L.flo_ladder_fetch.argtypes = [vp, sz, sz, C.c_char_p, sz, C.POINTER(vp), C.POINTER(sz)]
+    L.flo_ladder_device_files.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint64))]
+    L.flo_ladder_destroy.argtypes = [vp]
+    L.flo_ladder_destroy.restype = None
+    L.flo_encode_batch_ladder.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.c_uint32, C.c_uint8, sz, vp, C.POINTER(vp),
+                                          C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
     _LIB = L
     return L

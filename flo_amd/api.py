@@ -449,6 +449,15 @@ class Batch:
         """re-point a lossy batch at another quality; results of an earlier encode are dropped"""
         self.ctx._chk(self._L.flo_batch_set_quality(self._h, quality))
 
+    def encode_ladder(self, qualities) -> "Ladder":
+        """flo_batch_encode_ladder: every clip of this lossy batch as a finished file at each of the K qualities, from one
+        transform pass over the PCM the batch holds (rung j of clip i is encode_lossy's file at qualities[j]); complete on
+        return. The batch's own quality plays no part and its results are untouched; the Ladder may outlive the batch"""
+        q = np.ascontiguousarray(qualities, dtype=np.float32).reshape(-1)
+        h = C.c_void_p()
+        self.ctx._chk(self._L.flo_batch_encode_ladder(self._h, q.size, q.ctypes.data, C.byref(h)))
+        return Ladder(self.ctx, h, [float(x) for x in q])
+
     def fetch(self, clip, metadata=b"") -> bytes:
         out, n = C.c_void_p(), C.c_size_t()
         self.ctx._chk(self._L.flo_batch_fetch(self._h, clip, metadata, len(metadata), C.byref(out), C.byref(n)))
@@ -492,6 +501,49 @@ class Batch:
         offs, sizes = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
         self.ctx._chk(self._L.flo_batch_device_streams(self._h, C.byref(base), C.byref(offs), C.byref(sizes)))
         return base.value, [offs[i] for i in range(self.n_clips)], [sizes[i] for i in range(self.n_clips)]
+
+
+class Ladder:
+    """flo_ladder: the files of a quality ladder (Batch.encode_ladder), resident on the device. Closed before its context."""
+
+    def __init__(self, ctx: Context, handle, qualities):
+        self.ctx, self._L, self._h = ctx, ctx._L, handle
+        self.qualities = list(qualities)
+        nc, nq = C.c_size_t(), C.c_size_t()
+        ctx._chk(self._L.flo_ladder_shape(handle, C.byref(nc), C.byref(nq)))
+        self.n_clips, self.n_rungs = nc.value, nq.value
+        self.file_bytes = np.zeros((self.n_clips, self.n_rungs), np.uint64)   # without META
+        ctx._chk(self._L.flo_ladder_file_bytes(handle, self.file_bytes.ctypes.data))
+        ctx._batches.add(self)
+
+    def fetch(self, clip, rung, metadata=b"") -> bytes:
+        out, n = C.c_void_p(), C.c_size_t()
+        self.ctx._chk(self._L.flo_ladder_fetch(self._h, clip, rung, metadata, len(metadata), C.byref(out), C.byref(n)))
+        return self.ctx._take(out, n)
+
+    def device_files(self, rung):
+        """(base, offsets, sizes) of one rung's files as they sit in device memory (no META); offsets are multiples of 16"""
+        base = C.c_void_p()
+        offs, sizes = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        self.ctx._chk(self._L.flo_ladder_device_files(self._h, rung, C.byref(base), C.byref(offs), C.byref(sizes)))
+        return base.value, [offs[i] for i in range(self.n_clips)], [sizes[i] for i in range(self.n_clips)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.flo_ladder_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 _default_ctx = None
@@ -1184,6 +1236,41 @@ def size_curve(samples, sample_rate, channels, qualities=DEFAULT_RATE_GRID) -> n
     try:
         b.upload(0, p)
         return b.size_curve(qualities)[0]
+    finally:
+        b.close()
+
+
+def encode_ladder(samples, sample_rate, channels, qualities, metadata=None):
+    """The clip at every quality of the ladder, from one upload, one analysis and one transform pass: a list of files, rung
+    j being what encode_lossy's route (_encode_analysed) returns at qualities[j], analysis META merged (a trailing partial
+    sample-frame is analysed as encode_lossy_many analyses it: over all of the caller's samples)"""
+    return encode_ladder_many([samples], sample_rate, channels, qualities, [metadata] if metadata is not None else None)[0]
+
+
+def encode_ladder_many(clips, sample_rate, channels, qualities, metadata=None):
+    """encode_ladder of every clip: one upload, ONE batched analysis, one ladder. metadata: None, one bytes for every clip, or
+    one entry per clip. Returns files[clip][rung]"""
+    from . import meta as _meta
+    ps = [_f32(x) for x in clips]
+    n = len(ps)
+    if metadata is None or isinstance(metadata, (bytes, bytearray)):
+        user = [bytes(metadata or b"")] * n
+    else:
+        user = [bytes(m or b"") for m in metadata]
+        if len(user) != n:
+            raise ValueError(f"metadata has {len(user)} entries for {n} clips")
+    q = np.ascontiguousarray(qualities, dtype=np.float32).reshape(-1)
+    if not ps:
+        return []
+    ctx = default_context()
+    b = Batch(ctx, MODE_LOSSY, [p.size for p in ps], sample_rate, channels, float(q[0]) if q.size else 0.0)
+    try:
+        for i, p in enumerate(ps):
+            ctx._chk(b._L.flo_batch_upload(b._h, i, p.ctypes.data))
+        b.sync()   # (the copies have read ps)
+        metas = [_meta.merge_analysis(user[i], m) for i, m in enumerate(b.analysis_metadata_all(50))]
+        with b.encode_ladder(q) as lad:
+            return [[lad.fetch(i, j, metas[i]) for j in range(lad.n_rungs)] for i in range(n)]
     finally:
         b.close()
 

@@ -5,6 +5,7 @@ printed fields for the parts that sit on this repository's path -
     encode  <in.wav> <out.flo> [--level N] [--lossy | --transform] [--quality low|medium|high|veryhigh|transparent]
                                [--bitrate KBPS] [--target-kbps KBPS]
     curve   <in.wav> [--json]
+    ladder  <in.wav> <outdir> --qualities Q0,Q1,... [--json]
     decode  <in.flo> <out.wav>
     info    <in.flo>
     validate <in.flo>
@@ -27,6 +28,8 @@ decoded tail past the source's end, per channel (flo_compare, include/flo_hip.h)
 `encode --lossy --target-kbps N` and `curve` (not in reflo) measure instead of mapping: the size of the file at every quality
 of a grid comes from one device pass over the audio (flo_batch_size_curve), and the encode takes the best quality whose whole
 file, META included, stays within N kbps over the clip's duration.
+`ladder` (not in reflo) writes the file at every quality of a list, <outdir>/<stem>.r<j>.flo for rung j, from one upload and
+one transform pass on the device (flo_batch_encode_ladder): each file is what `encode --lossy --quality Qj` writes.
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
 """
@@ -89,6 +92,32 @@ def curve_report(audio_bytes: bytes, qualities=api.DEFAULT_RATE_GRID) -> list:
     sizes = api.size_curve(samples, sr, ch, qualities)
     secs = samples.size / ch / sr
     return [{"quality": float(q), "bytes": int(b), "kbps": (int(b) * 8 / 1000 / secs) if secs else 0.0} for q, b in zip(qualities, sizes)]
+
+
+def parse_rungs(text: str) -> list:
+    """"low,high,transparent" -> [0.2, 0.6, 1.0]: the names `encode --quality` takes"""
+    out = []
+    for t in (x.strip().lower() for x in text.split(",")):
+        if t not in QUALITY:
+            raise ValueError(f"Invalid quality level: {t}. Use: low, medium, high, veryhigh, transparent")
+        out.append(QUALITY[t])
+    return out
+
+
+def ladder_from_audio(audio_bytes: bytes, qualities, ctx=None, title=None, artist=None, album=None, encoding_time=None) -> list:
+    """the WAV at every quality of the list, one file per rung, each with the META `encode --lossy --quality` writes"""
+    samples, sr, ch = read_wav_bytes(audio_bytes)
+    c = ctx or api.default_context()
+    fmt = _wav_source_format(audio_bytes)
+    p = api._f32(samples)
+    b = api.Batch(c, api.MODE_LOSSY, [p.size], sr, ch, 0.0)
+    try:
+        b.upload(0, p)
+        with b.encode_ladder(qualities) as lad:
+            return [lad.fetch(0, j, meta.cli_metadata(samples.size, sr, ch, fmt, True, min(max(float(q), 0.0), 1.0), None, 5, title,
+                                                      artist, album, encoding_time)) for j, q in enumerate(qualities)]
+    finally:
+        b.close()
 
 
 def get_metadata(flo_bytes: bytes):
@@ -253,6 +282,14 @@ def main(argv=None) -> int:
     cu = sub.add_parser("curve", help="File size at every quality of a grid, measured on the device")
     cu.add_argument("input")
     cu.add_argument("--json", action="store_true", help="Output as JSON")
+    la = sub.add_parser("ladder", help="Encode a WAV file at every quality of a list, from one transform pass")
+    la.add_argument("input")
+    la.add_argument("outdir")
+    la.add_argument("--qualities", required=True, help="Comma-separated rungs: low, medium, high, veryhigh, transparent")
+    la.add_argument("--json", action="store_true", help="Output as JSON")
+    la.add_argument("--title", default=None, help="Title metadata")
+    la.add_argument("--artist", default=None, help="Artist metadata")
+    la.add_argument("--album", default=None, help="Album metadata")
     a = ap.parse_args(argv)
     try:
         if a.command == "encode":
@@ -386,6 +423,30 @@ def main(argv=None) -> int:
                 print(f"{'quality':>8}  {'bytes':>12}  {'kbps':>9}")
                 for r in rows:
                     print(f"{r['quality']:8.4f}  {r['bytes']:12d}  {r['kbps']:9.1f}")
+        elif a.command == "ladder":
+            import os
+            try:
+                rungs = parse_rungs(a.qualities)
+            except ValueError as ex:
+                print(ex, file=sys.stderr)
+                return 1
+            audio = open(a.input, "rb").read()
+            samples, sr, ch = read_wav_bytes(audio)
+            files = ladder_from_audio(audio, rungs, None, a.title, a.artist, a.album)
+            os.makedirs(a.outdir, exist_ok=True)
+            stem = os.path.splitext(os.path.basename(a.input))[0]
+            secs = samples.size / ch / sr
+            rows = []
+            for j, (q, f) in enumerate(zip(rungs, files)):
+                path = os.path.join(a.outdir, f"{stem}.r{j}.flo")
+                open(path, "wb").write(f)
+                rows.append({"rung": j, "quality": float(q), "bytes": len(f), "kbps": (len(f) * 8 / 1000 / secs) if secs else 0.0})
+            if a.json:
+                print(json.dumps(rows, indent=2))
+            else:
+                print(f"{'rung':>4}  {'quality':>8}  {'bytes':>12}  {'kbps':>9}")
+                for r in rows:
+                    print(f"{r['rung']:4d}  {r['quality']:8.4f}  {r['bytes']:12d}  {r['kbps']:9.1f}")
         elif a.command == "similar":
             print(similar_report(a.inputs, a.k, a.threshold, a.json))
         elif a.command == "compare":

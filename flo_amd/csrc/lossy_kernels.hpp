@@ -103,6 +103,18 @@ struct CurveArgs {
 };
 // sizes[clip * n_q + j] += the sparse bytes of every (frame, channel) of the clip at candidate j (integer atomics)
 int launch_lossy_curve(const CurveArgs &C, const float *a_t, const float *s_prev, unsigned long long *sizes, hipStream_t s);
+// Quality ladder (flo_batch_encode_ladder, ladder.cpp; ladder_kernels.hip): behind the same pass 1 and scan, lossy_ladder_kernel packs every
+// frame at every rung (C's candidates) from one transform. C.A.slots: [n_q][total_frames][slot_bytes], C.A.frame_size:
+// [n_q][total_frames], C.A.slot_bytes >= lossy_slot_bytes(nch); sizes[rung * n_clips + clip] += the clip's DATA bytes at
+// that rung (zeroed by the caller). n_q * total_frames stays below 2^31.
+int launch_lossy_ladder(const CurveArgs &C, const float *a_t, const float *s_prev, unsigned long long *sizes, hipStream_t s);
+// ... and behind one launch_finish_files over all rungs of a group (files rung-major, `count` per rung), the header byte
+// that differs from rung to rung: the quality level (the flags' high byte) of file v is level[v / count]
+struct LadderLevels {
+    unsigned char level[kMaxCurveCandidates];
+};
+int launch_ladder_header_levels(uint8_t *out, const unsigned long long *data_off, const unsigned int *clip_frames, unsigned int count,
+                                unsigned int n_files, const LadderLevels &lv, hipStream_t s);
 int launch_mdct_only(const LossyDevTables &T, const float *frames, unsigned long long n, float *out, hipStream_t s);
 int launch_quantise_smr(const LossyDevTables &T, const float *coeffs, const float *smr, unsigned long long n, short *q, float *sf,
                         hipStream_t s);

@@ -407,6 +407,36 @@ int flo_encode_batch_to_size(flo_ctx *ctx, size_t n_clips, const float *const *p
                              const uint64_t *target_bytes, const uint8_t *const *meta, const size_t *meta_lens,
                              uint8_t **outs, size_t *out_lens, uint32_t *chosen, int *fits);
 
+/* ---- quality ladders: every clip of a lossy batch as a finished file at each of K qualities, from ONE transform pass -------
+ * The identity behind the size curve, taken to the bytes: window, MDCT, band statistics, masking chain, scale factors and
+ * round(c * sf) do not depend on quality, so a frame at quality q_j is the same integers under another keep mask, packed
+ * again. Rung j of clip i is, byte for byte, the file flo_encode_lossy makes of that clip at qualities[j].
+ * flo_batch_encode_ladder: a lossy batch holding PCM (uploaded or filled; encoded or not); 1 <= n_q <= 32; duplicate and
+ *   unordered qualities are allowed, every rung is a file of its own. Synchronous: the ladder is complete on return. The
+ *   batch's own quality plays no part and its encode state and results are untouched. Device scratch is taken per call
+ *   and the clips are processed in groups that stay under FLO_LADDER_GROUP_BYTES (default 4 GiB, read per call; a clip
+ *   larger than the limit is a group of its own; one host synchronisation per group). Afterwards only the finished files
+ *   stay resident: their exact bytes, each at a 16-byte aligned offset of one allocation. FLO_ERR_ARG for a lossless
+ *   batch, n_q of 0 or above 32 and null pointers; FLO_ERR_STATE before any PCM was uploaded; the context stays usable.
+ * A ladder holds its own device memory and nothing of the batch: it may outlive the batch it was made from. It must be
+ *   destroyed before its context.
+ * flo_ladder_file_bytes: file_bytes[clip * n_q + j], the length without META (what flo_batch_size_curve returns).
+ * flo_ladder_fetch: the file of (clip, rung), malloc'ed (flo_free), META appended and meta_size patched as flo_batch_fetch.
+ * flo_ladder_device_files: the files of one rung as they sit in HBM (no META): clip i at base + offsets[i] (multiples of
+ *   16), sizes[i] bytes; the arrays belong to the ladder.
+ * flo_encode_batch_ladder: host buffers in, n_clips * n_q finished files out (outs[clip * n_q + j], malloc'ed, flo_free);
+ *   clip i's META goes behind each of its rungs; meta / meta_lens may be NULL (both). One upload, one ladder. */
+typedef struct flo_ladder flo_ladder;
+int flo_batch_encode_ladder(flo_batch *b, size_t n_q, const float *qualities, flo_ladder **out);
+int flo_ladder_shape(const flo_ladder *l, size_t *n_clips, size_t *n_q);
+int flo_ladder_file_bytes(const flo_ladder *l, uint64_t *file_bytes);
+int flo_ladder_fetch(flo_ladder *l, size_t clip, size_t rung, const uint8_t *meta, size_t meta_len, uint8_t **out, size_t *out_len);
+int flo_ladder_device_files(flo_ladder *l, size_t rung, const uint8_t **base, const uint64_t **offsets, const uint64_t **sizes);
+void flo_ladder_destroy(flo_ladder *l);
+int flo_encode_batch_ladder(flo_ctx *ctx, size_t n_clips, const float *const *pcm, const size_t *n_interleaved,
+                            uint32_t sample_rate, uint8_t channels, size_t n_q, const float *qualities,
+                            const uint8_t *const *meta, const size_t *meta_lens, uint8_t **outs, size_t *out_lens);
+
 /* ---- spectral similarity: spectral_similarity (core/analysis.rs:395-437, exported as spectral_similarity_score,
  * lib.rs:1357) over fingerprint sets ----------------------------------------------------------------------------------
  * flo_fingerprint is SpectralFingerprint (analysis.rs:10-26): what flo_analyze / flo_batch_analyze_all return in those
