@@ -6,7 +6,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 
+#include "analysis_plan.hpp"
 #include "batch_internal.hpp"
 #include "devmem.hpp"
 
@@ -62,130 +64,36 @@ float max_rust(float a, float b) {
 }
 }  // namespace
 
-// K-weighting of a clip beyond one exact segment: two passes over short segments with the filter state handed over
-// exactly (analysis_kernels.hip, "K-weighting, long clips"); FLO_ANALYSIS_EXACT=1 keeps the one-lane walk (diagnostic)
-static bool analysis_fast_path(uint64_t frames, unsigned hop, unsigned ch) {
-    return frames > 65536 && hop && ch <= 64 && !getenv("FLO_ANALYSIS_EXACT");
-}
-// a clip's geometry: everything launch_analysis needs but its buffers, for the per-clip and the batched path alike
-// (block_len: the lengths of the 400 ms blocks, when asked for). Nothing but n_peaks for an empty clip, or when
-// peaks_only. `like`: a clip of the same rate whose geometry is made - its filter coefficients (and its M^L, for the same
-// segment length) are copied rather than computed again (the same values: the batched path's clips share one rate).
+// a clip's AnalysisArgs but its buffers, from its plan (analysis_plan.cpp); `plan` keeps the plan for a later clip's `like`
 static void analysis_geometry(AnalysisArgs &A, size_t n, uint32_t sr, uint8_t ch, uint32_t pps, std::vector<uint64_t> *block_len_out,
-                              bool peaks_only = false, const AnalysisArgs *like = nullptr) {
-    A.n = n;
-    A.sample_rate = sr;
-    A.channels = ch;
-    A.samples_per_peak = (double)sr / (double)pps;
-    if (n) {
-        const double tp = std::ceil((double)n / (A.samples_per_peak * (double)ch));
-        // peak windows that start inside the clip (analysis.rs:54-64: the loop breaks at the first one that does not)
-        unsigned np = 0;
-        const unsigned cap = tp > 0 ? (tp > 4e9 ? 4000000000u : (unsigned)tp) : 0u;
-        while (np < cap && (uint64_t)((double)np * A.samples_per_peak) * ch < n) np++;
-        A.n_peaks = np;
-    }
-    if (!n || peaks_only) return;
-    if (like && (!like->n || like->sample_rate != sr)) like = nullptr;
-    // K-weighting (ebu_r128.rs:51-103) and block geometry (:190-192, :236-262)
-    if (like) {
-        memcpy(A.shelf, like->shelf, sizeof A.shelf);
-        memcpy(A.hp, like->hp, sizeof A.hp);
-        A.hop = like->hop;
-    } else {
-        const double rate = (double)sr;
-        const double f0 = 1681.974450955533, g_db = 3.999843853973347, q = 0.7071752369554196;
-        const double k = std::tan(M_PI * f0 / rate), vh = std::pow(10.0, g_db / 20.0), vb = std::pow(vh, 0.4996667741545416);
-        const double a0 = 1.0 + k / q + k * k;
-        A.shelf[0] = (vh + vb * k / q + k * k) / a0;
-        A.shelf[1] = 2.0 * (k * k - vh) / a0;
-        A.shelf[2] = (vh - vb * k / q + k * k) / a0;
-        A.shelf[3] = 2.0 * (k * k - 1.0) / a0;
-        A.shelf[4] = (1.0 - k / q + k * k) / a0;
-        const double f0h = 38.13547087602444, qh = 0.5003270373238773, kh = std::tan(M_PI * f0h / rate);
-        const double a0h = 1.0 + kh / qh + kh * kh;
-        A.hp[0] = 1.0;
-        A.hp[1] = -2.0;
-        A.hp[2] = 1.0;
-        A.hp[3] = 2.0 * (kh * kh - 1.0) / a0h;
-        A.hp[4] = (1.0 - kh / qh + kh * kh) / a0h;
-        A.hop = (unsigned)std::llround(rate * 0.1);
-    }
-    const uint64_t frames = n / ch;
-    std::vector<uint64_t> block_len;   // (ebu_r128.rs:236-262)
-    if (A.hop) {
-        uint64_t start = 0;
-        const uint64_t block = (uint64_t)A.hop * 4;
-        while (start < frames) {
-            const uint64_t end = start + block < frames ? start + block : frames;
-            if (end <= start) break;
-            block_len.push_back(end - start);
-            if (end == frames) break;
-            start += A.hop;
-        }
-    }
-    A.n_blocks = (unsigned)block_len.size();
-    // segments of the order-bound scans (analysis_kernels.hip): a block must not span more than two of them, and the
-    // warm-up is a quarter of a second (the 38 Hz high-pass has decayed by exp(-59) then)
-    A.seg_frames = 65536u > 8u * A.hop ? 65536u : 8u * A.hop;
-    A.warm_frames = 8192u > sr / 4u ? 8192u : sr / 4u;
-    {
-        const uint64_t longest = (n + ch - 1) / ch;   // samples of channel 0 (a trailing partial frame counts for the FIR)
-        A.n_seg = (unsigned)((longest + A.seg_frames - 1) / A.seg_frames);
-        if (A.n_seg == 0) A.n_seg = 1;
-    }
-    A.fast = analysis_fast_path(frames, A.hop, ch) ? 1u : 0u;
-    // segment length: two walks of L frames (150 ns per frame) against a scan over frames / L segments (35 ns each):
-    // the power of two next to sqrt(frames / 8), between 256 and 2048
-    A.kseg_frames = 256;
-    while (A.kseg_frames < 2048 && (uint64_t)A.kseg_frames * A.kseg_frames * 8 < frames) A.kseg_frames *= 2;
-    A.n_kseg = (unsigned)((frames + A.kseg_frames - 1) / A.kseg_frames);
-    A.kq = A.hop ? A.kseg_frames / A.hop + 2 : 1;
-    if (A.fast && like && like->fast && like->kseg_frames == A.kseg_frames) {
-        memcpy(A.kpow, like->kpow, sizeof A.kpow);
-    } else if (A.fast) {
-        // M^L: the homogeneous system (x = 0) walked L steps from each unit state, in the kernels' own arithmetic
-        for (int col = 0; col < 4; col++) {
-            double v[4] = {0, 0, 0, 0};
-            v[col] = 1.0;
-            for (unsigned i = 0; i < A.kseg_frames; i++) {
-                const double y = v[0];
-                const double n1 = -A.shelf[3] * y + v[1], n2 = -A.shelf[4] * y;
-                const double y2 = A.hp[0] * y + v[2];
-                const double m1 = A.hp[1] * y - A.hp[3] * y2 + v[3], m2 = A.hp[2] * y - A.hp[4] * y2;
-                v[0] = n1, v[1] = n2, v[2] = m1, v[3] = m2;
-            }
-            for (int r = 0; r < 4; r++) A.kpow[4 * r + col] = v[r];
-        }
-    }
-    A.sq_seg = 1u << 16;
-    A.n_sq_seg = (unsigned)((n + A.sq_seg - 1) / A.sq_seg);
-    // beyond one segment the sum of squares is chained chunk by chunk so that it IS the sequential f32 sum (analysis_kernels.hip)
-    A.sq_exact = n > A.sq_seg ? 1u : 0u;
-    A.n_sq_chunks = (n + 1023) / 1024;
-    if (A.sq_exact) A.n_sq_seg = 1;
-    if (like) {
-        memcpy(A.tp_coef, like->tp_coef, sizeof A.tp_coef);
-    } else {   // compute_true_peak's filter (ebu_r128.rs:117-140): 49-tap Hann-windowed sinc, designed at 4 fs, unit sum
-        const double oversample_rate = (double)sr * 4.0, cutoff = (double)sr * 0.45, center = 24.0;
-        double sum = 0.0;
-        for (int i = 0; i < 49; i++) {
-            const double nn = (double)i - center;
-            const double sinc = std::fabs(nn) < 1e-12 ? 2.0 * cutoff / oversample_rate : std::sin(2.0 * cutoff * nn / oversample_rate) / (M_PI * nn);
-            const double window = 0.5 * (1.0 - std::cos(2.0 * M_PI * (double)i / 48.0));
-            A.tp_coef[i] = sinc * window;
-        }
-        for (int i = 0; i < 49; i++) sum += A.tp_coef[i];
-        for (int i = 0; i < 49; i++) A.tp_coef[i] /= sum;
-    }
-    A.n_chunks = (9ull + 4ull * n + 1023ull) / 1024ull;
-    const uint64_t spc = n / ch;
-    const uint64_t pts[3] = {spc / 4, spc / 2, spc * 3 / 4};
-    for (int i = 0; i < 3; i++) {
-        A.points[i] = pts[i];
-        A.point_ok[i] = pts[i] + 256 < spc ? 1u : 0u;
-    }
-    if (block_len_out) *block_len_out = std::move(block_len);
+                              bool peaks_only = false, const AnalysisPlan *like = nullptr, AnalysisPlan *plan = nullptr) {
+    AnalysisPlan P;
+    analysis_plan(P, n, sr, ch, pps, block_len_out, peaks_only, like);
+    A.n = P.n;
+    A.sample_rate = P.sample_rate;
+    A.channels = P.channels;
+    A.samples_per_peak = P.samples_per_peak;
+    A.n_peaks = P.n_peaks;
+    memcpy(A.shelf, P.shelf, sizeof A.shelf);
+    memcpy(A.hp, P.hp, sizeof A.hp);
+    A.hop = P.hop;
+    A.n_blocks = P.n_blocks;
+    A.seg_frames = P.seg_frames;
+    A.warm_frames = P.warm_frames;
+    A.n_seg = P.n_seg;
+    A.sq_seg = P.sq_seg;
+    A.n_sq_seg = P.n_sq_seg;
+    A.fast = P.fast;
+    A.kseg_frames = P.kseg_frames;
+    A.n_kseg = P.n_kseg;
+    A.kq = P.kq;
+    memcpy(A.kpow, P.kpow, sizeof A.kpow);
+    A.sq_exact = P.sq_exact;
+    A.n_sq_chunks = P.n_sq_chunks;
+    memcpy(A.tp_coef, P.tp_coef, sizeof A.tp_coef);
+    A.n_chunks = P.n_chunks;
+    for (int i = 0; i < 3; i++) A.points[i] = P.points[i], A.point_ok[i] = P.point_ok[i];
+    if (plan) *plan = P;
 }
 // twiddles of the 256-point FFT: cos / sin in double, rounded to f32 (the values the oracle's FFT uses)
 constexpr size_t kAnTwBytes = 8 * 128 * 2 * sizeof(float);
@@ -333,10 +241,10 @@ struct AnExtents {
     }
 };
 // The per-clip path's result block: peaks | sum of squares [n_sq_seg] | peak bits [2] | block sums | twiddles | band
-// [3][16] | bin [3][8] | quanta || filter states | chunk records | maxima. Zeroed before the launch and read back behind
+// [3][16] | bin [3][8] | quanta || filter states (start, refinement end) | chunk records | maxima. Zeroed before the launch and read back behind
 // it up to `kst`: what lies behind is fully written by its kernels and stays on the device.
 struct AnClipLayout {
-    size_t peaks, sumsq, pk, blocks, tw, band, bin, kq, kst, sqd, sqr, pkp, bytes, cvs_bytes;
+    size_t peaks, sumsq, pk, blocks, tw, band, bin, kq, kst, kst2, sqd, sqr, pkp, bytes, cvs_bytes;
     explicit AnClipLayout(const AnalysisArgs &A) {
         const AnExtents E(A);
         peaks = 0;
@@ -348,7 +256,8 @@ struct AnClipLayout {
         bin = band + 3 * 16 * 4;
         kq = al16(bin + 3 * 8 * 4);
         kst = kq + E.kq;
-        sqd = kst + E.kstate;
+        kst2 = kst + E.kstate;
+        sqd = kst2 + E.kstate;
         sqr = sqd + E.sqd;
         pkp = sqr + E.sqr;
         bytes = pkp + E.pkp;
@@ -365,6 +274,7 @@ struct AnClipLayout {
         A.peak_bin = (unsigned int *)(rb + bin);
         A.kqpart = (double *)(rb + kq);
         A.kstate = (double *)(rb + kst);
+        A.kstate2 = (double *)(rb + kst2);
         A.sq_dsum = (double *)(rb + sqd);
         A.sq_rec = (double *)(rb + sqr);
         A.peak_part = (double *)(rb + pkp);
@@ -387,14 +297,15 @@ struct AnResLayout {
 };
 // the batched path, one clip's scratch: zeroed before the group (block sums, quanta) | not (filter states, chunk records, maxima, hash)
 struct AnScratch {
-    size_t blocks, kq, zbytes, kst, sqd, sqr, pkp, cvs, ubytes;
+    size_t blocks, kq, zbytes, kst, kst2, sqd, sqr, pkp, cvs, ubytes;
     explicit AnScratch(const AnalysisArgs &A) {
         const AnExtents E(A);
         blocks = 0;
         kq = al16(A.fast ? 0 : E.blocks);
         zbytes = al16(kq + E.kq);
         kst = 0;
-        sqd = al16(E.kstate);
+        kst2 = al16(E.kstate);
+        sqd = al16(kst2 + E.kstate);
         sqr = al16(sqd + E.sqd);
         pkp = al16(sqr + E.sqr);
         cvs = al16(pkp + E.pkp);
@@ -493,6 +404,28 @@ static int analyze_impl(flo_ctx *c, const float *pcm, const float *pcm_dev, size
                     fastpart[((size_t)cc * A.n_blocks + k) * 2] = e;
                 }
             part = fastpart.data();
+        }
+        std::vector<double> poisoned;
+        if (!A.fast && A.n_seg > 1) {
+            // Warm-up segments: a later segment restarts its filters from zero a warm-up ahead of its first frame, so a sample
+            // that is not finite (or a filter that has overflowed) in an earlier segment - which the sequential recurrence
+            // never recovers from: every later output is NaN - is forgotten there. The first segment with a share that is not
+            // finite tells: every share a later segment wrote becomes NaN (anb_block_energy_kernel does the same).
+            poisoned.assign(part, part + (size_t)ch * A.n_blocks * 2);
+            for (unsigned cc = 0; cc < ch; cc++) {
+                double *pc = poisoned.data() + (size_t)cc * A.n_blocks * 2;
+                uint64_t first = UINT64_MAX;   // the first segment that wrote a share that is not finite
+                for (unsigned k = 0; k < A.n_blocks; k++)
+                    for (unsigned slot = 0; slot < 2; slot++)
+                        if (!std::isfinite(pc[2 * k + slot])) first = std::min<uint64_t>(first, (uint64_t)k * A.hop / A.seg_frames + slot);
+                if (first == UINT64_MAX) continue;
+                const uint64_t behind = (first + 1) * A.seg_frames;   // the first frame of the segments that forgot
+                for (unsigned k = 0; k < A.n_blocks; k++) {
+                    const uint64_t start = (uint64_t)k * A.hop, end = start + block_len[k];
+                    if (end > behind) pc[2 * k + (start >= behind ? 0 : 1)] = std::numeric_limits<double>::quiet_NaN();
+                }
+            }
+            part = poisoned.data();
         }
         for (unsigned k = 0; k < A.n_blocks; k++) {
             double e = 0.0;
@@ -649,11 +582,12 @@ extern "C" int flo_batch_analyze_all(flo_batch *b, uint32_t pps, flo_analysis *o
     const size_t cap = batch_analysis_group_bytes();
     const unsigned long long max_items = 1ull << 22;   // workgroups per launch (a single clip may have more, as alone)
     size_t stage_floats = 0;
-    const AnalysisArgs *like = nullptr;   // (the last clip with samples: its rate's coefficients are reused)
+    AnalysisPlan plan, like_plan;
+    const AnalysisPlan *like = nullptr;   // (the last clip with samples: its rate's coefficients are reused)
     for (size_t i = 0; i < n_clips; i++) {
         A[i] = AnalysisArgs{};
-        analysis_geometry(A[i], b->n_il[i], b->sr, b->ch, pps, nullptr, false, like);
-        if (A[i].n) like = &A[i];
+        analysis_geometry(A[i], b->n_il[i], b->sr, b->ch, pps, nullptr, false, like, &plan);
+        if (A[i].n) like_plan = plan, like = &like_plan;
         res_off[i + 1] = res_off[i] + AnResLayout(A[i]).bytes;
         if (i < b->tail.size() && !b->tail[i].empty()) {   // an odd-length lossy clip: staged whole (frames, then the tail)
             stage_off[i] = stage_floats;
@@ -719,6 +653,7 @@ extern "C" int flo_batch_analyze_all(flo_batch *b, uint32_t pps, flo_analysis *o
             a.block_part = (double *)(z + S.blocks);
             a.kqpart = (double *)(z + S.kq);
             a.kstate = (double *)(u + S.kst);
+            a.kstate2 = (double *)(u + S.kst2);
             a.sq_dsum = (double *)(u + S.sqd);
             a.sq_rec = (double *)(u + S.sqr);
             a.peak_part = (double *)(u + S.pkp);

@@ -84,7 +84,7 @@ __global__ __launch_bounds__(64) void anb_kw_pass_kernel(AN_BATCH_PARAMS) {
     const unsigned cnt = have ? (unsigned)(f0 + L < frames ? L : frames - f0) : 0u;   // frames of this segment
     double *st = A.kstate + ((unsigned long long)c * A.n_kseg + s) * 4;
     double s1 = 0, s2 = 0, h1 = 0, h2 = 0;
-    if (PASS == 2 && have) s1 = st[0], s2 = st[1], h1 = st[2], h2 = st[3];
+    if (PASS >= 2 && have) s1 = st[0], s2 = st[1], h1 = st[2], h2 = st[3];
     const double b0 = A.shelf[0], b1 = A.shelf[1], b2 = A.shelf[2], a1 = A.shelf[3], a2 = A.shelf[4];
     const double c0 = A.hp[0], c1 = A.hp[1], c2 = A.hp[2], d1 = A.hp[3], d2 = A.hp[4];
     const unsigned hop = A.hop;
@@ -124,12 +124,16 @@ __global__ __launch_bounds__(64) void anb_kw_pass_kernel(AN_BATCH_PARAMS) {
     }
     if (!have) return;
     if (PASS == 1) st[0] = s1, st[1] = s2, st[2] = h1, st[3] = h2;
-    else if (cnt) qp[slot] = acc;
+    else if (PASS == 3) {   // the refinement walk's end state (an_kw_scan_body)
+        double *st2 = A.kstate2 + ((unsigned long long)c * A.n_kseg + s) * 4;
+        st2[0] = s1, st2[1] = s2, st2[2] = h1, st2[3] = h2;
+    } else if (cnt) qp[slot] = acc;
 }
+template <bool REFINE>
 __global__ __launch_bounds__(64) void anb_kw_scan_kernel(AN_BATCH_PARAMS) {
     unsigned it;
     const AnalysisArgs &A = an_clip(clips, pre, n_clips, kAnlKScan, it);
-    an_kw_scan_body(A, it);
+    an_kw_scan_body<REFINE>(A, it);
 }
 __device__ __forceinline__ unsigned an_tiles(const AnalysisArgs &A) {
     const unsigned long long longest = (A.n + A.channels - 1) / A.channels;
@@ -254,6 +258,29 @@ __global__ __launch_bounds__(64) void anb_block_energy_kernel(AN_BATCH_PARAMS) {
     const unsigned ch = A.channels, hop = A.hop;
     const unsigned long long frames = A.n / ch, L = A.kseg_frames;
     const unsigned long long nq = hop ? (frames + hop - 1) / hop : 0;
+    // Warm-up segments (the host's rule, analyze_impl): the first segment of a channel that wrote a share that is not finite
+    // - a sample that is not finite, a filter that has overflowed: the sequential recurrence never recovers - makes every
+    // share a later segment wrote NaN (those restarted their filters from zero and forgot it).
+    __shared__ unsigned first_bad[256];   // per channel (channels is a byte); ~0u: none
+    const bool warm = !A.fast && A.n_seg > 1;   // (uniform)
+    if (warm) {
+        for (unsigned cc = 0; cc < ch; cc++) {
+            unsigned first = 0xFFFFFFFFu;
+            const double *pc = A.block_part + (unsigned long long)cc * A.n_blocks * 2;
+            for (unsigned k = threadIdx.x; k < A.n_blocks; k += 64)
+                for (unsigned slot = 0; slot < 2; slot++) {
+                    const double v = pc[2ull * k + slot];
+                    const unsigned sg = (unsigned)((unsigned long long)k * hop / A.seg_frames) + slot;
+                    if (!(fabs(v) <= 1.7976931348623157e308) && sg < first) first = sg;
+                }
+            for (int o = 32; o; o >>= 1) {
+                const unsigned other = (unsigned)__shfl_xor((int)first, o);
+                first = other < first ? other : first;
+            }
+            if (threadIdx.x == 0) first_bad[cc] = first;
+        }
+        __syncthreads();
+    }
     for (unsigned k = threadIdx.x; k < A.n_blocks; k += 64) {
         const unsigned long long start = (unsigned long long)k * hop;
         const unsigned long long end = start + 4ull * hop < frames ? start + 4ull * hop : frames;
@@ -276,6 +303,14 @@ __global__ __launch_bounds__(64) void anb_block_energy_kernel(AN_BATCH_PARAMS) {
                 const double *pp = A.block_part + ((unsigned long long)cc * A.n_blocks + k) * 2;
                 p0 = pp[0];
                 p1 = pp[1];
+                if (warm && first_bad[cc] != 0xFFFFFFFFu) {
+                    const unsigned long long behind = (first_bad[cc] + 1ull) * A.seg_frames;   // the first frame of the segments that forgot
+                    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+                    if (end > behind) {
+                        if (start >= behind) p0 = nan;
+                        else p1 = nan;
+                    }
+                }
             }
             e += (p0 + p1) / (double)(end - start);
         }
@@ -306,7 +341,11 @@ int launch_analysis_batch(const AnBatchArgs &G, const unsigned long long (&total
     if (total[kAnlKw]) {
         hipLaunchKernelGGL(anb_kw_pass_kernel<1>, grid(kAnlKw), dim3(64), 0, s, G.clips, G.pre, G.n_clips);
         AN_LAUNCH_CHECK();
-        hipLaunchKernelGGL(anb_kw_scan_kernel, grid(kAnlKScan), dim3(64), 0, s, G.clips, G.pre, G.n_clips);
+        hipLaunchKernelGGL(anb_kw_scan_kernel<false>, grid(kAnlKScan), dim3(64), 0, s, G.clips, G.pre, G.n_clips);
+        AN_LAUNCH_CHECK();
+        hipLaunchKernelGGL(anb_kw_pass_kernel<3>, grid(kAnlKw), dim3(64), 0, s, G.clips, G.pre, G.n_clips);
+        AN_LAUNCH_CHECK();
+        hipLaunchKernelGGL(anb_kw_scan_kernel<true>, grid(kAnlKScan), dim3(64), 0, s, G.clips, G.pre, G.n_clips);
         AN_LAUNCH_CHECK();
         hipLaunchKernelGGL(anb_kw_pass_kernel<2>, grid(kAnlKw), dim3(64), 0, s, G.clips, G.pre, G.n_clips);
         AN_LAUNCH_CHECK();

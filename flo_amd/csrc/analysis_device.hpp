@@ -203,7 +203,8 @@ __device__ __forceinline__ void an_loud_body(const AnalysisArgs &A, unsigned seg
 // L = 2048 frames instead of one of 65 536 + 11 025: the 10 ms this stage took per clip whatever its length become 0.3 ms.
 // Against the sequential recurrence the start states differ by rounding (1e-16 relative, decaying with the filters'
 // memory) and a block is the sum of its four quanta, themselves sums of the segments' shares, instead of one running sum:
-// the block energies agree to ~1e-15, the f32 loudness of the META chunk is the same. Clips up to 65 536 frames keep the
+// the block energies agree to ~1e-15 once the start states have had their one step of refinement (an_kw_scan_body: a third
+// walk, pass 3, and a second scan), the f32 loudness of the META chunk is the same. Clips up to 65 536 frames keep the
 // one-lane walk in the reference's own order (an_loud_kernel): bit for bit.
 template <int PASS>
 __device__ __forceinline__ void an_kw_pass_body(const AnalysisArgs &A, unsigned sblk, unsigned c) {
@@ -215,7 +216,7 @@ __device__ __forceinline__ void an_kw_pass_body(const AnalysisArgs &A, unsigned 
     const unsigned cnt = (unsigned)(f0 + A.kseg_frames < frames ? A.kseg_frames : frames - f0);   // frames of this segment
     double *st = A.kstate + ((unsigned long long)c * A.n_kseg + s) * 4;
     double s1 = 0, s2 = 0, h1 = 0, h2 = 0;
-    if (PASS == 2) s1 = st[0], s2 = st[1], h1 = st[2], h2 = st[3];
+    if (PASS >= 2) s1 = st[0], s2 = st[1], h1 = st[2], h2 = st[3];
     const double b0 = A.shelf[0], b1 = A.shelf[1], b2 = A.shelf[2], a1 = A.shelf[3], a2 = A.shelf[4];
     const double c0 = A.hp[0], c1 = A.hp[1], c2 = A.hp[2], d1 = A.hp[3], d2 = A.hp[4];
     const unsigned hop = A.hop;
@@ -253,10 +254,21 @@ __device__ __forceinline__ void an_kw_pass_body(const AnalysisArgs &A, unsigned 
         }
     }
     if (PASS == 1) st[0] = s1, st[1] = s2, st[2] = h1, st[3] = h2;
-    else if (cnt) qp[slot] = acc;
+    else if (PASS == 3) {   // the refinement walk: where this segment ends when it starts from its scanned start state
+        double *st2 = A.kstate2 + ((unsigned long long)c * A.n_kseg + s) * 4;
+        st2[0] = s1, st2[1] = s2, st2[2] = h1, st2[3] = h2;
+    } else if (cnt) qp[slot] = acc;
 }
 // start states: v_0 = 0, v_{s+1} = M^L v_s + z_s (z_s = what pass 1 left). One wave per channel: 64 segments' z at a time
 // (one coalesced read), handed to the chain by shuffles; each lane keeps the start state of its segment and writes it back.
+// REFINE: pass 1 walks from a ZERO state, so its values are the signal's plus the response to the missing start state - at
+// high rates the high-pass is all but a double pole at z = 1 - 2 pi 38 / fs and that response grows like k r^k (135 times
+// the state at 96 kHz and k = 256): z_s carries roundings of that size and M^L v_s + z_s cancels them against each other
+// (a 440 Hz tone at 96 kHz: block energies 3.3e-14 off a long-double reference where the sequential f64 sum is 4.5e-15
+// off). One step of iterative refinement removes it: every segment is walked again from its scanned start state (pass 3,
+// at the signal's own magnitude, end states w_s), and the same chain run on the defects, c_0 = 0,
+// c_{s+1} = M^L c_s + (w_s - v_{s+1}), gives the corrections v_s += c_s (the walk is linear: W_s(v + c) = W_s(v) + M^L c).
+template <bool REFINE>
 __device__ __forceinline__ void an_kw_scan_body(const AnalysisArgs &A, unsigned c) {
     const unsigned lane = threadIdx.x;
     double v0 = 0, v1 = 0, v2 = 0, v3 = 0;
@@ -267,7 +279,13 @@ __device__ __forceinline__ void an_kw_scan_body(const AnalysisArgs &A, unsigned 
     for (unsigned long long s0 = 0; s0 < A.n_kseg; s0 += 64) {
         const unsigned long long mine = s0 + lane;
         const bool have = mine < A.n_kseg;
-        const double z0 = have ? st[4 * mine] : 0.0, z1 = have ? st[4 * mine + 1] : 0.0, z2 = have ? st[4 * mine + 2] : 0.0, z3 = have ? st[4 * mine + 3] : 0.0;
+        double z0 = 0.0, z1 = 0.0, z2 = 0.0, z3 = 0.0;
+        if (!REFINE) {
+            if (have) z0 = st[4 * mine], z1 = st[4 * mine + 1], z2 = st[4 * mine + 2], z3 = st[4 * mine + 3];
+        } else if (mine + 1 < A.n_kseg) {   // the defect between this segment's end and the next one's start (read before any lane corrects it)
+            const double *w = A.kstate2 + ((unsigned long long)c * A.n_kseg + mine) * 4, *nx = st + 4 * (mine + 1);
+            z0 = w[0] - nx[0], z1 = w[1] - nx[1], z2 = w[2] - nx[2], z3 = w[3] - nx[3];
+        }
         double k0 = 0, k1 = 0, k2 = 0, k3 = 0;
         const unsigned cnt = A.n_kseg - s0 < 64 ? (unsigned)(A.n_kseg - s0) : 64u;
         for (unsigned jj = 0; jj < cnt; jj++) {
@@ -287,7 +305,10 @@ __device__ __forceinline__ void an_kw_scan_body(const AnalysisArgs &A, unsigned 
             const double w3 = fma(P[12], v0, fma(P[13], v1, fma(P[14], v2, fma(P[15], v3, y3))));
             v0 = w0, v1 = w1, v2 = w2, v3 = w3;
         }
-        if (have) st[4 * mine] = k0, st[4 * mine + 1] = k1, st[4 * mine + 2] = k2, st[4 * mine + 3] = k3;
+        if (have) {
+            if (REFINE) k0 += st[4 * mine], k1 += st[4 * mine + 1], k2 += st[4 * mine + 2], k3 += st[4 * mine + 3];
+            st[4 * mine] = k0, st[4 * mine + 1] = k1, st[4 * mine + 2] = k2, st[4 * mine + 3] = k3;
+        }
     }
 }
 // sample peak and true-peak FIR of the whole clip (order-free: every output is its own sum, taps in the reference's order).

@@ -27,7 +27,8 @@ __global__ __launch_bounds__(64) void an_peaks_kernel(AnalysisArgs A) { an_peaks
 __global__ __launch_bounds__(128) void an_loud_kernel(AnalysisArgs A) { an_loud_body(A, blockIdx.x, blockIdx.y); }
 template <int PASS>
 __global__ __launch_bounds__(64) void an_kw_pass_kernel(AnalysisArgs A) { an_kw_pass_body<PASS>(A, blockIdx.x, blockIdx.y); }
-__global__ __launch_bounds__(64) void an_kw_scan_kernel(AnalysisArgs A) { an_kw_scan_body(A, blockIdx.x); }
+template <bool REFINE>
+__global__ __launch_bounds__(64) void an_kw_scan_kernel(AnalysisArgs A) { an_kw_scan_body<REFINE>(A, blockIdx.x); }
 __global__ __launch_bounds__(256) void an_peak_kernel(AnalysisArgs A) { an_peak_body(A, blockIdx.x, blockIdx.y, gridDim.x); }
 __global__ __launch_bounds__(256) void an_peak_reduce_kernel(AnalysisArgs A, unsigned long long n_part) { an_peak_reduce_body(A, n_part); }
 __global__ __launch_bounds__(64) void an_sq_dsum_kernel(AnalysisArgs A) { an_sq_dsum_body(A, blockIdx.x); }
@@ -56,7 +57,12 @@ int launch_analysis(const AnalysisArgs &A, hipStream_t s, const AnalysisSide *si
         if (A.fast) {
             hipLaunchKernelGGL(an_kw_pass_kernel<1>, dim3((A.n_kseg + 63) / 64, A.channels), dim3(64), 0, s, A);
             AN_LAUNCH_CHECK();
-            hipLaunchKernelGGL(an_kw_scan_kernel, dim3(A.channels), dim3(64), 0, s, A);
+            hipLaunchKernelGGL(an_kw_scan_kernel<false>, dim3(A.channels), dim3(64), 0, s, A);
+            AN_LAUNCH_CHECK();
+            // one refinement of the start states (an_kw_scan_body)
+            hipLaunchKernelGGL(an_kw_pass_kernel<3>, dim3((A.n_kseg + 63) / 64, A.channels), dim3(64), 0, s, A);
+            AN_LAUNCH_CHECK();
+            hipLaunchKernelGGL(an_kw_scan_kernel<true>, dim3(A.channels), dim3(64), 0, s, A);
             AN_LAUNCH_CHECK();
             hipLaunchKernelGGL(an_kw_pass_kernel<2>, dim3((A.n_kseg + 63) / 64, A.channels), dim3(64), 0, s, A);
             AN_LAUNCH_CHECK();

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "analysis_plan.hpp"
+
 namespace flo {
 
 struct AnalysisArgs {
@@ -28,6 +30,7 @@ struct AnalysisArgs {
     unsigned int kseg_frames, n_kseg, kq;   // frames per short segment, segments per channel, hop-quantum slots per segment
     double kpow[16];             // the filters' 4 x 4 state transition over kseg_frames steps (row-major)
     double *kstate;              // [channels][n_kseg][4]: pass 1 leaves zero-state END states, the scan turns them into START states
+    double *kstate2;             // [channels][n_kseg][4]: the END states of the refinement walk from those start states
     double *kqpart;              // [channels][n_kseg][kq]: pass 2, the segment's share of the 100 ms quanta it overlaps
     // The f32 sum of squares of clips beyond one segment: chunks of 1024 samples summed in parallel and chained so that the
     // result IS the sequential f32 sum, bit for bit (see "sum of squares, long clips" in analysis_kernels.hip)
@@ -71,50 +74,7 @@ int launch_analysis(const AnalysisArgs &A, hipStream_t s, const AnalysisSide *si
 // L, pre[L * (n_clips + 1) + i] is the number of workgroups of the clips in front of clip i (a workgroup takes
 // an_batch_per_wg(L) items of one clip in turn), and a workgroup finds its clip by binary search. The steps one workgroup walks alone for one clip (the hash tree, the sum-of-squares prefix and chain,
 // the K-weighting scan, the peak reduce) become one workgroup per clip.
-constexpr int kAnTile = 2048;   // frames per tile (an_loud, an_peak)
-enum AnList : int {
-    kAnlPeaks,     // n_peaks: one wave per peak window
-    kAnlLoud,      // clips of at most one exact segment: n_seg x channels
-    kAnlKw,        // longer clips: ceil(n_kseg / 64) x channels (K-weighting passes 1 and 2)
-    kAnlKScan,     // longer clips: channels
-    kAnlTile,      // longer clips: true / sample peak tiles x channels
-    kAnlFast1,     // longer clips: 1 (peak reduce)
-    kAnlSqChunk,   // sum of squares beyond one segment: n_sq_chunks
-    kAnlSq1,       // sum of squares beyond one segment: 1 (prefix, chain)
-    kAnlSumsq,     // sum of squares within one segment: n_sq_seg
-    kAnlB3,        // BLAKE3 chunks: ceil(n_chunks / 128)
-    kAnlClip,      // every clip with samples: 1 (hash tree, block energies)
-    kAnlFft,       // every clip with samples: 3
-    kAnlCount
-};
-// items of every list for one clip (host and device agree on the geometry through this one function)
-__host__ __device__ inline void an_batch_items(const AnalysisArgs &A, unsigned long long (&it)[kAnlCount]) {
-    for (int k = 0; k < kAnlCount; k++) it[k] = 0;
-    if (!A.n) return;
-    const unsigned long long ch = A.channels, longest = (A.n + ch - 1) / ch;
-    it[kAnlPeaks] = A.n_peaks;
-    if (A.fast) {
-        it[kAnlKw] = (A.n_kseg + 63ull) / 64ull * ch;
-        it[kAnlKScan] = ch;
-        it[kAnlTile] = (longest + kAnTile - 1) / kAnTile * ch;
-        it[kAnlFast1] = 1;
-    } else {
-        it[kAnlLoud] = (unsigned long long)A.n_seg * ch;
-    }
-    if (A.sq_exact) {
-        it[kAnlSqChunk] = A.n_sq_chunks;
-        it[kAnlSq1] = 1;
-    } else {
-        it[kAnlSumsq] = A.n_sq_seg;
-    }
-    it[kAnlB3] = (A.n_chunks + 127ull) / 128ull;
-    it[kAnlClip] = 1;
-    it[kAnlFft] = 3;
-}
-// items one workgroup takes in turn (one clip lookup for all of them); a list's prefix counts these workgroups
-__host__ __device__ constexpr unsigned an_batch_per_wg(int L) {
-    return L == kAnlPeaks ? 8u : L == kAnlTile ? 4u : L == kAnlSqChunk ? 16u : L == kAnlB3 ? 4u : 1u;
-}
+// (kAnTile, the work lists AnList, an_batch_items and an_batch_per_wg: analysis_plan.hpp - the host plans with them too)
 struct AnBatchArgs {
     const AnalysisArgs *clips;   // [n_clips] the group's descriptors (device)
     const unsigned int *pre;     // [kAnlCount][n_clips + 1]: workgroups of the clips in front (device)

@@ -336,53 +336,99 @@ double flo_o_gated_lufs(const double *energies, size_t n) {
     if (c2 == 0) return ungated;
     return -0.691 + 10.0 * log10(s2 / (double)c2);
 }
+/* The 400 ms block energies, summed over the channels (ebu_r128.rs:219-266): the K-weighting recurrence sample after
+ * sample, then every block's sum of squares in frame order, divided by its length, the channels added in order. One body
+ * for two number types: T = double is the reference's own arithmetic; T = long double (64-bit mantissa on x86-64) is its
+ * twin at higher precision, rounded to double at the very end - the yardstick for how far any double-precision order of
+ * the same additions may lie from the exact value. Returns the number of blocks; writes up to `cap` of them. */
+#define FLO_O_BLOCK_ENERGIES(NAME, T)                                                                              \
+    size_t NAME(const float *samples, size_t len, uint8_t channels, uint32_t sample_rate, double *out, size_t cap) { \
+        if (len == 0 || channels == 0) return 0;                                                                   \
+        const double sr = (double)sample_rate;                                                                     \
+        const size_t hop = (size_t)round(sr * 0.1), block = hop * 4;                                               \
+        const size_t frames = len / channels;                                                                      \
+        double shelf[5], hp[5];                                                                                    \
+        flo_o_kweighting_coeffs(sr, shelf, hp);                                                                    \
+        T *kw = (T *)malloc((frames ? frames : 1) * channels * sizeof(T)); /* [ch][frames] */                      \
+        for (size_t c = 0; c < channels; c++) {                                                                    \
+            T s1 = 0, s2 = 0, h1 = 0, h2 = 0;                                                                      \
+            for (size_t i = 0; i < frames; i++) {                                                                  \
+                T x = (T)samples[i * channels + c];                                                                \
+                T y = (T)shelf[0] * x + s1;                                                                        \
+                s1 = (T)shelf[1] * x - (T)shelf[3] * y + s2;                                                       \
+                s2 = (T)shelf[2] * x - (T)shelf[4] * y;                                                            \
+                T y2 = (T)hp[0] * y + h1;                                                                          \
+                h1 = (T)hp[1] * y - (T)hp[3] * y2 + h2;                                                            \
+                h2 = (T)hp[2] * y - (T)hp[4] * y2;                                                                 \
+                kw[c * frames + i] = y2;                                                                           \
+            }                                                                                                      \
+        }                                                                                                          \
+        size_t nb = 0, start = 0;                                                                                  \
+        while (start < frames) {                                                                                   \
+            size_t end = start + block < frames ? start + block : frames;                                          \
+            if (end <= start) break;                                                                               \
+            T energy = 0.0;                                                                                        \
+            const size_t l = end - start;                                                                          \
+            for (size_t c = 0; c < channels; c++) {                                                                \
+                T ss = 0.0;                                                                                        \
+                for (size_t i = start; i < end; i++) ss += kw[c * frames + i] * kw[c * frames + i];                \
+                energy += ss / (T)l;                                                                               \
+            }                                                                                                      \
+            if (out && nb < cap) out[nb] = (double)energy;                                                         \
+            nb++;                                                                                                  \
+            if (end == frames) break;                                                                              \
+            start += hop;                                                                                          \
+            if (hop == 0) break;                                                                                   \
+        }                                                                                                          \
+        free(kw);                                                                                                  \
+        return nb;                                                                                                 \
+    }
+FLO_O_BLOCK_ENERGIES(flo_o_block_energies, double)
+FLO_O_BLOCK_ENERGIES(flo_o_block_energies_ld, long double)
+
 double flo_o_integrated_lufs(const float *samples, size_t len, uint8_t channels, uint32_t sample_rate) {
     if (len == 0 || channels == 0) return -23.0;
-    const double sr = (double)sample_rate;
-    const size_t hop = (size_t)round(sr * 0.1), block = hop * 4;
-    const size_t frames = len / channels;
-    double shelf[5], hp[5];
-    flo_o_kweighting_coeffs(sr, shelf, hp);
-    double *kw = (double *)malloc((frames ? frames : 1) * channels * sizeof(double)); /* [ch][frames] */
-    for (size_t c = 0; c < channels; c++) {
-        double s1 = 0, s2 = 0, h1 = 0, h2 = 0;
-        for (size_t i = 0; i < frames; i++) {
-            double x = (double)samples[i * channels + c];
-            double y = shelf[0] * x + s1;
-            s1 = shelf[1] * x - shelf[3] * y + s2;
-            s2 = shelf[2] * x - shelf[4] * y;
-            double y2 = hp[0] * y + h1;
-            h1 = hp[1] * y - hp[3] * y2 + h2;
-            h2 = hp[2] * y - hp[4] * y2;
-            kw[c * frames + i] = y2;
-        }
-    }
-    double *en = NULL;
-    size_t nb = 0, capb = 0;
-    size_t start = 0;
-    while (start < frames) {
-        size_t end = start + block < frames ? start + block : frames;
-        if (end <= start) break;
-        double energy = 0.0;
-        const size_t l = end - start;
-        for (size_t c = 0; c < channels; c++) {
-            double ss = 0.0;
-            for (size_t i = start; i < end; i++) ss += kw[c * frames + i] * kw[c * frames + i];
-            energy += ss / (double)l;
-        }
-        if (nb == capb) {
-            capb = capb ? 2 * capb : 64;
-            en = (double *)realloc(en, capb * sizeof(double));
-        }
-        en[nb++] = energy;
-        if (end == frames) break;
-        start += hop;
-        if (hop == 0) break;
-    }
+    const size_t nb = flo_o_block_energies(samples, len, channels, sample_rate, NULL, 0);
+    double *en = (double *)malloc((nb ? nb : 1) * sizeof(double));
+    flo_o_block_energies(samples, len, channels, sample_rate, en, nb);
     double r = flo_o_gated_lufs(en, nb);
     free(en);
-    free(kw);
     return r;
+}
+/* the loudness range from the block energies (ebu_r128.rs:268-345): the two gates, then the 95th minus the 10th percentile
+ * of the gated blocks' loudness, linearly interpolated; 0 with fewer than two gated blocks */
+static int cmp_double(const void *a, const void *b);
+double flo_o_loudness_range(const double *en, size_t nb) {
+    if (nb == 0) return 0.0;
+    const double abs_gate = pow(10.0, (-70.0 + 0.691) / 10.0);
+    double sum = 0.0, lra = 0.0;
+    size_t cnt = 0;
+    for (size_t i = 0; i < nb; i++)
+        if (en[i] >= abs_gate) {
+            sum += en[i];
+            cnt++;
+        }
+    if (!cnt) return 0.0;
+    const double ungated = -0.691 + 10.0 * log10(sum / (double)cnt);
+    const double rel_gate = pow(10.0, (ungated - 10.0 + 0.691) / 10.0);
+    double *vals = (double *)malloc(nb * sizeof(double));
+    size_t c2 = 0;
+    for (size_t i = 0; i < nb; i++)
+        if (en[i] >= abs_gate && en[i] >= rel_gate) vals[c2++] = en[i] > 0.0 ? -0.691 + 10.0 * log10(en[i]) : -150.0;
+    if (c2 >= 2) {
+        qsort(vals, c2, sizeof(double), cmp_double);
+        const double n = (double)c2;
+        const double pos[2] = {0.10 * (n - 1.0), 0.95 * (n - 1.0)};
+        double pv[2];
+        for (int q = 0; q < 2; q++) {
+            const size_t i = (size_t)floor(pos[q]);
+            const double frac = pos[q] - (double)i;
+            pv[q] = i + 1 < c2 ? vals[i] * (1.0 - frac) + vals[i + 1] * frac : vals[i];
+        }
+        lra = pv[1] - pv[0];
+    }
+    free(vals);
+    return lra;
 }
 
 /* compute_true_peak (ebu_r128.rs:112-179): a 49-tap Hann-windowed sinc (cutoff 0.45 fs, designed at 4 fs, normalised to
@@ -585,7 +631,8 @@ int flo_o_analysis_metadata(const float *samples, size_t len, uint32_t sample_ra
     /* waveform_data */
     mp_str(&b, "waveform_data");
     {
-        size_t cap = len / (channels ? channels : 1) + 16;
+        /* (sized by a counting call: more peaks a second than sample-frames leaves more windows than frames) */
+        size_t cap = flo_o_waveform_peaks(samples, len, channels, sample_rate, peaks_per_second, NULL, 0) + 1;
         float *peaks = (float *)malloc(cap * sizeof(float));
         size_t np = flo_o_waveform_peaks(samples, len, channels, sample_rate, peaks_per_second, peaks, cap);
         buf_push(&b, 0x83);

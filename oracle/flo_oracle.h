@@ -127,6 +127,11 @@ void flo_o_spectral_fingerprint(const float *samples, size_t len, uint8_t channe
 void flo_o_kweighting_coeffs(double sample_rate, double shelf[5], double hp[5]);      /* ebu_r128.rs:51-103 */
 double flo_o_gated_lufs(const double *energies, size_t n);                            /* ebu_r128.rs:268-318 */
 double flo_o_integrated_lufs(const float *samples, size_t len, uint8_t channels, uint32_t sample_rate); /* :182-318 */
+/* the 400 ms block energies summed over channels, in the reference's order (:219-266); _ld: the same at long double,
+ * rounded to double at the end. Return the block count, write up to cap. flo_o_loudness_range: the LRA from them (:268-345) */
+size_t flo_o_block_energies(const float *samples, size_t len, uint8_t channels, uint32_t sample_rate, double *out, size_t cap);
+size_t flo_o_block_energies_ld(const float *samples, size_t len, uint8_t channels, uint32_t sample_rate, double *out, size_t cap);
+double flo_o_loudness_range(const double *energies, size_t n);
 double flo_o_true_peak_dbtp(const float *samples, size_t len, uint8_t channels, uint32_t sample_rate); /* ebu_r128.rs:112-179 */
 /* out = {integrated_lufs, loudness_range_lu, true_peak_dbtp, sample_peak_dbfs}                   ebu_r128.rs:182-355 */
 void flo_o_loudness_metrics(const float *samples, size_t len, uint8_t channels, uint32_t sample_rate, double out[4]);

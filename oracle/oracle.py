@@ -324,7 +324,9 @@ def waveform_peaks(pcm, channels, sample_rate, peaks_per_second=50):
     L.flo_o_waveform_peaks.restype = C.c_size_t
     L.flo_o_waveform_peaks.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
     p = _f32(pcm)
-    out = np.zeros(p.size // max(channels, 1) + 16, np.float32)
+    # (sized by a counting call: more peaks a second than sample-frames leaves more windows than frames)
+    n = L.flo_o_waveform_peaks(p.ctypes.data, p.size, channels, sample_rate, peaks_per_second, None, 0)
+    out = np.zeros(n + 1, np.float32)
     n = L.flo_o_waveform_peaks(p.ctypes.data, p.size, channels, sample_rate, peaks_per_second, out.ctypes.data, out.size)
     return out[:n].copy()
 
@@ -347,6 +349,38 @@ def integrated_lufs(pcm, channels, sample_rate) -> float:
     L.flo_o_integrated_lufs.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32]
     p = _f32(pcm)
     return L.flo_o_integrated_lufs(p.ctypes.data, p.size, channels, sample_rate)
+
+
+def block_energies(pcm, channels, sample_rate, long_double=False) -> np.ndarray:
+    """the 400 ms block energies summed over channels (ebu_r128.rs:219-266) in the reference's order; long_double: the
+    same recurrence and sums at a 64-bit mantissa, rounded to f64 at the end"""
+    L = lib()
+    f = L.flo_o_block_energies_ld if long_double else L.flo_o_block_energies
+    f.restype = C.c_size_t
+    f.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_void_p, C.c_size_t]
+    p = _f32(pcm)
+    nb = f(p.ctypes.data, p.size, channels, sample_rate, None, 0)
+    out = np.zeros(nb, np.float64)
+    f(p.ctypes.data, p.size, channels, sample_rate, out.ctypes.data, nb)
+    return out
+
+
+def gated_lufs(energies) -> float:
+    """the two gates over block energies (ebu_r128.rs:268-318)"""
+    L = lib()
+    L.flo_o_gated_lufs.restype = C.c_double
+    L.flo_o_gated_lufs.argtypes = [C.c_void_p, C.c_size_t]
+    e = np.ascontiguousarray(energies, np.float64)
+    return L.flo_o_gated_lufs(e.ctypes.data, e.size)
+
+
+def loudness_range(energies) -> float:
+    """the loudness range from block energies (ebu_r128.rs:268-345)"""
+    L = lib()
+    L.flo_o_loudness_range.restype = C.c_double
+    L.flo_o_loudness_range.argtypes = [C.c_void_p, C.c_size_t]
+    e = np.ascontiguousarray(energies, np.float64)
+    return L.flo_o_loudness_range(e.ctypes.data, e.size)
 
 
 def loudness_metrics(pcm, channels, sample_rate) -> dict:

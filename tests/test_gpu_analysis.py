@@ -4,6 +4,7 @@ restatement, field by field and as META bytes (the order-bound sums keep the ref
 import numpy as np
 import pytest
 
+import analysis_model as AM
 import flo_amd
 import signals
 from conftest import example_bytes
@@ -38,11 +39,9 @@ def test_analysis_equals_the_oracle(ctx, name, pcm, sr, ch):
     assert a["hash"] == fp["hash"]
     for k in ("duration_ms", "frequency_peaks", "energy_profile", "avg_loudness"):
         assert a[k] == fp[k], k
-    lo = O.integrated_lufs(pcm, ch, sr)
-    if pcm.size // ch <= 65536:     # one segment: the reference's own order of accumulation, bit for bit
-        assert a["integrated_lufs"] == lo or (np.isnan(a["integrated_lufs"]) and np.isnan(lo))
-    else:                           # segments with a filter warm-up (analysis_kernels.hip): equal to ~1e-15
-        assert abs(a["integrated_lufs"] - lo) <= 1e-12 * abs(lo) or (np.isnan(a["integrated_lufs"]) and np.isnan(lo))
+    # one segment: the reference's own order of accumulation, bit for bit; beyond: within the bound derived from the oracle's
+    # long-double twin (analysis_model.reference)
+    AM.check_loudness(a, AM.reference(pcm, sr, ch, loudness_only=True), name)
     assert ctx.analysis_metadata(pcm, sr, ch, 50) == O.analysis_metadata(pcm, sr, ch, 50)
 
 
@@ -77,16 +76,16 @@ import analysis_cases as AC  # noqa: E402
 
 @pytest.mark.parametrize("name,pcm,ch,sr,check", list(AC.loudness_cases()), ids=[c[0] for c in AC.loudness_cases()])
 def test_reference_loudness_bars_hold_on_the_device(ctx, name, pcm, ch, sr, check):
+    """Beyond one exact segment the loudness must lie within (10 / ln 10) 4 E + 4 ulp of the oracle's long-double twin
+    (analysis_model.reference). "sine at 96000 Hz" is the input that showed why the two-pass K-weighting refines its start
+    states (an_kw_scan_body): without that step it lay 1.51e-13 dB from the twin against a bound of 8.45e-14."""
     a = ctx.analyze(pcm, sr, ch, 50)
     m = {k: a[k] for k in ("integrated_lufs", "loudness_range_lu", "true_peak_dbtp", "sample_peak_dbfs")}
     check(m)
-    o = O.loudness_metrics(pcm, ch, sr)
-    one_segment = pcm.size // max(ch, 1) <= 65536
-    for k in m:
-        if one_segment:
-            assert m[k] == o[k], (k, m[k], o[k])     # one segment: the reference's own order of accumulation, bit for bit
-        else:
-            assert abs(m[k] - o[k]) <= 1e-9 * max(1.0, abs(o[k])), (k, m[k], o[k])
+    if pcm.size:   # one segment: the reference's own order of accumulation, bit for bit; beyond: peaks still, loudness in the derived bound
+        AM.check_loudness(m, AM.reference(pcm, sr, ch, loudness_only=True), name)
+    else:
+        assert m == O.loudness_metrics(pcm, ch, sr)
 
 
 def test_reference_waveform_and_fingerprint_bars_hold_on_the_device(ctx):
@@ -95,14 +94,12 @@ def test_reference_waveform_and_fingerprint_bars_hold_on_the_device(ctx):
 
 
 def test_long_clips_in_segments_agree_with_the_sequential_oracle(ctx):
-    # beyond 65 536 frames the order-bound scans run in segments (filter warm-up, partial block sums): the loudness
-    # agrees to ~1e-12, the META chunk (f32 loudness, u8 levels) byte for byte
+    # beyond 65 536 frames the order-bound scans run in segments: true and sample peak stay bit for bit, loudness and range
+    # lie within the bound derived from the oracle's long-double twin, the META chunk (f32 loudness, u8 levels) byte for byte
     for sr, ch, secs in ((44100, 2, 12.3), (96000, 1, 5.0), (8000, 2, 40.0)):
         pcm = signals.music_like(sr, int(sr * secs), ch, seed=int(secs * 10))
         a = ctx.analyze(pcm, sr, ch, 50)
-        o = O.loudness_metrics(pcm, ch, sr)
-        for k in ("integrated_lufs", "loudness_range_lu", "true_peak_dbtp", "sample_peak_dbfs"):
-            assert abs(a[k] - o[k]) <= 1e-9 * max(1.0, abs(o[k])), (sr, k, a[k], o[k])
+        AM.check_loudness(a, AM.reference(pcm, sr, ch, loudness_only=True), (sr, ch, secs))
         assert ctx.analysis_metadata(pcm, sr, ch, 50) == O.analysis_metadata(pcm, sr, ch, 50)
 
 
@@ -154,7 +151,5 @@ def test_long_clip_loudness_two_pass_state_hand_over(ctx):
     for sr, ch, secs in ((44100, 2, 180.0), (48000, 1, 61.7), (8000, 3, 33.3), (192000, 2, 4.1)):
         pcm = signals.music_like(sr, int(sr * secs) + 13, ch, seed=int(secs))
         a = ctx.analyze(pcm, sr, ch, 50)
-        o = O.loudness_metrics(pcm, ch, sr)
-        for k in ("integrated_lufs", "loudness_range_lu", "true_peak_dbtp", "sample_peak_dbfs"):
-            assert abs(a[k] - o[k]) <= 1e-9 * max(1.0, abs(o[k])), (sr, ch, k, a[k], o[k])
+        AM.check_loudness(a, AM.reference(pcm, sr, ch, loudness_only=True), (sr, ch, secs))
         assert ctx.analysis_metadata(pcm, sr, ch, 50) == O.analysis_metadata(pcm, sr, ch, 50)
