@@ -192,6 +192,18 @@ int ll_decode_device(flo_ctx *c, const LlWrapperList &w, uint64_t out_sf, const 
                 (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_enter).count() / 1e3);
     // the temporaries go back to the pool
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (getenv("FLO_TRACE")) {
+        // the serial flags as the kernels left them: what the host set, plus the wrappers the parallel form gave up
+        // (a 256-ones escape, a sample outside i32); read before the descriptor block returns to the pool
+        std::vector<int> flags(w.serial.size());
+        if (!flags.empty()) HIPCHK(c, hipMemcpy(flags.data(), blk.at<int>(d_desc.p, kSer), flags.size() * sizeof(int), hipMemcpyDeviceToHost));
+        size_t by_host = 0, by_device = 0;
+        for (size_t i = 0; i < flags.size(); i++) {
+            if (w.serial[i]) by_host++;
+            else if (flags[i]) by_device++;
+        }
+        fprintf(stderr, "[flo] ll decode: serial by the host %zu, by the device %zu\n", by_host, by_device);
+    }
     return FLO_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "fidelity_kernels.hpp"
+#include "ll_route.hpp"
 #include "lossy_device.hpp"
 
 namespace flo {
@@ -73,15 +74,7 @@ struct LossyDecArgs {
     LossyCmpArgs cmp;                 // fidelity reports only (launch_lossy_compare); `out` is not written then
 };
 
-// One ALPC / raw / silent channel wrapper of one frame = one thread.
-struct LlChannelDev {
-    unsigned long long off;           // payload offset
-    unsigned long long out_off;       // int32 offset of this channel-frame in the planar scratch
-    unsigned int len;                 // payload bytes
-    unsigned int samples;             // frame_samples
-    unsigned char n_coeffs, shift_bits, rice_k, pad;
-    int coeffs[12];
-};
+// (LlChannelDev, LlFrameDev and the tile constants kRiceTileBits / kRiceStates / kRiceMaxK: ll_route.hpp)
 struct LlDecArgs {
     const uint8_t *bytes;
     const LlChannelDev *ch;
@@ -93,9 +86,6 @@ struct LlDecArgs {
 // Parallel form of the ALPC decode (lldec_kernels.hip). A Rice stream is cut into tiles of kRiceTileBits bits;
 // `tile0` is the running tile count over the wrappers (0 tiles for raw / silent wrappers and for those the host
 // already handed to the serial kernel through `serial`).
-constexpr int kRiceTileBits = 1024;
-constexpr int kRiceStates = 16;       // entry states of a tile: skip 0..k bits (k <= 14), or "inside a unary run" (k + 1)
-constexpr int kRiceMaxK = kRiceStates - 2;
 struct LlParArgs {
     const uint8_t *bytes;
     const LlChannelDev *ch;
@@ -109,14 +99,6 @@ struct LlParArgs {
                                       // outside i32)
     const unsigned int *others;       // [n_others] the wrappers that are no LPC recurrence (fixed predictors, raw, silent, too short): one
     unsigned int n_others;            // workgroup each in ll_predict behind the LPC groups (a workgroup per wrapper cost 0.2 ms in dispatch alone)
-};
-// Per frame: mid/side, interleave, int -> float.
-struct LlFrameDev {
-    unsigned long long out_off;       // sample-frame offset of the frame in the output
-    unsigned long long scratch_off[2];  // first two channel wrappers (mid/side needs exactly two)
-    unsigned int first_channel, n_channels;
-    unsigned int samples;
-    unsigned int mid_side;
 };
 struct LlFinishArgs {
     const LlFrameDev *fr;

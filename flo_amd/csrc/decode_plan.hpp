@@ -14,56 +14,9 @@
 
 #include "ctx_internal.hpp"
 #include "decode_kernels.hpp"
+#include "ll_route.hpp"
 
-// Which kernels take one channel wrapper. This mirrors the limits of lldec_kernels.hip: its tile tables have room for
-// Rice parameters k <= kRiceMaxK only; the tile stages put a wrapper's tiles (four per workgroup at least) in gridDim.y
-// (<= 65535); the f64 LPC recurrence is exact only for sum |coef| < 2^21 and shift <= 20 (it holds
-// r * 2^shift + sum c * s, |r|, |s| < 2^31, in 53 bits). A wrapper outside them goes to the serial kernel. Wrappers that
-// are no LPC recurrence ll_predict's row form takes (fixed predictors, raw, silent, too short) are "others".
-struct LlRoute {
-    uint32_t tiles = 0;   // Rice tiles of the parallel form (0: none, or serial)
-    uint8_t serial = 0, other = 0;
-};
-LlRoute ll_route(const LlChannelDev &d, bool force_serial);
-
-// A wrapper's descriptor; samples and out_off are set when it joins a list.
-LlChannelDev ll_channel(uint64_t off, uint32_t len, uint8_t n_coeffs, uint8_t shift_bits, uint8_t rice_k, const int32_t *coeffs);
-
-// The wrappers of one call in the order the kernels see them, with what the wrapper stage needs besides: the running
-// tile count, the serial flags and the "others". Each wrapper's samples get the next run of the int32 scratch
-// (out_off). clear() keeps the capacity.
-struct LlWrapperList {
-    std::vector<LlChannelDev> chs;
-    std::vector<unsigned int> tile0{0u};   // [chs + 1]
-    std::vector<int> serial;
-    std::vector<unsigned int> others;
-    std::vector<LlFrameDev> frs;           // the frames appended by add_frame
-    uint64_t scratch = 0;                  // ints of scratch the wrappers take
-    unsigned max_tiles = 0, max_samples = 0;
-
-    void clear();
-    unsigned tiles() const { return tile0.back(); }
-    // append one wrapper, routed already; returns its index
-    unsigned push(const LlChannelDev &d, const LlRoute &r);
-    // append a frame of n wrappers, wrapper(k) giving wrapper k's descriptor, each routed here
-    template <class F>
-    void add_frame(uint64_t out_off, uint32_t samples, bool mid_side, unsigned n, bool force_serial, F &&wrapper) {
-        LlFrameDev fd{};
-        fd.out_off = out_off;
-        fd.first_channel = (unsigned)chs.size();
-        fd.n_channels = n;
-        fd.samples = samples;
-        fd.mid_side = mid_side ? 1u : 0u;
-        for (unsigned k = 0; k < n; k++) {
-            LlChannelDev d = wrapper(k);
-            d.samples = samples;
-            if (k < 2) fd.scratch_off[k] = scratch;
-            push(d, ll_route(d, force_serial));
-        }
-        if (samples > max_samples) max_samples = samples;
-        frs.push_back(fd);
-    }
-};
+// (ll_route, ll_channel and LlWrapperList: ll_route.hpp, which needs no HIP)
 
 // A call's host arrays as one block for one copy: part i at off[i], a multiple of 256 bytes. A part with no source is
 // space the caller fills itself.
