@@ -309,6 +309,20 @@ class Context:
                                              q.ctypes.data, sfw.ctypes.data))
         return dict(q=q, sf_words=sfw)
 
+    def lossy_pack_frames(self, coeffs, sample_rate, quality):
+        """lossy_quantize that keeps the frames: the clip's DATA bytes and frame sizes beside the integers and scale words,
+        in the form force_path names (5, 2, else 1)."""
+        c = np.ascontiguousarray(coeffs, np.float32)
+        hops, channels = c.shape[0], c.shape[1]
+        q = np.zeros((hops, channels, 1024), np.int16)
+        sfw = np.zeros((hops, channels, 25), np.uint16)
+        data = np.zeros(hops * (12 + channels * (50 + 4 + 2064)) + 16, np.uint8)
+        sizes = np.zeros(max(hops, 1), np.uint32)
+        n = C.c_size_t()
+        self._chk(self._L.flo_lossy_pack_frames(self._h, c.ctypes.data, hops, sample_rate, channels, quality, q.ctypes.data,
+                                                sfw.ctypes.data, data.ctypes.data, data.size, C.byref(n), sizes.ctypes.data))
+        return dict(q=q, sf_words=sfw, data=data[:n.value].tobytes(), frame_sizes=sizes[:hops].astype(np.int64))
+
     def lossy_quantize_smr(self, coeffs, smr, sample_rate, quality):
         """TransformEncoder::quantize_coefficients on the device (encoder.rs:109-154): vectors of 1024 coefficients and the
         caller's signal-to-mask ratios -> (i16 [n][1024], f32 scale factors [n][25]); smr=None: scale factors only."""
@@ -596,13 +610,16 @@ class TransformEncoder:
     """lossy::TransformEncoder — lossy/encoder.rs:6-53,63-164,167-239. One fresh encoder per clip is the contract."""
 
     _HISTORY = 65   # frames whose masking levels can still reach the newest one: the temporal step is max(a_t, 0.7 s_{t-1}),
-                    # and the frame-parallel kernels resolve it exactly from a 64-frame warm-up (tests compare them to the chain)
+                    # and the frame-parallel kernels resolve it exactly from a 64-frame warm-up (tests compare them to the chain);
+                    # a level of +inf is the exception, kept by _pin
 
     def __init__(self, sample_rate: int, channels: int, quality: float, ctx: Context = None):
         self.sample_rate, self.channels = sample_rate, channels
         self.quality = float(min(max(quality, 0.0), 1.0))
         self._ctx = ctx
         self._spectra = []   # the last _HISTORY frames' coefficients [ch][1024]: the psychoacoustic model's temporal state
+        self._pinned = []    # in front of them: the spectra whose level may never decay (see _pin)
+        self._pinned_n = {}
 
     def set_quality(self, quality: float):
         self.quality = float(min(max(quality, 0.0), 1.0))
@@ -610,6 +627,30 @@ class TransformEncoder:
     def reset(self):
         """encoder.rs:157-164: forget the temporal masking state (and the transform's, which keeps none here)"""
         self._spectra = []
+        self._pinned = []
+        self._pinned_n = {}
+
+    _PIN_CAP = 32   # pinned spectra per channel
+
+    def _pin(self, old):
+        """A spectrum that leaves the history takes its masking levels with it, which is right for every finite level (0.7^65
+        of it is nothing) and wrong for +inf, the level of a band whose f32 energy overflowed: the reference keeps that one
+        for good. Such a spectrum therefore stays in front of the history, the other channels zeroed. Whether a band's f32
+        sum overflows depends on the kernel's summation order, so the test here is deliberately wide: every channel whose sum
+        of squares (f64) is not below a quarter of the f32 maximum - NaN included - is kept, and keeping one whose level was
+        finite after all changes nothing (in front of 65 frames it has decayed). Each kept spectrum is judged by the device
+        again in every pass, so no decision is taken here. Up to _PIN_CAP per channel, the earliest: not covered is a clip
+        with more than that many such frames of which none of the first _PIN_CAP overflowed on the device."""
+        for c in range(self.channels):
+            if self._pinned_n.get(c, 0) >= self._PIN_CAP:
+                continue
+            with np.errstate(all="ignore"):
+                e = float((old[c].astype(np.float64) ** 2).sum())
+            if not e < 0.25 * float(np.finfo(np.float32).max):
+                keep = np.zeros_like(old)
+                keep[c] = old[c]
+                self._pinned.append(keep)
+                self._pinned_n[c] = self._pinned_n.get(c, 0) + 1
 
     def encode_frame(self, samples) -> TransformFrame:
         """encoder.rs:63-106: one block of 2048 sample-frames (interleaved; shorter blocks are zero-padded) -> its quantised
@@ -627,8 +668,8 @@ class TransformEncoder:
         spec = ctx.mdct_forward(block.reshape(-1))            # [ch][1024], device
         self._spectra.append(spec)
         if len(self._spectra) > self._HISTORY:
-            self._spectra.pop(0)
-        g = ctx.lossy_quantize(np.stack(self._spectra), self.sample_rate, self.quality)
+            self._pin(self._spectra.pop(0))
+        g = ctx.lossy_quantize(np.stack(self._pinned + self._spectra), self.sample_rate, self.quality)
         _, sf = ctx.lossy_quantize_smr(spec, None, self.sample_rate, self.quality)
         return TransformFrame([g["q"][-1, c].copy() for c in range(ch)], [sf[c].copy() for c in range(ch)],
                               [g["sf_words"][-1, c].copy() for c in range(ch)])

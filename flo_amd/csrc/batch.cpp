@@ -31,6 +31,9 @@ static int alloc_frame_scratch(flo_batch *b, const LossyPlan &p) {
     HIPCHK(c, pool_alloc(&b->d_at, n));
     HIPCHK(c, pool_alloc(&b->d_sprev, n));
     HIPCHK(c, pool_alloc(&b->d_bmax, n));
+    const size_t marks = b->n_clips * b->ch * 32 * sizeof(unsigned long long);
+    HIPCHK(c, pool_alloc(&b->d_inf_mark, marks));
+    HIPCHK(c, hipMemsetAsync(b->d_inf_mark, 0, marks, c->stream));
     if (p.coef_handover) HIPCHK(c, pool_alloc(&b->d_coef, (size_t)b->total_frames * 8192));
     HIPCHK(c, pool_alloc(&b->d_slots, (size_t)b->total_frames * lossy_slot_bytes(b->ch)));
     HIPCHK(c, pool_alloc(&b->d_frame_off, (size_t)(b->total_frames + 1) * 8));
@@ -43,7 +46,7 @@ extern "C" void flo_batch_destroy(flo_batch *b) {
     hipStreamSynchronize(b->ctx->stream);
     void *ptrs[] = {b->d_pcm, b->d_plan, b->d_hops, b->d_out, b->d_frame_size, b->d_clip_bytes, b->d_crc, b->d_part, b->d_at,
                     b->d_sprev, b->d_slots, b->d_frame_off, b->d_dbg_coeffs, b->d_dbg_q, b->d_dbg_sfw, b->d_pack_plan, b->d_next, b->d_bmax, b->d_coef,
-                    b->d_crc_ready, b->d_done_q};
+                    b->d_crc_ready, b->d_done_q, b->d_inf_mark};
     for (void *p : ptrs)
         if (p) pool_free(p);
     if (b->ev_pack_plan) hipEventDestroy(b->ev_pack_plan);
@@ -339,6 +342,8 @@ static int batch_encode_launch(flo_batch *b) {
         int arc = alloc_frame_scratch(b, P);
         if (arc != FLO_OK) return arc;
         LossyArgs A = make_args(b);
+        A.inf_mark = b->d_inf_mark;
+        A.inf_tag = ++b->inf_tag;   // (marks of an earlier encode of this batch carry another tag: nothing to clear)
         if ((rc = timed_launch(c, "lossy_bands", [&] { return launch_lossy_frames_pass(A, P.pass1, c->stream); })) != FLO_OK) return rc;
         if (P.scan() && (rc = timed_launch(c, "lossy_scan", [&] { return launch_lossy_scan(A, c->stream); })) != FLO_OK) return rc;
         if ((rc = timed_launch(c, "lossy_frames", [&] { return launch_lossy_frames_pass(A, P.pass2, c->stream); })) != FLO_OK) return rc;

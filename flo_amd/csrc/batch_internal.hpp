@@ -38,6 +38,8 @@ struct flo_batch {
     uint64_t *pin_sizes = nullptr;            // pinned [n_clips]: DATA sizes, copied behind finish_files (sizes_queued)
     bool sizes_queued = false;
     float *d_bmax = nullptr;   // band maxima of every frame (frame-parallel form: pass 1 -> pass 2)
+    unsigned long long *d_inf_mark = nullptr;   // [n_clips][ch][32] first frame of a +inf level (LossyArgs::inf_mark), zeroed once
+    uint32_t inf_tag = 0;                       // of the last frame-parallel launch sequence
     void *d_coef = nullptr;    // ... and, for a few long stereo clips, every frame's coefficients (8 KB per frame)
     float *d_at = nullptr, *d_sprev = nullptr;
     uint8_t *d_slots = nullptr;

@@ -131,12 +131,13 @@ extern "C" int flo_batch_encode_ladder(flo_batch *b, size_t n_q, const float *qu
                 v_hops[v] = b->hops[g.first + i];
             }
     DevBuf<float> d_at, d_sprev, d_bmax;
+    DevBuf<unsigned long long> d_inf;   // LossyArgs::inf_mark, a tag per group
     DevBuf<unsigned long long> d_rel, d_sizes, d_vframe0, d_vout, d_vbytes, d_foff, d_pack;
     DevBuf<unsigned int> d_vhops, d_fsize, d_part;
     DevBuf<uint8_t> d_slots;
     std::deque<DevBuf<uint8_t>> work;   // per group: its finished files at their DATA-aligned places, until the last move
     QuiesceOnExit quiesce(c);
-    if (!d_at.alloc(max_frames * ch * 32) || !d_sprev.alloc(max_frames * ch * 32) || (ch == 2 && !d_bmax.alloc(max_frames * ch * 32)) ||
+    if (!d_at.alloc(max_frames * ch * 32) || !d_inf.alloc(n * ch * 32) || !d_sprev.alloc(max_frames * ch * 32) || (ch == 2 && !d_bmax.alloc(max_frames * ch * 32)) ||
         !d_rel.alloc(n) || !d_sizes.alloc(V) || !d_vframe0.alloc(V) || !d_vout.alloc(V) || !d_vbytes.alloc(V) || !d_vhops.alloc(V) ||
         !d_part.alloc(max_parts + 1) || !d_foff.alloc(max_frames * K + 1) || !d_fsize.alloc(max_frames * K + 1) ||
         !d_pack.alloc(3 * V) || !d_slots.alloc((size_t)max_frames * K * slot_bytes))
@@ -145,6 +146,7 @@ extern "C" int flo_batch_encode_ladder(flo_batch *b, size_t n_q, const float *qu
     LCHK(hipMemcpyAsync(d_vframe0.p, v_frame0.data(), V * 8, hipMemcpyHostToDevice, c->stream));
     LCHK(hipMemcpyAsync(d_vhops.p, v_hops.data(), V * 4, hipMemcpyHostToDevice, c->stream));
     LCHK(hipMemsetAsync(d_sizes.p, 0, V * 8, c->stream));
+    LCHK(hipMemsetAsync(d_inf.p, 0, n * ch * 32 * 8, c->stream));
     const unsigned long long *plan = (const unsigned long long *)b->d_plan;
     const FrameKernel pass1 = ch == 1 ? FrameKernel::Mono1 : ch == 2 ? FrameKernel::Pair1 : FrameKernel::Multi1;
     std::vector<uint64_t> src_off(V);   // the files inside their group's work buffer
@@ -164,6 +166,8 @@ extern "C" int flo_batch_encode_ladder(flo_batch *b, size_t n_q, const float *qu
         A.bmax_t = d_bmax.p;
         A.s_prev_out = d_sprev.p;
         A.s_prev = d_sprev.p;
+        A.inf_mark = d_inf.p;
+        A.inf_tag++;   // (inf_tag shares its storage with epoch, which nothing sets on this struct: frame-parallel launches only)
         A.slots = d_slots.p;
         A.slot_bytes = slot_bytes;
         A.frame_size = d_fsize.p;

@@ -62,6 +62,23 @@
 
 namespace flo {
 
+// ---------------------------------------------------------------------------------------------- levels that stay
+// s_t = max(a_t, 0.7 s_(t-1)) forgets every finite level (0.7^64 of it is left after a scan block) but not +inf: an f32 band
+// energy that overflowed gives a_t = +inf, and 0.7 inf = inf for every later frame. The frame-parallel form, which warms a
+// block up from 0, therefore records per (clip, channel, band) the first frame whose a_t is +inf (pass 1) and starts a
+// warm-up from +inf when that frame lies in front of it. (-inf and NaN never stay: max drops them.)
+__device__ __forceinline__ void mark_inf_level(const LossyArgs &A, unsigned clip, unsigned ch, unsigned band, unsigned h, float a) {
+    if (A.inf_mark && a == __builtin_inff())
+        atomicMax(A.inf_mark + ((unsigned long long)clip * (unsigned)A.nch + ch) * 32 + band,
+                  ((unsigned long long)A.inf_tag << 32) | (unsigned long long)(0xFFFFFFFFu - h));
+}
+// whether a frame in front of frame h left the level at +inf
+__device__ __forceinline__ bool inf_level_before(const LossyArgs &A, unsigned clip, unsigned ch, unsigned band, unsigned h) {
+    if (!A.inf_mark || h == 0) return false;
+    const unsigned long long v = A.inf_mark[((unsigned long long)clip * (unsigned)A.nch + ch) * 32 + band];
+    return (unsigned)(v >> 32) == A.inf_tag && 0xFFFFFFFFu - (unsigned)v < h;
+}
+
 // ---------------------------------------------------------------------------------------------- frame body
 template <int CH>
 struct FrameState {
@@ -1041,6 +1058,10 @@ __global__ __launch_bounds__(64) void lossy_frame_kernel(LossyArgs A) {
 #pragma unroll
         for (int ch = 0; ch < CH; ch++) st.prev[ch] = 0.f;
         analyse_frame<CH, true, EXACT>(lane, c, lds, L, A, A.T, 0, st, gframe, q, sfw, P);
+        if (lane < 25) {
+#pragma unroll
+            for (int ch = 0; ch < CH; ch++) mark_inf_level(A, clip, (unsigned)ch, (unsigned)lane, h, A.a_t[(gframe * A.nch + ch) * 32 + lane]);
+        }
         return;
     }
     store_coeffs_dbg<CH>(lane, c, A, gframe, 0);
@@ -1152,6 +1173,7 @@ __global__ __launch_bounds__(64) void lossy_frame2x_kernel(LossyArgs A) {
         if (bnd < 25) {
             A.a_t[(gframe * 2 + up) * 32 + bnd] = a;
             A.bmax_t[(gframe * 2 + up) * 32 + bnd] = bmax1;
+            mark_inf_level(A, clip, (unsigned)up, (unsigned)bnd, h, a);
         }
         return;
     }
@@ -1160,12 +1182,13 @@ __global__ __launch_bounds__(64) void lossy_frame2x_kernel(LossyArgs A) {
     float prev = 0.f;
     if constexpr (kSmall) {
         // The temporal chain s_t = max(a_t, 0.7 s_(t-1)) over the 64 frames before this one, from 0: what lossy_scan_kernel
-        // computes for the first frame of each of its blocks (history older than 64 frames cannot reach a threshold, see
-        // there), here for every frame by the workgroup that needs it - 64 independent 4-byte loads per lane and a chain
+        // computes for the first frame of each of its blocks (history older than 64 frames cannot reach a threshold unless it
+        // is +inf, see there), here for every frame by the workgroup that needs it - 64 independent 4-byte loads per lane and a chain
         // of 128 instructions instead of a launch of its own (10.6 us for a 3-minute clip) between the passes.
         const float *at = A.a_t + ((gframe - h) * 2 + (unsigned)up) * 32 + (unsigned)(bnd < 25 ? bnd : 0);
         float s = 0.f;
         if (h >= (unsigned)kScanBlock) {   // (uniform)
+            if (inf_level_before(A, clip, (unsigned)up, (unsigned)(bnd < 25 ? bnd : 0), h - (unsigned)kScanBlock)) s = __builtin_inff();
             float av[kScanBlock];
 #pragma unroll
             for (int j = 0; j < kScanBlock; j++) av[j] = at[(unsigned long long)(h - kScanBlock + j) * 64];
@@ -1322,6 +1345,7 @@ __global__ __launch_bounds__(64) void lossy_frame_n_kernel(LossyArgs A) {
         if (PASS == 1) {
             st.prev[0] = 0.f;
             analyse_frame<1, true, EXACT>(lane, c, lds, L, A, A.T, ch, st, gframe, q, sfw, P);
+            if (lane < 25) mark_inf_level(A, clip, (unsigned)ch, (unsigned)lane, h, A.a_t[(gframe * A.nch + ch) * 32 + lane]);
             continue;
         }
         store_coeffs_dbg<1>(lane, c, A, gframe, ch);
@@ -1476,9 +1500,11 @@ __global__ __launch_bounds__(64) void lossy_curve_kernel(CurveArgs C, const floa
 
 // temporal recurrence s_t = max(a_t, 0.7 s_{t-1}), s_{-1} = 0 (psychoacoustic.rs:198-203) for the frame-parallel
 // form: blocks of 64 frames, one thread per (clip, block, channel, band), each warmed up over the 64 frames before its
-// block. History older than 64 frames can only contribute 0.7^64 (1e-10) of its level; levels below 4.77e-7 (half an
-// ulp of 10) vanish in fl(s - 10) and in max(s, ath) - 10, so every threshold derived from the blocked scan is
-// bit-identical to the sequential chain's (the chain kernel keeps the true sequential state).
+// block. History older than 64 frames can only contribute 0.7^64 (1e-10) of its level when that level is finite; levels
+// below 4.77e-7 (half an ulp of 10) vanish in fl(s - 10) and in max(s, ath) - 10, so every threshold derived from the
+// blocked scan is bit-identical to the sequential chain's (the chain kernel keeps the true sequential state). A level of
+// +inf (a band energy that overflowed f32) never decays: a block whose warm-up starts behind the first such frame starts
+// from +inf (inf_level_before, from pass 1's marks).
 // Writes the state seen BEFORE each frame.
 __global__ void lossy_scan_kernel(LossyArgs A) {
     const unsigned clip = blockIdx.x;   // clips in x: gridDim.y stops at 65535
@@ -1494,7 +1520,7 @@ __global__ void lossy_scan_kernel(LossyArgs A) {
     const unsigned fe = fs + kScanBlock < hops ? fs + kScanBlock : hops;
     // The recurrence is a serial chain, the loads are not: fetch sixteen levels at a time, then run the chain on
     // registers (one thread would otherwise pay a full memory latency per frame, 128 times in a row).
-    float s = 0.f;
+    float s = inf_level_before(A, clip, ch, band, fw) ? __builtin_inff() : 0.f;
     const unsigned long long stride = (unsigned long long)A.nch * 32;
     const float *at = A.a_t + (f0 * A.nch + ch) * 32 + band;
     float *sp = A.s_prev_out + (f0 * A.nch + ch) * 32 + band;
@@ -1515,8 +1541,9 @@ __global__ void lossy_scan_kernel(LossyArgs A) {
 
 // The temporal recurrence over a stream step's frames (flo_stream_encode_ready), seeded per (stream, channel, band) from
 // the level the stream carried over: seed[(i * nch + ch) * 25 + band]. Blocks of kScanBlock frames as in lossy_scan_kernel;
-// the first two blocks run from the seed, which is the sequential chain, a later block is warmed up from 0 over the 64
-// frames in front of it, which gives the same thresholds (see there). The thread of a stream's last block leaves the level
+// the first two blocks run from the seed, which is the sequential chain, a later block is warmed up over the 64 frames in
+// front of it - from 0, which gives the same thresholds for every finite level (see there), or from +inf when the seed or
+// a frame in front of the warm-up left the level there. The thread of a stream's last block leaves the level
 // after the stream's last frame in level_out (same layout): the state the stream carries into its next step.
 __global__ void lossy_stream_scan_kernel(LossyArgs A, const float *seed, float *level_out) {
     const unsigned clip = blockIdx.x;
@@ -1530,7 +1557,9 @@ __global__ void lossy_stream_scan_kernel(LossyArgs A, const float *seed, float *
     const unsigned fw = fs >= 2 * kScanBlock ? fs - kScanBlock : 0;
     const unsigned fe = fs + kScanBlock < hops ? fs + kScanBlock : hops;
     const unsigned lvl = (clip * (unsigned)A.nch + ch) * 25u + band;
-    float s = fw == 0 ? seed[lvl] : 0.f;
+    // (a carried level of +inf, like a +inf in front of the warm-up, is what a later block must start from)
+    float s = seed[lvl];
+    if (fw != 0) s = (s == __builtin_inff() || inf_level_before(A, clip, ch, band, fw)) ? __builtin_inff() : 0.f;
     const unsigned long long stride = (unsigned long long)A.nch * 32;
     const float *at = A.a_t + (f0 * A.nch + ch) * 32 + band;
     float *sp = A.s_prev_out + (f0 * A.nch + ch) * 32 + band;
@@ -1939,7 +1968,10 @@ int launch_lossy_chain(const LossyArgs &A, const LossyPlan &P, hipStream_t s) {
     default: return -1;
     }
 }
+// The frame-parallel form needs LossyArgs::inf_mark (it shares its place with done_q, which only the lock-step chain form
+// uses): launches without it are refused, so a caller that forgets it fails instead of forgetting levels of +inf.
 int launch_lossy_frames_pass(const LossyArgs &A, FrameKernel k, hipStream_t s) {
+    if (!A.inf_mark || !A.inf_tag) return -1;
     dim3 g((unsigned)A.total_frames), b(64);
     const size_t dynb = (size_t)A.slot_bytes + 256 + (size_t)A.nch * 2048;   // lossy_frame_n_kernel
     switch (k) {
@@ -1961,6 +1993,7 @@ int launch_lossy_frames_pass(const LossyArgs &A, FrameKernel k, hipStream_t s) {
     return 0;
 }
 int launch_lossy_stream_pass(const LossyArgs &A, int pass, hipStream_t s) {
+    if (!A.inf_mark || !A.inf_tag) return -1;
     dim3 g((unsigned)A.total_frames), b(64);
     const size_t dynb = (size_t)A.slot_bytes + 256 + (size_t)A.nch * 2048;   // lossy_frame_n_kernel
     constexpr int S1 = 1 | kStreamStep, S2 = 2 | kStreamStep;
@@ -1985,6 +2018,7 @@ int launch_lossy_stream_pass(const LossyArgs &A, int pass, hipStream_t s) {
     return 0;
 }
 int launch_lossy_stream_scan(const LossyArgs &A, const float *seed, float *level_out, hipStream_t s) {
+    if (!A.inf_mark || !A.inf_tag) return -1;
     const unsigned max_hops = (unsigned)A.max_hops;
     hipLaunchKernelGGL(lossy_stream_scan_kernel, dim3(A.n_clips, (max_hops + kScanBlock - 1) / kScanBlock), dim3(32 * A.nch), 0, s, A,
                        seed, level_out);
@@ -1992,6 +2026,7 @@ int launch_lossy_stream_scan(const LossyArgs &A, const float *seed, float *level
     return 0;
 }
 int launch_lossy_scan(const LossyArgs &A, hipStream_t s) {
+    if (!A.inf_mark || !A.inf_tag) return -1;
     unsigned max_hops = (unsigned)A.max_hops;
     hipLaunchKernelGGL(lossy_scan_kernel, dim3(A.n_clips, (max_hops + kScanBlock - 1) / kScanBlock), dim3(32 * A.nch), 0, s, A);
     FLO_LAUNCH_CHECK();

@@ -49,11 +49,21 @@ struct LossyArgs {
     // exhausted computes the CRC slice registers (FinishArgs::part_reg layout) of its last clip and of finished clips
     // it takes from the done queue, and marks them crc_ready[clip] = epoch
     unsigned int *clear_next;                // zeroed at launch: the counters of the launch after this one (other parity)
-    unsigned long long *done_q;              // [n_clips] queue entries: epoch << 32 | clip
+    union {
+        unsigned long long *done_q;          // [n_clips] queue entries: epoch << 32 | clip
+        // frame-parallel form (which has no done queue; the union keeps the argument layout of every kernel what it was):
+        // the first frame at which a band's level before temporal masking is +inf, per (clip, channel, band):
+        // [n_clips][nch][32] words inf_tag << 32 | ~frame, raised by pass 1 with an atomic maximum. A word of another tag
+        // is "none": the buffer is zeroed once and every launch sequence brings a tag of its own. Null: no marks are kept.
+        unsigned long long *inf_mark;
+    };
     unsigned int *crc_ready;                 // [n_clips]
     unsigned int *part_reg;                  // [n_clips * parts]
     unsigned int parts;                      // slices per clip (finish_parts)
-    unsigned int epoch;                      // of this launch, never 0
+    union {
+        unsigned int epoch;                  // of this launch, never 0
+        unsigned int inf_tag;                // frame-parallel form: of this launch sequence, never 0
+    };
     const unsigned int *crc_tab;             // crc_device_tables()
     int n_cus;                               // compute units of the device (persistent workgroups)
 };

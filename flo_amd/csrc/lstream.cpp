@@ -98,7 +98,7 @@ struct LossyGroup {
     size_t in_bytes = 0, work_bytes = 0, out_bytes = 0;
     // offsets inside the group's part of the device buffer
     size_t o_desc = 0, o_hops = 0, o_seed = 0, o_win = 0;      // input (one upload)
-    size_t o_at = 0, o_bmax = 0, o_sprev = 0, o_slots = 0, o_foff = 0;
+    size_t o_at = 0, o_bmax = 0, o_sprev = 0, o_slots = 0, o_foff = 0, o_inf = 0;
     size_t o_out = 0, r_lvl = 0, r_tot = 0, r_bytes = 0;       // output (one read-back): sizes | levels | total | bytes
     size_t guess = 0;      // bytes read back in the first copy
     uint8_t *dev = nullptr;
@@ -123,7 +123,8 @@ struct LossyGroup {
         o_sprev = al(o_bmax + lv);
         o_slots = al(o_sprev + lv);
         o_foff = al(o_slots + (size_t)frames * lossy_slot_bytes((int)nch));
-        o_out = al(o_foff + (frames + 1) * 8);
+        o_inf = al(o_foff + (frames + 1) * 8);   // LossyArgs::inf_mark, zeroed per step
+        o_out = al(o_inf + S * nch * 32 * 8);
         work_bytes = o_out - in_bytes;
         r_lvl = al(frames * 4);
         r_tot = al(r_lvl + S * nch * kBands * 4);
@@ -204,6 +205,9 @@ int enqueue_group(flo_ctx *c, LossyGroup &g) {
     A.frame_off = (unsigned long long *)(d + g.o_foff);
     A.n_cus = c->prop.multiProcessorCount;
     A.exact = lossy_exact(false, A.T);
+    A.inf_mark = (unsigned long long *)(d + g.o_inf);
+    A.inf_tag = 1;
+    HIPCHK(c, hipMemsetAsync(A.inf_mark, 0, S * nch * 32 * 8, c->stream));
     const float *d_seed = (const float *)(d + g.o_seed);
     float *d_lvl = (float *)(out + g.r_lvl);
     int rc;

@@ -69,13 +69,15 @@ extern "C" int flo_batch_size_curve(flo_batch *b, size_t n_q, const float *quali
         groups.push_back(g);
     }
     DevBuf<float> d_at, d_sprev, d_bmax;
+    DevBuf<unsigned long long> d_inf;   // LossyArgs::inf_mark, a tag per group
     DevBuf<unsigned long long> d_rel, d_sizes;
     QuiesceOnExit quiesce(c);
-    if (!d_at.alloc(max_frames * ch * 32) || !d_sprev.alloc(max_frames * ch * 32) || (ch == 2 && !d_bmax.alloc(max_frames * ch * 32)) ||
+    if (!d_at.alloc(max_frames * ch * 32) || !d_inf.alloc(n * ch * 32) || !d_sprev.alloc(max_frames * ch * 32) || (ch == 2 && !d_bmax.alloc(max_frames * ch * 32)) ||
         !d_rel.alloc(n) || !d_sizes.alloc(n * K))
         return fail(c, FLO_ERR_NOMEM, "size curve scratch");
     HIPCHK(c, hipMemcpyAsync(d_rel.p, rel.data(), n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_sizes.p, 0, n * K * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_inf.p, 0, n * ch * 32 * 8, c->stream));
     const unsigned long long *plan = (const unsigned long long *)b->d_plan;
     const FrameKernel pass1 = ch == 1 ? FrameKernel::Mono1 : ch == 2 ? FrameKernel::Pair1 : FrameKernel::Multi1;
     for (const Group &g : groups) {
@@ -93,6 +95,8 @@ extern "C" int flo_batch_size_curve(flo_batch *b, size_t n_q, const float *quali
         A.bmax_t = d_bmax.p;
         A.s_prev_out = d_sprev.p;
         A.s_prev = d_sprev.p;
+        A.inf_mark = d_inf.p;
+        A.inf_tag++;   // (inf_tag shares its storage with epoch, which nothing sets on this struct: frame-parallel launches only)
         A.slot_bytes = lossy_slot_bytes(ch);
         int rc;
         if ((rc = timed_launch(c, "curve_bands", [&] { return launch_lossy_frames_pass(A, pass1, c->stream); })) != FLO_OK) return rc;

@@ -1,4 +1,4 @@
-// stages.cpp — the stage entry points (flo_mdct_forward, flo_lossy_analyze / quantize / quantize_smr, flo_sparse_pack):
+// stages.cpp — the stage entry points (flo_mdct_forward, flo_lossy_analyze / quantize / pack_frames / quantize_smr, flo_sparse_pack):
 // single stages of the lossy encoder on host buffers, for tests against the reference's stages.
 #include <cstring>
 
@@ -28,7 +28,8 @@ extern "C" int flo_mdct_forward(flo_ctx *c, const float *frames, size_t n_frames
 }
 
 static int analyze_common(flo_ctx *c, const float *pcm, size_t n, const float *in_coeffs, size_t in_hops, uint32_t sr,
-                          uint8_t ch, float quality, int exact, float *coeffs, int16_t *q, uint16_t *sfw, size_t *num_hops) {
+                          uint8_t ch, float quality, int exact, float *coeffs, int16_t *q, uint16_t *sfw, size_t *num_hops,
+                          uint8_t *data = nullptr, size_t data_cap = 0, size_t *data_len = nullptr, uint32_t *frame_sizes = nullptr) {
     flo_batch *b = nullptr;
     size_t n_il = in_coeffs ? (in_hops ? (in_hops - 1) * 1024 * ch : 0) : n;
     if (in_coeffs && in_hops == 0) return FLO_OK;
@@ -63,6 +64,32 @@ static int analyze_common(flo_ctx *c, const float *pcm, size_t n, const float *i
     if (e == hipSuccess && q) e = hipMemcpy(q, b->d_dbg_q, per * 1024 * 2, hipMemcpyDeviceToHost);
     if (e == hipSuccess && sfw) e = hipMemcpy(sfw, b->d_dbg_sfw, per * 25 * 2, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return done(fail(c, FLO_ERR_DEVICE, std::string("analysis D2H: ") + hipGetErrorString(e)));
+    if (data_len) {   // the clip's DATA chunk and frame sizes, read out of its finished file (header 70 bytes, TOC, DATA)
+        uint8_t *file = nullptr;
+        size_t len = 0;
+        rc = flo_batch_fetch(b, 0, nullptr, 0, &file, &len);
+        if (rc != FLO_OK) return done(rc);
+        uint32_t n_toc = 0;
+        uint64_t toc_size = 0, data_size = 0;
+        bool ok = len >= 74;
+        if (ok) {
+            memcpy(&toc_size, file + 38, 8);
+            memcpy(&data_size, file + 46, 8);
+            memcpy(&n_toc, file + 70, 4);
+            ok = n_toc == hops && toc_size == 4 + 20 * (uint64_t)hops && 70 + toc_size + data_size <= len;
+        }
+        if (ok && data_size > data_cap) {
+            flo_free(file);
+            return done(fail(c, FLO_ERR_ARG, "output buffer too small"));
+        }
+        if (ok) {
+            for (size_t h = 0; frame_sizes && h < hops; h++) memcpy(&frame_sizes[h], file + 74 + 20 * h + 12, 4);
+            if (data_size) memcpy(data, file + 70 + toc_size, data_size);
+            *data_len = data_size;
+        }
+        flo_free(file);
+        if (!ok) return done(fail(c, FLO_ERR_DEVICE, "flo_lossy_pack_frames: the finished file does not parse"));
+    }
     return done(FLO_OK);
 }
 
@@ -75,6 +102,13 @@ extern "C" int flo_lossy_quantize(flo_ctx *c, const float *coeffs, size_t num_ho
                                   float quality, int exact, int16_t *q, uint16_t *sfw) {
     if (!c || (num_hops && !coeffs)) return FLO_ERR_ARG;
     return analyze_common(c, nullptr, 0, coeffs, num_hops, sr, ch, quality, exact, nullptr, q, sfw, nullptr);
+}
+
+extern "C" int flo_lossy_pack_frames(flo_ctx *c, const float *coeffs, size_t num_hops, uint32_t sr, uint8_t ch, float quality,
+                                     int16_t *q, uint16_t *sfw, uint8_t *data, size_t data_cap, size_t *data_len, uint32_t *frame_sizes) {
+    if (!c || !data_len || (num_hops && (!coeffs || !data || !frame_sizes))) return FLO_ERR_ARG;
+    *data_len = 0;
+    return analyze_common(c, nullptr, 0, coeffs, num_hops, sr, ch, quality, 0, nullptr, q, sfw, nullptr, data, data_cap, data_len, frame_sizes);
 }
 
 extern "C" int flo_lossy_quantize_smr(flo_ctx *c, const float *coeffs, const float *smr, size_t n_vec, uint32_t sr, float quality,

@@ -252,7 +252,8 @@ int flo_batch_fill_synthetic(flo_batch *b, uint32_t seed, uint64_t clip_id0);
  * per channel, 2: frame-parallel kernels, 5: clip-chain kernel with one transform wave that carries both channels in
  * lock-step (packed f32 arithmetic) + one quantiser-and-packer wave per stereo clip, persistent workgroups that deal
  * the clips dynamically: the form auto picks for stereo batches; 3 and 4 (stereo chain forms of earlier rounds,
- * retired) mean 5 (lossy only; all forms produce identical bytes; 5 falls back to 1 for mono) */
+ * retired) mean 5 (lossy only; all forms produce identical bytes, a masking level of +inf - a band energy that overflows
+ * f32 - included: the frame-parallel form records where one first occurs; 5 falls back to 1 for mono) */
 int flo_batch_encode(flo_batch *b, int which);
 int flo_batch_sync(flo_batch *b);
 /* after sync: total compressed DATA bytes of the batch, and of one clip */
@@ -593,6 +594,13 @@ int flo_lossy_analyze(flo_ctx *ctx, const float *pcm, size_t n_interleaved, uint
  * of the threshold with the reference's own dB-domain f32 expression (a test yardstick, never used by an encode). */
 int flo_lossy_quantize(flo_ctx *ctx, const float *coeffs, size_t num_hops, uint32_t sample_rate, uint8_t channels,
                        float quality, int exact, int16_t *quantized, uint16_t *sf_words);
+/* flo_lossy_quantize (exact = 0) that keeps what the encode wrote: beside the integers and scale words (either may be NULL)
+ * the clip's DATA chunk (data_cap bytes of room, *data_len written; FLO_ERR_ARG when it does not fit) and the size of each
+ * of its num_hops frames. The form is the one flo_ctx_force_path names (5: the lock-step chain kernel's coefficient-input
+ * instantiation, 2: the frame-parallel kernels, otherwise 1), so the packer of each form runs on hand-made spectra. */
+int flo_lossy_pack_frames(flo_ctx *ctx, const float *coeffs, size_t num_hops, uint32_t sample_rate, uint8_t channels,
+                          float quality, int16_t *quantized, uint16_t *sf_words, uint8_t *data, size_t data_cap,
+                          size_t *data_len, uint32_t *frame_sizes);
 /* TransformEncoder::quantize_coefficients as the reference exposes it (lossy/encoder.rs:109-154): n_vec vectors of 1024
  * coefficients with the caller's own signal-to-mask ratios -> i16 (kept iff smr > the quality's threshold, c * scale factor
  * rounded half away from zero) and the 25 band scale factors (30000 / band maximum, 1.0 for a silent band) per vector.
