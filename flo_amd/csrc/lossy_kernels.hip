@@ -25,6 +25,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "chain2q_roles.hpp"
 #include "crc_device.hpp"
 #include "lossy_device.hpp"
 #include "lossy_kernels.hpp"
@@ -601,8 +602,10 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
     }
     __syncthreads();
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // waves 0 .. g-1 are the transform waves, waves g .. 2g-1 the packers
-    const int cl = wv % clips_per_wg;
+    // which slot this wave serves, and as what: chain2q_roles.hpp (every slot's two waves on different SIMDs, the SIMDs'
+    // instruction loads as even as 2g waves on four SIMDs allow)
+    const Chain2qRole role = chain2q_role(clips_per_wg, wv);
+    const int cl = role.slot;
     Clip2qLds &cs = *reinterpret_cast<Clip2qLds *>(lds_raw + kPackBytesHotT + (size_t)cl * sizeof(Clip2qLds));
     // Clips are dealt dynamically: the workgroups are persistent (one per CU, the LDS holds no second one) and every
     // (transform wave, packer wave) pair takes the next unclaimed clip of the batch when it has finished one, so CUs
@@ -610,13 +613,17 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
     // its transform wave through LDS; frame counters run on across clips (fbase), so nothing is ever reset. The two
     // roles are two separate loops so that neither's registers are live in the other's code.
     uint32_t fbase = 0, seq = 0;
-    if (wv >= clips_per_wg) {
+    if (role.packer) {
         // ------------------------------------------------------------------ packer: quantise, serialise, flush
         // its clip slot waits for this wave (the transform wave has a third of a frame to spare): it goes first on its SIMD
 #ifndef FLO_PRIO_P
 #define FLO_PRIO_P 1
 #endif
         __builtin_amdgcn_s_setprio(FLO_PRIO_P);
+        // Two packers on one SIMD have the same priority and the older one wins issue: its slot runs ahead, the other's
+        // is the launch's last. Where the launcher asks (launches of one round, whose length is their slowest slot's),
+        // such packers go first in turn, by the parity of the clip's frame. 0: no turns, 1 / 2: first on odd / even frames
+        const uint32_t pturn = A.chain2q_pturns && chain2q_peers_on_simd(clips_per_wg, wv) > 1 ? 1u + (uint32_t)(chain2q_rank_on_simd(clips_per_wg, wv) & 1) : 0u;
         typedef __attribute__((address_space(3))) v4f lds_v4f;
         float athn[16];
         uint32_t ts_a[16];
@@ -666,6 +673,10 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             for (unsigned h = 0; h < hops; h++) {
                 const int ln = lane_id_opaque();
                 const uint32_t g = fbase + h;
+                if (pturn) {   // uniform
+                    if ((h + pturn) & 1u) __builtin_amdgcn_s_setprio(FLO_PRIO_P);
+                    else __builtin_amdgcn_s_setprio(FLO_PRIO_P + 1);
+                }
                 // The next frame's coefficients are taken as soon as the transform wave has them and this wave's registers
                 // are free (behind the quantiser, between the channels' blobs, in front of the flush): the sooner the
                 // transform wave has its buffer back, the less it waits in front of its next FFT exchange.
@@ -819,7 +830,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
 #ifdef FLO_STAMPS
             if (A.dbg_stamps && lane == 0) {
                 st_sum[13] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) |
-                             ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11)) << 32) | ((unsigned long long)cl << 40);
+                             ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11)) << 32) | ((unsigned long long)cl << 40) | ((unsigned long long)wv << 48);
                 for (int i = 0; i < 14; i++) A.dbg_stamps[((unsigned long long)clip * 2 + 1) * 16 + i] = st_sum[i];
                 A.dbg_stamps[((unsigned long long)clip * 2 + 1) * 16 + 14] = __builtin_amdgcn_s_memrealtime();   // when the clip's bytes were out
             }
@@ -1001,9 +1012,9 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             mask_publish(ln, fbase + hops - 1u, hops - 1u, pend_e, pend_m, reinterpret_cast<const float *>(T.pack + kRowS10 * 64)[64 + ln], sd0, sd1);
         }
 #ifdef FLO_STAMPS
-        if (A.dbg_stamps && lane == 0) {   // [13]: where the wave ran (HW_ID, XCC_ID, clip slot): diag/stamps_clips.py groups the records by it
+        if (A.dbg_stamps && lane == 0) {   // [13]: where the wave ran (HW_ID, XCC_ID, clip slot, wave of the workgroup): diag/stamps_clips.py groups the records by it
             st_sum[13] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) |
-                         ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11)) << 32) | ((unsigned long long)cl << 40);
+                         ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11)) << 32) | ((unsigned long long)cl << 40) | ((unsigned long long)wv << 48);
             for (int i = 0; i < 14; i++) A.dbg_stamps[((unsigned long long)clip * 2) * 16 + i] = st_sum[i];
             A.dbg_stamps[((unsigned long long)clip * 2) * 16 + 14] = __builtin_amdgcn_s_memrealtime();   // when the clip's last frame left the transform wave (100 MHz)
         }
@@ -1945,7 +1956,15 @@ static int launch_chain2q_t(const LossyArgs &A, int clips, hipStream_t s) {
     if (int rc = allow_big_lds(reinterpret_cast<const void *>(&lossy_chain2q_kernel<COEFFS, DIRTY, DBG>))) return rc;
     unsigned wgs = (unsigned)((A.n_clips + g - 1) / g);
     if (A.n_cus > 0 && wgs > (unsigned)A.n_cus) wgs = (unsigned)A.n_cus;   // persistent: one workgroup per CU, clips dealt dynamically
-    hipLaunchKernelGGL((lossy_chain2q_kernel<COEFFS, DIRTY, DBG>), dim3(wgs), dim3(128 * g), lds, s, A, g);
+    // One round (no slot takes a second clip): the launch ends with its slowest slot and nothing is dealt that could
+    // even the slots out, so packers that share a SIMD take turns at going first (kernel: pturn). With more rounds the
+    // dealing evens the slots out.
+#ifndef FLO_C2Q_PTURNS
+#define FLO_C2Q_PTURNS 1
+#endif
+    LossyArgs B = A;
+    B.chain2q_pturns = (unsigned long long)wgs * (unsigned)g >= (unsigned long long)A.n_clips ? FLO_C2Q_PTURNS : 0u;
+    hipLaunchKernelGGL((lossy_chain2q_kernel<COEFFS, DIRTY, DBG>), dim3(wgs), dim3(128 * g), lds, s, B, g);
     FLO_LAUNCH_CHECK();
     return 0;
 }

@@ -66,6 +66,8 @@ struct LossyArgs {
     };
     const unsigned int *crc_tab;             // crc_device_tables()
     int n_cus;                               // compute units of the device (persistent workgroups)
+    unsigned int chain2q_pturns;             // lock-step stereo form, set by its launcher (launches of one round): packers that share
+                                             // a SIMD go first in turn, frame by frame (0: the older one always wins issue)
 };
 
 // Whether a launch runs the exact-threshold instantiations (quantise<., EXACT = true>): when the caller asks for the
