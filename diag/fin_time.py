@@ -11,6 +11,6 @@ for _ in range(3):
 ctx.profile_reset()
 for _ in range(10):
     b.encode(0); b.sync()
-for k in ("lossy_chain3", "finish_files"):
+for k in ("lossy_chain2q", "finish_files"):
     ms, cnt = ctx.profile_query(k)
     print(k, round(ms / max(cnt, 1), 4), "ms")

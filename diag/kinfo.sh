@@ -1,7 +1,7 @@
 #!/bin/bash
 # VGPR / SGPR / scratch / LDS of the kernels in a built library (every gfx950 code object in it):
 #   diag/kinfo.sh [lib] [name-regex]
-lib=${1:-flo_amd/libflo_hip.so}; pat=${2:-chain2x}
+lib=${1:-flo_amd/libflo_hip.so}; pat=${2:-lossy_chain2q_kernel}
 tmp=$(mktemp -d)
 python3 - "$lib" "$tmp" <<'PY'
 import struct, sys

@@ -1,5 +1,6 @@
 #!/bin/bash
-# per-phase ticks + per-slot records of the lock-step chain kernels (FLO_STAMPS build): diag/stamps_q.sh "FLO_CHAIN2Q=0" "FLO_CHAIN2Q=1"
+# per-phase ticks + per-slot records of the lock-step chain kernel (FLO_STAMPS build), once per environment setting:
+#   diag/stamps_q.sh "FLO_CHAIN2X_CLIPS=5" "FLO_CHAIN2X_CLIPS=6"   (clips per workgroup; "FLO_TAIL_CRC=0": no CRC in the tail)
 R=$GRAFT_REPO_ROOT; cd $R
 for v in "$@"; do
   echo "== env=$v clips=10000"

@@ -332,9 +332,6 @@ static int batch_encode_launch(flo_batch *b) {
         rc = timed_launch(c, "lossy_chain2q", [&] { return launch_lossy_chain2q(A, P, c->stream); });
         if (rc == FLO_OK) b->epoch = epoch;   // (a launch that did not run zeroed nothing: its epoch is used again)
     } else if (P.form == LossyForm::Chain) {
-#ifdef FLO_STAMPS
-        if (!b->d_stamps) HIPCHK(c, pool_alloc(&b->d_stamps, b->n_clips * b->ch * 16 * 8));
-#endif
         LossyArgs A = make_args(b);
         rc = timed_launch(c, "lossy_chain", [&] { return launch_lossy_chain(A, P, c->stream); });
     } else {   // frame-parallel form
@@ -401,6 +398,59 @@ extern "C" int flo_batch_encode(flo_batch *b, int which) {
     return erc;
 }
 
+// FLO_STAMPS builds (diagnostic, see lossy_kernels.hip): what the waves of the last lossy_chain2q launch recorded, as two
+// [stamps2x] lines on stderr; FLO_STAMPS_DUMP=file keeps the raw per-clip records for diag/stamps_clips.py.
+#ifdef FLO_STAMPS
+static int stamps_report(flo_batch *b) {
+    flo_ctx *c = b->ctx;
+    if (!b->d_stamps || b->plan.form != LossyForm::Chain2q) return FLO_OK;
+    std::vector<unsigned long long> st(b->n_clips * 2 * 16);   // [clip][transform wave, packer][16]
+    HIPCHK(c, hipMemcpy(st.data(), b->d_stamps, st.size() * 8, hipMemcpyDeviceToHost));
+    double t[14] = {0}, p[14] = {0};
+    for (size_t k = 0; k < b->n_clips; k++)
+        for (int i = 0; i < 14; i++) { t[i] += (double)st[(2 * k) * 16 + i]; p[i] += (double)st[(2 * k + 1) * 16 + i]; }
+    static const char *tn[] = {"fold", "prefetch", "fft", "postrot", "bandstats", "mask", "quant", "wait-consumed", "handover"};
+    static const char *pn[] = {"wait-ready", "read/quant", "pack0", "pack1", "flush", "wait-ts"};
+    fprintf(stderr, "[stamps2x] ticks (10 ns) per stereo frame | T:");
+    double tt = 0, pt = 0;
+    for (int i = 0; i < 9; i++) { fprintf(stderr, " %s=%.1f", tn[i], t[i] / b->total_frames); tt += t[i]; }
+    fprintf(stderr, " total=%.1f | P:", tt / b->total_frames);
+    for (int i = 0; i < 6; i++) { fprintf(stderr, " %s=%.1f", pn[i], p[i] / b->total_frames); pt += p[i]; }
+    fprintf(stderr, " total=%.1f item-form declined %.4f of channel-frames", pt / b->total_frames, p[6] / (2.0 * b->total_frames));
+    fprintf(stderr, " | T waits>1000: %.2f%% of frames, %.0f cyc/frame avg; >5000: %.2f%%, %.0f | P busy>12000: %.2f%%, %.0f; >20000: %.2f%%, %.0f\n",
+            100 * t[10] / b->total_frames, t[9] / b->total_frames, 100 * t[12] / b->total_frames, t[11] / b->total_frames,
+            100 * p[10] / b->total_frames, p[9] / b->total_frames, 100 * p[12] / b->total_frames, p[11] / b->total_frames);
+    // per clip: the packer's busy ticks per frame against the transform's (who waits for whom is a property
+    // of the clip's content): deciles over the clips
+    std::vector<double> pb(b->n_clips), tb(b->n_clips);
+    for (size_t k = 0; k < b->n_clips; k++) {
+        const double fr = (double)b->hops[k] > 0 ? (double)b->hops[k] : 1.0;
+        double tq = 0, pq = 0;
+        for (int i = 0; i < 9; i++) if (i != 7) tq += (double)st[(2 * k) * 16 + i];
+        for (int i = 1; i < 5; i++) pq += (double)st[(2 * k + 1) * 16 + i];
+        tb[k] = tq / fr; pb[k] = pq / fr;
+    }
+    if (const char *dump = getenv("FLO_STAMPS_DUMP")) {   // raw per-clip records for diag/stamps_clips.py
+        if (FILE *fh = fopen(dump, "wb")) {
+            fwrite(st.data(), 8, st.size(), fh);
+            fclose(fh);
+        }
+    }
+    std::vector<double> ps = pb, ts = tb;
+    std::sort(ps.begin(), ps.end()); std::sort(ts.begin(), ts.end());
+    fprintf(stderr, "[stamps2x] per-clip busy ticks per frame, deciles | P:");
+    for (int d = 0; d <= 10; d++) fprintf(stderr, " %.0f", ps[std::min(b->n_clips - 1, (size_t)(d * (b->n_clips - 1) / 10))]);
+    fprintf(stderr, " | T:");
+    for (int d = 0; d <= 10; d++) fprintf(stderr, " %.0f", ts[std::min(b->n_clips - 1, (size_t)(d * (b->n_clips - 1) / 10))]);
+    size_t pbound = 0;
+    for (size_t k = 0; k < b->n_clips; k++) pbound += pb[k] > tb[k];
+    fprintf(stderr, " | clips whose packer is busier than their transform: %.1f%%\n", 100.0 * pbound / b->n_clips);
+    return FLO_OK;
+}
+#else
+static int stamps_report(flo_batch *) { return FLO_OK; }
+#endif
+
 // done = nullptr: wait for the context's stream; else wait for that event only (recorded behind the batch's encode):
 // the pipeline of flo_encode_batch must not wait for the NEXT chunk's work that is already queued on the stream
 static int batch_sync_impl(flo_batch *b, hipEvent_t done) {
@@ -436,63 +486,7 @@ static int batch_sync_impl(flo_batch *b, hipEvent_t done) {
                 fprintf(stderr, "[tail] clips %zu: CRC in the encode's tail %zu, in finish_files %zu\n", b->n_clips, tail, b->n_clips - tail);
             }
 #endif
-#ifdef FLO_STAMPS
-            if (b->d_stamps) {
-                std::vector<unsigned long long> st(b->n_clips * b->ch * 16);
-                HIPCHK(c, hipMemcpy(st.data(), b->d_stamps, st.size() * 8, hipMemcpyDeviceToHost));
-                double sum[14] = {0};
-                for (size_t w = 0; w < b->n_clips * b->ch; w++)
-                    for (int i = 0; i < 14; i++) sum[i] += (double)st[w * 16 + i];
-                double frames = (double)b->total_frames * b->ch;
-                if (b->plan.form == LossyForm::Chain2q) {   // lock-step form: wave 0 = transform, wave 1 = packer
-                    double t[14] = {0}, p[14] = {0};
-                    for (size_t k = 0; k < b->n_clips; k++)
-                        for (int i = 0; i < 14; i++) { t[i] += (double)st[(2 * k) * 16 + i]; p[i] += (double)st[(2 * k + 1) * 16 + i]; }
-                    static const char *tn[] = {"fold", "prefetch", "fft", "postrot", "bandstats", "mask", "quant", "wait-consumed", "handover"};
-                    static const char *pn[] = {"wait-ready", "read/quant", "pack0", "pack1", "flush", "wait-ts"};
-                    fprintf(stderr, "[stamps2x] ticks (10 ns) per stereo frame | T:");
-                    double tt = 0, pt = 0;
-                    for (int i = 0; i < 9; i++) { fprintf(stderr, " %s=%.1f", tn[i], t[i] / b->total_frames); tt += t[i]; }
-                    fprintf(stderr, " total=%.1f | P:", tt / b->total_frames);
-                    for (int i = 0; i < 6; i++) { fprintf(stderr, " %s=%.1f", pn[i], p[i] / b->total_frames); pt += p[i]; }
-                    fprintf(stderr, " total=%.1f item-form declined %.4f of channel-frames", pt / b->total_frames, p[6] / (2.0 * b->total_frames));
-                    fprintf(stderr, " | T waits>1000: %.2f%% of frames, %.0f cyc/frame avg; >5000: %.2f%%, %.0f | P busy>12000: %.2f%%, %.0f; >20000: %.2f%%, %.0f\n",
-                            100 * t[10] / b->total_frames, t[9] / b->total_frames, 100 * t[12] / b->total_frames, t[11] / b->total_frames,
-                            100 * p[10] / b->total_frames, p[9] / b->total_frames, 100 * p[12] / b->total_frames, p[11] / b->total_frames);
-                    // per clip: the packer's busy ticks per frame against the transform's (who waits for whom is a property
-                    // of the clip's content): deciles over the clips
-                    std::vector<double> pb(b->n_clips), tb(b->n_clips);
-                    for (size_t k = 0; k < b->n_clips; k++) {
-                        const double fr = (double)b->hops[k] > 0 ? (double)b->hops[k] : 1.0;
-                        double tq = 0, pq = 0;
-                        for (int i = 0; i < 9; i++) if (i != 7) tq += (double)st[(2 * k) * 16 + i];
-                        for (int i = 1; i < 5; i++) pq += (double)st[(2 * k + 1) * 16 + i];
-                        tb[k] = tq / fr; pb[k] = pq / fr;
-                    }
-                    if (const char *dump = getenv("FLO_STAMPS_DUMP")) {   // raw per-clip records for diag/stamps_clips.py
-                        if (FILE *fh = fopen(dump, "wb")) {
-                            fwrite(st.data(), 8, st.size(), fh);
-                            fclose(fh);
-                        }
-                    }
-                    std::vector<double> ps = pb, ts = tb;
-                    std::sort(ps.begin(), ps.end()); std::sort(ts.begin(), ts.end());
-                    fprintf(stderr, "[stamps2x] per-clip busy ticks per frame, deciles | P:");
-                    for (int d = 0; d <= 10; d++) fprintf(stderr, " %.0f", ps[std::min(b->n_clips - 1, (size_t)(d * (b->n_clips - 1) / 10))]);
-                    fprintf(stderr, " | T:");
-                    for (int d = 0; d <= 10; d++) fprintf(stderr, " %.0f", ts[std::min(b->n_clips - 1, (size_t)(d * (b->n_clips - 1) / 10))]);
-                    size_t pbound = 0;
-                    for (size_t k = 0; k < b->n_clips; k++) pbound += pb[k] > tb[k];
-                    fprintf(stderr, " | clips whose packer is busier than their transform: %.1f%%\n", 100.0 * pbound / b->n_clips);
-                }
-                static const char *nm[] = {"wait-loads+fold", "issue-loads", "fft", "postrot", "analyse(bands,psy,quant,plan)",
-                                           "sync-tot", "emit", "sync-emit", "flush", "sync-tail"};
-                fprintf(stderr, "[stamps] s_memtime ticks (100 MHz) per frame-channel:");
-                for (int i = 0; i < 10; i++) fprintf(stderr, " %s=%.0f", nm[i], sum[i] / frames);
-                fprintf(stderr, " | inside analyse: bands=%.0f psy=%.0f quantise=%.0f (plan = analyse rest)", sum[10] / frames, sum[11] / frames, sum[12] / frames);
-                fprintf(stderr, "\n");
-            }
-#endif
+            if (int rc = stamps_report(b)) return rc;
         } else {
             std::string err;
             if (lossless_collect(b->ll, err) != 0) return fail(c, FLO_ERR_DEVICE, "lossless collect: " + err);

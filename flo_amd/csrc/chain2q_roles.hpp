@@ -50,11 +50,7 @@ constexpr uint64_t kChain2qWord5 = 0xBAC4893210ull;
 
 FLO_ROLES_HD constexpr uint64_t chain2q_role_word(int g) {
     constexpr uint64_t w1 = chain2q_rule_word(1), w2 = chain2q_rule_word(2), w3 = chain2q_rule_word(3), w6 = chain2q_rule_word(6);
-#ifdef FLO_C2Q_FIRST_RULE   // diagnostic builds: the first rule at every g (diag/abn_shard.sh compares the two)
-    constexpr uint64_t w4 = chain2q_rule_word(4), w5 = chain2q_rule_word(5);
-#else
     constexpr uint64_t w4 = kChain2qWord4, w5 = kChain2qWord5;
-#endif
     return g == 1 ? w1 : g == 2 ? w2 : g == 3 ? w3 : g == 4 ? w4 : g == 5 ? w5 : w6;
 }
 FLO_ROLES_HD constexpr Chain2qRole chain2q_role(int g, int wave) {

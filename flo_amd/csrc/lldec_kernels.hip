@@ -499,9 +499,6 @@ __device__ __forceinline__ void predict_rows(const LlParArgs &A, const unsigned 
             buf[j] = i < n ? r[i] : 0;
         }
     };
-#ifdef FLO_PRED_DBG
-    const unsigned long long dbg_t0 = __builtin_readcyclecounter(), dbg_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     int pf[kSb], outs[kSb];
     fetch(pf, 1u);   // (while block b is stepped, the other accumulator is armed with the residuals of block b + 1)
 #pragma unroll
@@ -582,9 +579,6 @@ __device__ __forceinline__ void predict_rows(const LlParArgs &A, const unsigned 
         }
     }
     const bool bad = !(worst < 2147483648.0);
-#ifdef FLO_PRED_DBG
-    if (lane == 0 && (blockIdx.x == 7 || (__builtin_amdgcn_s_memrealtime() - dbg_r0) > 110000ull)) printf("rows wg %u: nb %u cycles %llu realtime(100MHz) %llu\n", blockIdx.x, nb, (unsigned long long)(__builtin_readcyclecounter() - dbg_t0), (unsigned long long)(__builtin_amdgcn_s_memrealtime() - dbg_r0));
-#endif
     if (bad) A.serial[chi] = 1;
 }
 
@@ -616,13 +610,7 @@ __global__ __launch_bounds__(64) void ll_predict_kernel(LlParArgs A) {
     const unsigned oi = blockIdx.x - groups;   // (uniform)
     if (oi >= A.n_others) return;
     const unsigned chi = A.others[oi];
-#ifdef FLO_PRED_DBG
-    const unsigned long long dbg_f0 = __builtin_amdgcn_s_memrealtime();
-#endif
     if (!takes_rows(A, chi, order)) predict_one(A, chi, lane, cs);
-#ifdef FLO_PRED_DBG
-    if (lane == 0 && (chi == 5 || (__builtin_amdgcn_s_memrealtime() - dbg_f0) > 60000ull)) printf("other wg %u chi %u realtime(100MHz) %llu\n", blockIdx.x, chi, (unsigned long long)(__builtin_amdgcn_s_memrealtime() - dbg_f0));
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------ launcher

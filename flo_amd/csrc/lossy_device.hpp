@@ -45,11 +45,7 @@ struct LossyDevTables {
 
 constexpr int kXchStride = 9;            // complex elements per exchange row (8 + 1 pad)
 constexpr int kXchFloats = 64 * kXchStride * 2;  // 1152 floats per channel
-#ifdef FLO_COEF_PAD16
-constexpr int kCoefFloats = 1280;
-#else
 constexpr int kCoefFloats = 1152;        // 1024 coefficients, 4 floats of padding per 32 (see post_rotate_transpose)
-#endif
 constexpr int kSlotCap = 96;
 constexpr int kFrameCap = 4352;          // >= 16 + 6+4+2+100+2*(4+2064), multiple of 16
 
@@ -93,11 +89,6 @@ __device__ __forceinline__ void wave_sync() {
     asm volatile("" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
-}
-// Workgroup barrier that orders LDS traffic only: outstanding global loads (the next half-frame's prefetch) and
-// stores (the previous frame's flush) stay in flight across it, unlike __syncthreads() which drains vmcnt(0).
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 // ------------------------------------------------------------------------------------------------ scalar helpers
@@ -446,11 +437,7 @@ __device__ __forceinline__ void post_rotate_transpose(const int lane, const floa
         const float4 t4 = T.pack[(kRowTw + (r >> 1)) * 64 + lane];
         const float2 w = (r & 1) ? make_float2(t4.z, t4.w) : make_float2(t4.x, t4.y);
         const int k0 = 2 * m, k1 = 1023 - 2 * m;
-#ifdef FLO_COEF_PAD16
-        const int p0 = k0 + 4 * (k0 >> 4), p1 = k1 + 4 * (k1 >> 4);
-#else
         const int p0 = k0 + 4 * (k0 >> 5), p1 = k1 + 4 * (k1 >> 5);
-#endif
 #pragma unroll
         for (int ch = 0; ch < CH; ch++) {
             float R = fmaf(-zi[ch][r], w.y, -(zr[ch][r] * w.x));
@@ -462,11 +449,7 @@ __device__ __forceinline__ void post_rotate_transpose(const int lane, const floa
     wave_sync();
 #pragma unroll
     for (int ch = 0; ch < CH; ch++) {
-#ifdef FLO_COEF_PAD16
-        const float4 *p = reinterpret_cast<const float4 *>(&coef[ch][20 * lane]);
-#else
         const float4 *p = reinterpret_cast<const float4 *>(&coef[ch][16 * lane + 4 * (lane >> 1)]);
-#endif
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             float4 v = p[q];
@@ -852,25 +835,6 @@ __device__ __forceinline__ float spread_threshold(const int lane, float energy, 
     return m + (-6.0f);
 }
 
-// x = max(x, x of the lane CTRL names); lanes without a source keep x. One instruction: the maximum itself carries the
-// DPP modifier (the generic dpp_f + max_raw pair costs a constant load, a move and the maximum). The s_nop covers the
-// two wait states a DPP read needs behind the vector write of its source.
-template <int CTRL>
-__device__ __forceinline__ float max_self_dpp(float x) {
-    static_assert(CTRL == 0x101 || CTRL == 0x102 || CTRL == 0x104 || CTRL == 0x108, "row_shl:1/2/4/8");
-    if (CTRL == 0x101) asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shl:1 row_mask:0xf bank_mask:0xf" : "+v"(x));
-    if (CTRL == 0x102) asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shl:2 row_mask:0xf bank_mask:0xf" : "+v"(x));
-    if (CTRL == 0x104) asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0xf" : "+v"(x));
-    if (CTRL == 0x108) asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shl:8 row_mask:0xf bank_mask:0xf" : "+v"(x));
-    return x;
-}
-// value of lane - 1, lane 0 receives lane 63's (wave_ror:1): every lane has a source, so no `old` operand to prepare
-__device__ __forceinline__ float ror1(float x) {
-    float r;
-    asm("s_nop 1\n\tv_mov_b32_dpp %0, %1 wave_ror:1 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x));
-    return r;
-}
-
 // The same for both channels of a stereo frame in ONE pass: channel 0's bands on lanes 0..24, channel 1's on lanes
 // 32..56 (band = lane & 31). Every lane goes through exactly the operations of spread_threshold; what differs is the
 // bookkeeping between the halves: the row-0 / row-2 lanes take bands 16..24 from lane 16 / 48, and the shifted copy of
@@ -1138,11 +1102,7 @@ __device__ __forceinline__ void band_stats_2(const int lane, const v2f (&c)[16],
                 am.w = max_abs_raw(am.w, c[e].y);
             }
             if ((dirty >> e) & 1u) {   // compile-time
-#ifdef FLO_MASKED_SLOTS   // diagnostic: only the lanes that close a segment here store (the others' stores went to per-lane trash slots)
-                if (kp[k] == 0.0f || e == 15) *reinterpret_cast<lds_v4f *>((uintptr_t)(s0 + 2u * dv[k])) = am;
-#else
                 *reinterpret_cast<lds_v4f *>((uintptr_t)(s0 + 2u * dv[k])) = am;
-#endif
                 if (e < 15) {
                     am.xy = am.xy * splat2(kp[k]);
                     am.zw = am.zw * splat2(kp[k]);
@@ -1485,9 +1445,6 @@ __device__ __forceinline__ void sparse_emit_n(const int lane, const int (&q)[CH]
     for (int c = 0; c < CH; c++) {
         m[c] = P[c].M & 0xFFFFu;
         hm[c] = P[c].M >> 16;
-#ifdef FLO_EMIT_NOHDR
-        hm[c] = 0;
-#endif
         nn_rel[c] = P[c].nn - base;
         nzend_rel[c] = P[c].nz_end - base;
         any |= hm[c];
@@ -1521,7 +1478,6 @@ __device__ __forceinline__ void sparse_emit_n(const int lane, const int (&q)[CH]
         }
     }
     // values: every position stores two bytes, zeros go to the trash bytes
-#ifndef FLO_EMIT_NOVAL
 #pragma unroll
     for (int i = 0; i < 16; i++) {
 #pragma unroll
@@ -1534,7 +1490,6 @@ __device__ __forceinline__ void sparse_emit_n(const int lane, const int (&q)[CH]
             dst[c][o + 1] = (uint8_t)(v >> 8);
         }
     }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------ sparse RLE, block form

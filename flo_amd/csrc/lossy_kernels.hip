@@ -31,22 +31,25 @@
 #include "lossy_kernels.hpp"
 #include "../../include/flo_synth.h"
 
-// Diagnostic builds only (never shipped): FLO_ABLATE=n cuts the chain kernel's frame body short so that phase costs can
-// be read from timing differences; intermediate values are kept alive so nothing upstream is optimised away.
-//   0 full | 1 no flush/barriers | 2 no emit | 3 no sparse plan | 4 no quantise | 5 no band stats/psy | 6 loads+fold only
-#ifndef FLO_ABLATE
-#define FLO_ABLATE 0
-#endif
-// FLO_ABLATE3=n (three-wave form): 1 packer does nothing | 2 + channel waves stop after the transform |
-//   3 + no post-rotation/transposition | 4 + no FFT (loads and fold only)
+// ---------------------------------------------------------------------------------------------- diagnostic builds
+// Never shipped; diag/build_variant.sh builds a library with any of them. All of them address lossy_chain2q_kernel only.
+//   FLO_STAMPS      s_memtime at the phase boundaries of both roles' frame loops, summed per wave and clip into
+//                   A.dbg_stamps [clip][transform, packer][16] (batch.cpp reports them; FLO_STAMPS_DUMP=file keeps the
+//                   records for diag/stamps_clips.py and diag/tail_spread.py). The stamps pin the schedule.
+//   FLO_MARKS       "; MARK <section>" comments in the transform wave's assembly listing (profiles/phase_table.py counts
+//                   the instructions between them). They pin the schedule too.
+//   FLO_SKIP=bits   leaves phases out to see what each costs. THE RESULTS ARE INVALID: timing and counters only.
+//                     1  band statistics            16  masking pass (level, temporal masking, scale factors)
+//                     2  (unused)                   32  sparse packers (item and block form)
+//                     4  post-rotation + transpose  64  quantiser
+//                     8  FFT                       128  the next frame's fold
+//                   What a skipped phase would have produced is replaced by something cheap that keeps its inputs alive
+//                   (FLO_KEEP), so nothing upstream is optimised away.
+//   FLO_TAIL_STATS  host only (batch.cpp): how many clips' CRCs the launch's idle tail computed.
 #ifndef FLO_SKIP
 #define FLO_SKIP 0
 #endif
-#ifndef FLO_ABLATE3
-#define FLO_ABLATE3 0
-#endif
 #define FLO_KEEP(x) asm volatile("" ::"v"(x))
-// FLO_STAMPS (diagnostic builds only): s_memtime at phase boundaries of the chain kernel, summed per wave.
 #ifdef FLO_STAMPS
 #define STAMP(i)                                                                                  \
     do {                                                                                          \
@@ -57,8 +60,32 @@
         st_sum[i] += t_ - st_last;                                                                \
         st_last = t_;                                                                             \
     } while (0)
+// a clip's sums start at zero, its clock now
+#define STAMPS_BEGIN()                                                                            \
+    unsigned long long st_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last;  \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory")
+// The clip's record of one role (0 transform wave, 1 packer). [13]: where the wave ran (HW_ID, XCC_ID, clip slot, wave of
+// the workgroup): diag/stamps_clips.py groups the records by it. [14]: when the role was through with the clip (100 MHz):
+// its last frame left the transform wave / its bytes were out.
+#define STAMPS_RECORD(role)                                                                                               \
+    do {                                                                                                                  \
+        if (A.dbg_stamps && lane == 0) {                                                                                  \
+            st_sum[13] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) |                     \
+                         ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11)) << 32) |             \
+                         ((unsigned long long)cl << 40) | ((unsigned long long)wv << 48);                                 \
+            for (int i = 0; i < 14; i++) A.dbg_stamps[((unsigned long long)clip * 2 + (role)) * 16 + i] = st_sum[i];      \
+            A.dbg_stamps[((unsigned long long)clip * 2 + (role)) * 16 + 14] = __builtin_amdgcn_s_memrealtime();           \
+        }                                                                                                                 \
+    } while (0)
 #else
 #define STAMP(i) do {} while (0)
+#define STAMPS_BEGIN() do {} while (0)
+#define STAMPS_RECORD(role) do {} while (0)
+#endif
+#ifdef FLO_MARKS
+#define FLO_MARK(x) asm volatile("; MARK " x ::: "memory")
+#else
+#define FLO_MARK(x)
 #endif
 
 namespace flo {
@@ -88,29 +115,13 @@ struct FrameState {
 
 // Everything between the MDCT and the byte stream for CH channels held by this wave: band statistics, masking
 // level, temporal masking, scale factors, quantiser, sparse-RLE plan. ch0 = index of c[0] among the clip's channels.
-#ifdef FLO_STAMPS
-#define ASTAMP(i)                                                                                 \
-    do {                                                                                          \
-        if (stamps) {                                                                             \
-            __builtin_amdgcn_sched_barrier(0);                                                    \
-            unsigned long long t_;                                                                \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");          \
-            __builtin_amdgcn_sched_barrier(0);                                                    \
-            stamps[i] += t_ - stamps[15];                                                         \
-            stamps[15] = t_;                                                                      \
-        }                                                                                         \
-    } while (0)
-#else
-#define ASTAMP(i) do {} while (0)
-#endif
 template <int CH, bool BANDS_ONLY, bool EXACT, bool PLAN = true>
 __device__ __forceinline__ void analyse_frame(const int lane, float (&c)[CH][16], WaveLds<CH> &lds, const LaneConst &L,
                                               const LossyArgs &A, const LossyDevTables &T, int ch0, FrameState<CH> &st,
                                               unsigned long long gframe, int (&q)[CH][16], uint32_t (&sfw)[CH],
-                                              SparsePlan (&P)[CH], unsigned long long *stamps = nullptr) {
+                                              SparsePlan (&P)[CH]) {
     float energy[CH], bmax[CH];
     band_stats<CH>(lane, c, lds.slots, T, energy, bmax);
-    ASTAMP(10);
 #pragma unroll
     for (int ch = 0; ch < CH; ch++) {
         float a = spread_threshold(lane, energy[ch], L.rcount, T);
@@ -132,17 +143,7 @@ __device__ __forceinline__ void analyse_frame(const int lane, float (&c)[CH][16]
     }
     if (BANDS_ONLY) return;
     wave_sync();
-    ASTAMP(11);
-#if FLO_ABLATE >= 4
-    for (int ch = 0; ch < CH; ch++) { FLO_KEEP(sfw[ch]); for (int e = 0; e < 16; e++) q[ch][e] = 0; P[ch].total = 3; P[ch].off0 = 0; P[ch].M = 0; }
-    return;
-#endif
     quantise<CH, EXACT>(lane, c, lds, L, T, q);
-    ASTAMP(12);
-#if FLO_ABLATE >= 3
-    for (int ch = 0; ch < CH; ch++) { P[ch].total = 3; P[ch].off0 = 0; P[ch].M = 0; }
-    return;
-#endif
     if (A.dbg_q) {
 #pragma unroll
         for (int ch = 0; ch < CH; ch++) {
@@ -275,11 +276,9 @@ __device__ __forceinline__ void pair_sync(uint32_t *cnt, int w, uint32_t step) {
     } while (true);
 }
 
-#ifndef FLO_CHAIN_WAVES_PER_SIMD
-#define FLO_CHAIN_WAVES_PER_SIMD 3
-#endif
+constexpr int kChainWavesPerSimd = 3;
 template <int NW, bool EXACT>
-__global__ __launch_bounds__(768, FLO_CHAIN_WAVES_PER_SIMD) void lossy_chain_kernel(LossyArgs A, int clips_per_wg) {
+__global__ __launch_bounds__(768, kChainWavesPerSimd) void lossy_chain_kernel(LossyArgs A, int clips_per_wg) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63;
@@ -325,10 +324,6 @@ __global__ __launch_bounds__(768, FLO_CHAIN_WAVES_PER_SIMD) void lossy_chain_ker
     }
     unsigned long long written = 0;
     uint32_t pend = 0, step = 0, tailb = 0;
-#ifdef FLO_STAMPS
-    unsigned long long st_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
-#endif
     // One frame. (pe, po) hold the frame's first half, (ce, co) its second half = the next frame's first half.
     auto frame_body = [&](const unsigned h, float (&pe)[1][8], float (&po)[1][8], float (&ce)[1][8],
                           float (&co)[1][8]) __attribute__((always_inline)) {
@@ -344,52 +339,27 @@ __global__ __launch_bounds__(768, FLO_CHAIN_WAVES_PER_SIMD) void lossy_chain_ker
         } else {
             float zr[1][8], zi[1][8];
             fold<1>(ln, pe, po, ce, co, zr, zi, T);
-            STAMP(0);
             // the older half is dead after the fold: the half-frame after next is loaded into its registers now and
             // consumed at the top of the next call, where the two register sets have swapped roles
             // unconditional, also behind the last frame (the batch allocates one spare half-frame per clip): a
             // conditional load would merge "loaded" and "kept" registers and cost 16 copies per frame
             load_half_fast<1>(ln, pcm, NW, w, (long long)(h + 1) * 1024, pe, po);
-#if FLO_ABLATE >= 6
-            for (int r = 0; r < 8; r++) { FLO_KEEP(zr[0][r]); FLO_KEEP(zi[0][r]); }
-            return;
-#endif
-            STAMP(1);
             fft512<1>(ln, zr, zi, lds.u.xch, T);
-            STAMP(2);
             post_rotate_transpose<1>(ln, zr, zi, lds.u.coef, c, T);
-            STAMP(3);
             store_coeffs_dbg<1>(ln, c, A, frame0 + h, w);
         }
-#if FLO_ABLATE >= 5
-        for (int e = 0; e < 16; e++) FLO_KEEP(c[0][e]);
-        return;
-#endif
         int q[1][16];
         uint32_t sfw[1];
         SparsePlan P[1];
         {
             LaneConst L;
             load_lane_const(ln, L, T);
-#ifdef FLO_STAMPS
-            st_sum[15] = st_last;
-            analyse_frame<1, false, EXACT>(ln, c, lds, L, A, T, w, st, frame0 + h, q, sfw, P, st_sum);
-            st_last = st_sum[15];
-#else
             analyse_frame<1, false, EXACT>(ln, c, lds, L, A, T, w, st, frame0 + h, q, sfw, P);
-#endif
         }
-        STAMP(4);
-#if FLO_ABLATE >= 2
-        FLO_KEEP(P[0].total); FLO_KEEP(P[0].off0); FLO_KEEP(P[0].M); FLO_KEEP(sfw[0]);
-        for (int e = 0; e < 16; e++) FLO_KEEP(q[0][e]);
-        return;
-#endif
         uint32_t tot[2];
         if (NW > 1) {
             if (ln == 0) cs.tot[w] = P[0].total;
             pair_sync(cs.cnt, w, ++step);   // both plans are known; the previous frame's flush has been read out
-            STAMP(5);
             tot[0] = cs.tot[0];
             tot[1] = cs.tot[1];
         } else {
@@ -400,13 +370,7 @@ __global__ __launch_bounds__(768, FLO_CHAIN_WAVES_PER_SIMD) void lossy_chain_ker
         // the < 16 bytes the previous frame left unflushed go back to the front of the staging buffer
         if (ptid < (int)pend) stage[ptid] = (uint8_t)tailb;
         const uint32_t flen = emit_frame<1>(ln, stage + pend, NW, w, tot, sfw, P, q);
-        STAMP(6);
-#if FLO_ABLATE >= 1
-        FLO_KEEP(flen);
-        return;
-#endif
         if (NW > 1) pair_sync(cs.cnt, w, ++step); else wave_sync();
-        STAMP(7);
         if (ptid == 0) A.frame_size[frame0 + h] = flen;
         // flush complete 16-byte chunks; the rest is carried in a register until the next frame's rendezvous
         const uint32_t have = pend + flen;
@@ -417,7 +381,6 @@ __global__ __launch_bounds__(768, FLO_CHAIN_WAVES_PER_SIMD) void lossy_chain_ker
         pend = have & 15u;
         tailb = (ptid < (int)pend) ? stage[(n16 << 4) + ptid] : 0u;
         written += (unsigned long long)n16 << 4;
-        STAMP(8);
     };
     // two frames per trip so that the two half-frame register sets alternate roles without copies
     for (unsigned h = 0; h < hops; h += 2) {
@@ -426,31 +389,27 @@ __global__ __launch_bounds__(768, FLO_CHAIN_WAVES_PER_SIMD) void lossy_chain_ker
     }
     if (ptid < (int)pend) gout[written + ptid] = (uint8_t)tailb;
     if (ptid == 0) A.clip_bytes[clip] = written + pend;
-#ifdef FLO_STAMPS
-    if (A.dbg_stamps && lane == 0)
-        for (int i = 0; i < 14; i++) A.dbg_stamps[((unsigned long long)clip * NW + w) * 16 + i] = st_sum[i];
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------- counters between the waves of a clip
+constexpr int kCounterSleep = 1;   // s_sleep argument between two looks at a counter (64 clocks each)
 // wait until the LDS counter at `p` reaches `want` (written by another wave of this workgroup)
-template <int SLEEP = 1>
 __device__ __forceinline__ void wait_counter(const uint32_t *p, uint32_t want) {
     const uint32_t a = (uint32_t)(uintptr_t)p;
     uint32_t seen;
     do {
         asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(seen) : "v"(a) : "memory");
         if (seen >= want) break;
-        __builtin_amdgcn_s_sleep(SLEEP);
+        __builtin_amdgcn_s_sleep(kCounterSleep);
     } while (true);
 }
-// publish: every LDS access this wave issued before is performed first (a wave's LDS instructions execute in order)
 // The counter's value now, through a ds_read the compiler tracks (it waits where the value is first used): issued well
 // ahead of the hand-over, it turns the usual case - the partner is already there - into no wait at all.
 __device__ __forceinline__ uint32_t peek_counter(const uint32_t *p) {
     typedef volatile __attribute__((address_space(3))) uint32_t lds_vu32;
     return *reinterpret_cast<lds_vu32 *>((uintptr_t)(uint32_t)(uintptr_t)p);
 }
+// publish: every LDS access this wave issued before is performed first (a wave's LDS instructions execute in order)
 __device__ __forceinline__ void set_counter(uint32_t *p, uint32_t v) {
     const uint32_t a = (uint32_t)(uintptr_t)p;
     asm volatile("ds_write_b32 %0, %1" ::"v"(a), "v"(v) : "memory");
@@ -460,11 +419,6 @@ __device__ __forceinline__ void set_counter(uint32_t *p, uint32_t v) {
 #define FLO_C2X_THREADS 768
 #endif
 // DIRTY (template parameter of the lock-step chain kernel): see kDirty44k in encode_plan.hpp
-#ifdef FLO_MARKS   // diagnostic builds: section markers in the assembly listing (they pin the schedule: never shipped)
-#define FLO_MARK(x) asm volatile("; MARK " x ::: "memory")
-#else
-#define FLO_MARK(x)
-#endif
 
 // ---------------------------------------------------------------------------------------------- two waves per clip
 // Stereo clips. One TRANSFORM wave per clip carries both channels in lock-step: every constant row (window, twiddles, band
@@ -507,9 +461,6 @@ struct Clip2qLds {
 static_assert(sizeof(Clip2qLds) % 16 == 0, "clip LDS block keeps 16-byte alignment");
 constexpr int kPackBytesHotT = kPackRowsHotT * 64 * 16;
 
-#ifndef FLO_PSLEEP
-#define FLO_PSLEEP 1
-#endif
 static_assert(sizeof(Clip2qLds::u) >= 8 * 256 * sizeof(uint32_t), "the tail's CRC tables fit the exchange buffer");
 
 // ---------------------------------------------------------------------------------------------- CRC in the idle tail
@@ -582,6 +533,11 @@ __device__ __forceinline__ void tail_crc(const LossyArgs &A, uint32_t *tabs, con
     }
 }
 
+// The packer's priority: its clip slot waits for this wave (the transform wave has a third of a frame to spare), so it goes
+// first on its SIMD.
+constexpr int kPackerPrio = 1;
+// What a launch of one round passes as chain2q_pturns (0: no turns): packers that share a SIMD go first in turn.
+constexpr unsigned kPackerTurns = 1;
 template <bool COEFFS, uint32_t DIRTY, bool DBG>
 __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArgs A, int clips_per_wg) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
@@ -615,11 +571,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
     uint32_t fbase = 0, seq = 0;
     if (role.packer) {
         // ------------------------------------------------------------------ packer: quantise, serialise, flush
-        // its clip slot waits for this wave (the transform wave has a third of a frame to spare): it goes first on its SIMD
-#ifndef FLO_PRIO_P
-#define FLO_PRIO_P 1
-#endif
-        __builtin_amdgcn_s_setprio(FLO_PRIO_P);
+        __builtin_amdgcn_s_setprio(kPackerPrio);
         // Two packers on one SIMD have the same priority and the older one wins issue: its slot runs ahead, the other's
         // is the launch's last. Where the launcher asks (launches of one round, whose length is their slowest slot's),
         // such packers go first in turn, by the parity of the clip's frame. 0: no turns, 1 / 2: first on odd / even frames
@@ -666,16 +618,13 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             uint8_t *gout = A.out + A.out_off[clip];
             unsigned long long written = 0;
             uint32_t pend = 0, tailb = 0;
-#ifdef FLO_STAMPS
-            unsigned long long st_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
-#endif
+            STAMPS_BEGIN();
             for (unsigned h = 0; h < hops; h++) {
                 const int ln = lane_id_opaque();
                 const uint32_t g = fbase + h;
                 if (pturn) {   // uniform
-                    if ((h + pturn) & 1u) __builtin_amdgcn_s_setprio(FLO_PRIO_P);
-                    else __builtin_amdgcn_s_setprio(FLO_PRIO_P + 1);
+                    if ((h + pturn) & 1u) __builtin_amdgcn_s_setprio(kPackerPrio);
+                    else __builtin_amdgcn_s_setprio(kPackerPrio + 1);
                 }
                 // The next frame's coefficients are taken as soon as the transform wave has them and this wave's registers
                 // are free (behind the quantiser, between the channels' blobs, in front of the flush): the sooner the
@@ -698,7 +647,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
                     for (int q = 0; q < 8; q++) blk[q] = bp[q];
                 }
                 if (!have) {
-                    wait_counter<FLO_PSLEEP>(&cs.coef_ready, g + 1);
+                    wait_counter(&cs.coef_ready, g + 1);
 #pragma unroll
                     for (int k = 0; k < 8; k++) cf[k] = *reinterpret_cast<const lds_v4f *>((uintptr_t)(cf_a + 1152u * (uint32_t)k));
                     set_counter(&cs.consumed, g + 1);   // (behind the reads: a wave's LDS instructions execute in order)
@@ -707,7 +656,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
 #ifdef FLO_STAMPS
                 const unsigned long long st_frame0 = st_last;
 #endif
-                wait_counter<FLO_PSLEEP>(&cs.ts_ready, g + 1);
+                wait_counter(&cs.ts_ready, g + 1);
                 STAMP(5);
                 const uint32_t par = g & 1u;
                 const uint32_t sfw_both = cs.sfwh[par][ln >> 5][ln & 31];   // scale words: lanes 0..24 left, 32..56 right
@@ -827,34 +776,18 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             if (lane == 0) A.clip_bytes[clip] = written + pend;
             done_clip = clip;
             done_bytes = written + pend;
-#ifdef FLO_STAMPS
-            if (A.dbg_stamps && lane == 0) {
-                st_sum[13] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) |
-                             ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11)) << 32) | ((unsigned long long)cl << 40) | ((unsigned long long)wv << 48);
-                for (int i = 0; i < 14; i++) A.dbg_stamps[((unsigned long long)clip * 2 + 1) * 16 + i] = st_sum[i];
-                A.dbg_stamps[((unsigned long long)clip * 2 + 1) * 16 + 14] = __builtin_amdgcn_s_memrealtime();   // when the clip's bytes were out
-            }
-#endif
+            STAMPS_RECORD(1);
             fbase += hops;
         }
     }
 
     // ---------------------------------------------------------------------- transform wave: both channels
-#ifdef FLO_PRIO_T
-    __builtin_amdgcn_s_setprio(FLO_PRIO_T);
-#endif
     LossyDevTables T = A.T;
     T.pack = reinterpret_cast<const float4 *>(lds_raw);
-#ifndef FLO_SO_LDS
     // the slot area belongs to band statistics alone in this form: its zero slot is written once and the lane's twelve
     // gather addresses stay in registers (the wave has them to spare now that the quantiser lives in the packer)
     uint32_t so_pre[12];
     band_stats_2_prepare(lane, cs.slot, A.T.pack, so_pre);
-    constexpr bool kSoPre = true;
-#else
-    const uint32_t *so_pre = nullptr;
-    constexpr bool kSoPre = false;
-#endif
     for (;;) {
         wait_counter(&cs.clip_seq, ++seq);
         const unsigned clip = (unsigned)__builtin_amdgcn_readfirstlane((int)cs.clip_cur);
@@ -868,10 +801,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
 #pragma unroll
         for (int r = 0; r < 8; r++) ae[r] = ao[r] = splat2(0.f);  // pre-roll: 1024 zeros (encoder.rs:177)
         if (!COEFFS) load_half_fast_2(lane_id_opaque(), pcm, 0, be, bo);   // (opaque: keeps 16 address pairs out of loop-invariant registers)
-#ifdef FLO_STAMPS
-        unsigned long long st_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
-#endif
+        STAMPS_BEGIN();
         // The frame loop is software-pipelined by two phases. (1) The fold of frame h + 1, which only needs PCM that is already
         // in registers, runs at the end of frame h: entering frame h, (zr, zi) hold its folded input, and the half-frame
         // after next is loaded at the TOP of the frame into the registers the last fold freed. (2) The masking pass of
@@ -950,7 +880,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
                 STAMP(1);
                 if ((uint32_t)__builtin_amdgcn_readfirstlane((int)consumed_early) < g) wait_counter(&cs.consumed, g);
                 STAMP(7);
-#if (FLO_SKIP & 8) == 0   // FLO_SKIP (diagnostic builds, results invalid): leave a phase out to see what it costs
+#if (FLO_SKIP & 8) == 0
                 fft512_2(ln, zr, zi, cs.u.xch4, T, [&]() __attribute__((always_inline)) {
                     if (h > 0) mask_publish(ln, g - 1u, h - 1u, pend_e, pend_m, rcount, sd0, sd1);   // uniform
                 });
@@ -980,7 +910,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             // band statistics (both channels): channel 0's band b on lane b, channel 1's on lane 32 + b
             float energy1, bmax1;
 #if (FLO_SKIP & 1) == 0
-            band_stats_2<DIRTY, kSoPre>(ln, c, cs.slot, T, energy1, bmax1, so_pre);
+            band_stats_2<DIRTY, true>(ln, c, cs.slot, T, energy1, bmax1, so_pre);
 #else
             energy1 = c[0].x + c[5].y;
             bmax1 = c[1].x + c[7].y;
@@ -1011,14 +941,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             const float4 sd0 = T.pack[kRowS10 * 64], sd1 = T.pack[kRowS10 * 64 + 1];
             mask_publish(ln, fbase + hops - 1u, hops - 1u, pend_e, pend_m, reinterpret_cast<const float *>(T.pack + kRowS10 * 64)[64 + ln], sd0, sd1);
         }
-#ifdef FLO_STAMPS
-        if (A.dbg_stamps && lane == 0) {   // [13]: where the wave ran (HW_ID, XCC_ID, clip slot, wave of the workgroup): diag/stamps_clips.py groups the records by it
-            st_sum[13] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) |
-                         ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11)) << 32) | ((unsigned long long)cl << 40) | ((unsigned long long)wv << 48);
-            for (int i = 0; i < 14; i++) A.dbg_stamps[((unsigned long long)clip * 2) * 16 + i] = st_sum[i];
-            A.dbg_stamps[((unsigned long long)clip * 2) * 16 + 14] = __builtin_amdgcn_s_memrealtime();   // when the clip's last frame left the transform wave (100 MHz)
-        }
-#endif
+        STAMPS_RECORD(0);
         fbase += hops;
     }
 }
@@ -1959,11 +1882,8 @@ static int launch_chain2q_t(const LossyArgs &A, int clips, hipStream_t s) {
     // One round (no slot takes a second clip): the launch ends with its slowest slot and nothing is dealt that could
     // even the slots out, so packers that share a SIMD take turns at going first (kernel: pturn). With more rounds the
     // dealing evens the slots out.
-#ifndef FLO_C2Q_PTURNS
-#define FLO_C2Q_PTURNS 1
-#endif
     LossyArgs B = A;
-    B.chain2q_pturns = (unsigned long long)wgs * (unsigned)g >= (unsigned long long)A.n_clips ? FLO_C2Q_PTURNS : 0u;
+    B.chain2q_pturns = (unsigned long long)wgs * (unsigned)g >= (unsigned long long)A.n_clips ? kPackerTurns : 0u;
     hipLaunchKernelGGL((lossy_chain2q_kernel<COEFFS, DIRTY, DBG>), dim3(wgs), dim3(128 * g), lds, s, B, g);
     FLO_LAUNCH_CHECK();
     return 0;
