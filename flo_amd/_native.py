@@ -44,6 +44,7 @@ EXPORTS = [
     "flo_batch_size_curve", "flo_batch_set_quality", "flo_rate_pick", "flo_encode_batch_to_size",
     "flo_batch_encode_ladder", "flo_ladder_shape", "flo_ladder_file_bytes", "flo_ladder_fetch", "flo_ladder_device_files",
     "flo_ladder_destroy", "flo_encode_batch_ladder",
+    "flo_resample_filter", "flo_resample_out_frames", "flo_batch_resample", "flo_resample",
 ]
 
 
@@ -94,6 +95,10 @@ class Fidelity(C.Structure):   # flo_fidelity: one channel of one clip
                 ("seg_snr_db", C.c_double), ("peak_error", C.c_float), ("peak_out", C.c_float), ("clipped", C.c_uint64),
                 ("compared_frames", C.c_uint64), ("source_frames", C.c_uint64), ("decoded_frames", C.c_uint64),
                 ("n_blocks", C.c_uint32), ("seg_blocks", C.c_uint32)]
+
+
+class ResampleInfo(C.Structure):   # flo_resample_info
+    _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("taps", C.c_uint32), ("tile_outputs", C.c_uint32)]
 
 
 class FloError(RuntimeError):
@@ -255,5 +260,9 @@ def lib():
     L.flo_ladder_destroy.restype = None
     L.flo_encode_batch_ladder.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.c_uint32, C.c_uint8, sz, vp, C.POINTER(vp),
                                           C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
+    L.flo_resample_filter.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(ResampleInfo), C.POINTER(vp), C.c_char_p, sz]
+    L.flo_resample_out_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.flo_batch_resample.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.flo_resample.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint8, C.POINTER(vp), C.POINTER(sz)]
     _LIB = L
     return L

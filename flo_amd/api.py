@@ -143,6 +143,15 @@ class Context:
         """compute units the persistent encode kernels currently leave free"""
         return int(self._L.flo_ctx_reserved_cus(self._h))
 
+    def resample(self, samples, in_rate, out_rate, channels):
+        """flo_resample: the interleaved f32 clip at out_rate (one upload, the batch kernel, one fetch)"""
+        p = _f32(samples)
+        out, n = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.flo_resample(self._h, p.ctypes.data, p.size, in_rate, out_rate, channels, C.byref(out), C.byref(n)))
+        res = np.frombuffer(C.string_at(out.value, n.value * 4), np.float32).copy() if n.value else np.zeros(0, np.float32)
+        self._L.flo_free(out)
+        return res
+
     def upload_path(self):
         """(path large host uploads take on this host, GB/s the probe measured for pageable-direct, for the pinned ring)"""
         name, a, b = C.create_string_buffer(64), C.c_double(), C.c_double()
@@ -367,16 +376,30 @@ class Context:
 class Batch:
     """Device-resident batch of clips (flo_batch): PCM stays in HBM, bitstreams are left in HBM."""
 
-    def __init__(self, ctx: Context, mode, n_interleaved, sample_rate, channels, quality_or_level):
+    def __init__(self, ctx: Context, mode, n_interleaved, sample_rate, channels, quality_or_level, _handle=None):
         self.ctx, self._L = ctx, ctx._L
         self.channels = int(channels)
+        self.sample_rate = int(sample_rate)
         self.n_clips = len(n_interleaved)
         self.n_interleaved = list(int(x) for x in n_interleaved)
-        lens = (C.c_size_t * self.n_clips)(*self.n_interleaved)
+        self._made = (mode, quality_or_level)
         h = C.c_void_p()
-        ctx._chk(self._L.flo_batch_create(ctx._h, mode, self.n_clips, lens, sample_rate, channels, quality_or_level, C.byref(h)))
+        if _handle is None:
+            lens = (C.c_size_t * self.n_clips)(*self.n_interleaved)
+            ctx._chk(self._L.flo_batch_create(ctx._h, mode, self.n_clips, lens, sample_rate, channels, quality_or_level, C.byref(h)))
+        else:
+            h = _handle   # (made by the library: Batch.resample)
         self._h = h
         ctx._batches.add(self)
+
+    def resample(self, out_rate) -> "Batch":
+        """flo_batch_resample: a new batch of the same mode, channels, quality / level and bit depth at out_rate, every clip
+        converted on the device in one launch (enqueued; sync() of either batch orders it). Whole sample-frames are
+        converted; this batch stays valid and unchanged"""
+        h = C.c_void_p()
+        self.ctx._chk(self._L.flo_batch_resample(self._h, out_rate, C.byref(h)))
+        lens = [resample_out_frames(self.sample_rate, out_rate, n // self.channels) * self.channels for n in self.n_interleaved]
+        return Batch(self.ctx, self._made[0], lens, out_rate, self.channels, self._made[1], _handle=h)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1160,6 +1183,49 @@ def decode_streams(decoders, max_frames: int = 0, out=None, ctx: Context = None)
     st = st[:n].copy()
     errors = [decoders[i]._err() if st[i] else "" for i in range(n)]
     return StreamsResult(out[:int(offs[-1])], offs, st, errors)
+
+
+def resample_out_frames(in_rate, out_rate, in_frames) -> int:
+    """flo_resample_out_frames: ceil(in_frames * L / M), the sample-frames a clip of in_frames has after conversion"""
+    n = C.c_uint64()
+    if _native.lib().flo_resample_out_frames(in_rate, out_rate, in_frames, C.byref(n)) != 0:
+        raise FloError(f"unsupported sample-rate conversion {in_rate} -> {out_rate}")
+    return int(n.value)
+
+
+def resample_filter(in_rate, out_rate):
+    """flo_resample_filter: (info, table): info a dict with L, M, taps and tile_outputs, table the f32 array [L, taps] of
+    the conversion's polyphase filter. Host only: needs no device"""
+    L = _native.lib()
+    info, tab, err = _native.ResampleInfo(), C.c_void_p(), C.create_string_buffer(256)
+    if L.flo_resample_filter(in_rate, out_rate, C.byref(info), C.byref(tab), err, 256) != 0:
+        raise FloError(err.value.decode())
+    n = info.L * info.taps
+    table = np.frombuffer(C.string_at(tab.value, n * 4), np.float32).reshape(info.L, info.taps).copy()
+    L.flo_free(tab)
+    return dict(L=info.L, M=info.M, taps=info.taps, tile_outputs=info.tile_outputs), table
+
+
+def resample(samples, in_rate, out_rate, channels) -> np.ndarray:
+    """the interleaved f32 clip converted to out_rate on the device (Context.resample on the default context)"""
+    return default_context().resample(samples, in_rate, out_rate, channels)
+
+
+def resample_many(clips, in_rate, out_rate, channels, ctx: Context = None):
+    """every clip converted to out_rate: one batch, one launch; a list of f32 arrays (whole sample-frames are converted)"""
+    c = ctx or default_context()
+    ps = [_f32(x) for x in clips]
+    b = Batch(c, MODE_LOSSLESS, [p.size for p in ps], in_rate, channels, 0)
+    try:
+        for i, p in enumerate(ps):
+            c._chk(c._L.flo_batch_upload(b._h, i, p.ctypes.data))
+        r = b.resample(out_rate)
+        try:
+            return [r.download_pcm(i) for i in range(r.n_clips)]
+        finally:
+            r.close()
+    finally:
+        b.close()
 
 
 def _encode_analysed(mode, samples, sample_rate, channels, quality_or_level, bit_depth, metadata) -> bytes:

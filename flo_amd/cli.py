@@ -3,7 +3,8 @@
 Mirrors the reference CLI (reflo/src/main.rs:19-93, 218-420): the same sub-commands, options, quality names and
 printed fields for the parts that sit on this repository's path -
     encode  <in.wav> <out.flo> [--level N] [--lossy | --transform] [--quality low|medium|high|veryhigh|transparent]
-                               [--bitrate KBPS] [--target-kbps KBPS]
+                               [--bitrate KBPS] [--target-kbps KBPS] [--rate HZ]
+    resample <in.wav> <out.wav> --rate HZ
     curve   <in.wav> [--json]
     ladder  <in.wav> <outdir> --qualities Q0,Q1,... [--json]
     decode  <in.flo> <out.wav>
@@ -30,6 +31,8 @@ of a grid comes from one device pass over the audio (flo_batch_size_curve), and 
 file, META included, stays within N kbps over the clip's duration.
 `ladder` (not in reflo) writes the file at every quality of a list, <outdir>/<stem>.r<j>.flo for rung j, from one upload and
 one transform pass on the device (flo_batch_encode_ladder): each file is what `encode --lossy --quality Qj` writes.
+`resample` and `encode --rate N` (not in reflo) convert the audio to N Hz on the device first (flo_resample: a polyphase
+Kaiser-windowed sinc, include/flo_hip.h); the encode then analyses and encodes the converted audio, and header and META carry N.
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
 """
@@ -61,11 +64,25 @@ def _wav_source_format(audio_bytes: bytes) -> str:
     return "UNKNOWN"
 
 
-def encode_from_audio(audio_bytes: bytes, level=5, lossy=False, quality=0.6, bitrate=None, ctx=None, title=None, artist=None,
-                      album=None, encoding_time=None) -> bytes:
-    """reflo::encode_from_audio (reflo/src/lib.rs:183-306) for WAV input."""
+def _read_at_rate(audio_bytes: bytes, rate, ctx=None):
+    """the WAV's samples, converted to `rate` Hz on the device when one is given and differs"""
     samples, sr, ch = read_wav_bytes(audio_bytes)
+    if rate is not None and int(rate) != sr:
+        samples, sr = (ctx or api.default_context()).resample(samples, sr, int(rate), ch), int(rate)
+    return samples, sr, ch
+
+
+def resample_wav(audio_bytes: bytes, rate, ctx=None) -> bytes:
+    """the WAV at `rate` Hz, as the 32-bit float WAV `decode` writes"""
+    samples, sr, ch = _read_at_rate(audio_bytes, rate, ctx)
+    return write_wav_bytes(samples, sr, ch)
+
+
+def encode_from_audio(audio_bytes: bytes, level=5, lossy=False, quality=0.6, bitrate=None, ctx=None, title=None, artist=None,
+                      album=None, encoding_time=None, rate=None) -> bytes:
+    """reflo::encode_from_audio (reflo/src/lib.rs:183-306) for WAV input; rate: convert to that sample rate first."""
     c = ctx or api.default_context()
+    samples, sr, ch = _read_at_rate(audio_bytes, rate, c)
     level = min(int(level), 9)
     is_lossy = bool(lossy or bitrate is not None)
     quality = min(max(float(quality), 0.0), 1.0)
@@ -77,9 +94,9 @@ def encode_from_audio(audio_bytes: bytes, level=5, lossy=False, quality=0.6, bit
     return api.Encoder(sr, ch, 16, c).with_compression(level).encode(samples, mb)
 
 
-def encode_to_target(audio_bytes: bytes, target_kbps, title=None, artist=None, album=None, encoding_time=None):
+def encode_to_target(audio_bytes: bytes, target_kbps, title=None, artist=None, album=None, encoding_time=None, rate=None):
     """(file, info): the WAV encoded at the best quality of api.DEFAULT_RATE_GRID whose whole file fits target_kbps"""
-    samples, sr, ch = read_wav_bytes(audio_bytes)
+    samples, sr, ch = _read_at_rate(audio_bytes, rate)
     shown = int(target_kbps) if float(target_kbps).is_integer() else target_kbps
     mb = meta.cli_metadata(samples.size, sr, ch, _wav_source_format(audio_bytes), True, 0.0, shown, 5, title, artist, album,
                            encoding_time)
@@ -250,9 +267,14 @@ def main(argv=None) -> int:
     e.add_argument("--quality", default="high", help="Lossy quality level (low, medium, high, veryhigh, transparent)")
     e.add_argument("--bitrate", type=int, default=None, help="Target bitrate in kbps (alternative to quality)")
     e.add_argument("--target-kbps", type=float, default=None, help="Lossy: the best measured quality whose file stays within this bitrate")
+    e.add_argument("--rate", type=int, default=None, help="Convert to this sample rate (Hz) on the device before encoding")
     e.add_argument("--title", default=None, help="Title metadata")
     e.add_argument("--artist", default=None, help="Artist metadata")
     e.add_argument("--album", default=None, help="Album metadata")
+    rs = sub.add_parser("resample", help="Convert a WAV file to another sample rate on the device")
+    rs.add_argument("input")
+    rs.add_argument("output")
+    rs.add_argument("--rate", type=int, required=True, help="Output sample rate in Hz")
     d = sub.add_parser("decode", help="Decode a flo file to WAV")
     d.add_argument("input")
     d.add_argument("output")
@@ -299,10 +321,13 @@ def main(argv=None) -> int:
             print(f"  Sample rate: {sr} Hz")
             print(f"  Channels: {ch}")
             print(f"  Duration: {samples.size / ch / sr:.2f}s")
+            if a.rate is not None and a.rate != sr:
+                print(f"Converting to {a.rate} Hz...")
+                samples, sr, ch = _read_at_rate(audio, a.rate)
             lossy = a.lossy or a.transform
             if a.target_kbps is not None:
                 print(f"Encoding to flo (lossy, at most {a.target_kbps:g} kbps, measured)...")
-                flo, info = encode_to_target(audio, a.target_kbps, a.title, a.artist, a.album)
+                flo, info = encode_to_target(audio, a.target_kbps, a.title, a.artist, a.album, rate=a.rate)
                 secs = samples.size / ch / sr
                 print(f"  Quality: {info['quality']:.4f} (candidate {info['index']}){'' if info['fits'] else ' - the target is below the smallest file'}")
                 print(f"  Achieved: {(len(flo) * 8 / 1000 / secs) if secs else 0.0:.1f} kbps ({len(flo)} of {info['target_bytes']} bytes)")
@@ -316,15 +341,27 @@ def main(argv=None) -> int:
                         return 1
                     q = QUALITY[a.quality.lower()]
                     print(f"Encoding to flo (lossy, {a.quality} quality)...")
-                flo = encode_from_audio(audio, a.level, True, q if q is not None else 0.6, a.bitrate, None, a.title, a.artist, a.album)
+                flo = encode_from_audio(audio, a.level, True, q if q is not None else 0.6, a.bitrate, None, a.title, a.artist, a.album, rate=a.rate)
             else:
                 print("Encoding to flo (lossless)...")
-                flo = encode_from_audio(audio, a.level, title=a.title, artist=a.artist, album=a.album)
+                flo = encode_from_audio(audio, a.level, title=a.title, artist=a.artist, album=a.album, rate=a.rate)
             open(a.output, "wb").write(flo)
             original = int(samples.size * 4)
             print("Done!")
             print(f"  Output: {a.output}")
             print(f"  Size: {len(flo)} bytes ({original / max(len(flo), 1):.1f}x compression)")
+        elif a.command == "resample":
+            print(f"Reading {a.input}...")
+            audio = open(a.input, "rb").read()
+            samples, sr, ch = read_wav_bytes(audio)
+            print(f"  Sample rate: {sr} Hz")
+            print(f"  Channels: {ch}")
+            print(f"  Duration: {samples.size / ch / sr:.2f}s")
+            print(f"Converting to {a.rate} Hz...")
+            wav = resample_wav(audio, a.rate)
+            open(a.output, "wb").write(wav)
+            print("Done!")
+            print(f"  Output: {a.output}")
         elif a.command == "decode":
             print(f"Reading {a.input}...")
             flo = open(a.input, "rb").read()

@@ -1,6 +1,6 @@
 // batch_internal.hpp — the device-resident batch (flo_batch_*, include/flo_hip.h) as the library's source files see it:
 // batch.cpp makes, encodes and releases it; decode.cpp, fidelity.cpp, analysis.cpp, dist.cpp, stages.cpp, stream.cpp and
-// rate.cpp read it. Not part of the C ABI.
+// rate.cpp read it; resample.cpp makes one from another. Not part of the C ABI.
 #pragma once
 #include <vector>
 
@@ -62,6 +62,9 @@ struct flo_batch {
     std::vector<uint32_t> h_frame_size;
     // lossless
     LosslessPlan *ll = nullptr;
+    // a batch made by flo_batch_resample (resample.cpp): the filter table and work list of the launch that fills it, device
+    // and pinned, kept until the batch goes (the launch is only enqueued)
+    void *d_resample = nullptr, *pin_resample = nullptr;
     // lossy clips of n_interleaved % ch != 0 uploaded from the host: the trailing partial sample-frame, which the encoder
     // drops (so it stays out of the device copy) but the analysis covers (flo_batch_analyze_all)
     std::vector<std::vector<float>> tail;

@@ -438,6 +438,30 @@ int flo_encode_batch_ladder(flo_ctx *ctx, size_t n_clips, const float *const *pc
                             uint32_t sample_rate, uint8_t channels, size_t n_q, const float *qualities,
                             const uint8_t *const *meta, const size_t *meta_lens, uint8_t **outs, size_t *out_lens);
 
+/* ---- sample-rate conversion: a resident batch at one rate becomes a resident batch at another, on the device ---------------
+ * in_rate -> out_rate with g = gcd: L = out_rate / g phases, M = in_rate / g. Output frame j of a clip sits at input time
+ * j * M / L: with i = floor(j * M / L) and p = (j * M) mod L, y[j] = sum_k h[p][k] * x[i + k - taps/2 + 1] per channel, x zero
+ * outside the clip; n_in frames give ceil(n_in * L / M). h is a Kaiser-windowed sinc (beta 9, 32 zero crossings each side at
+ * the lower of the two rates, cut-off at 0.91 of the lower Nyquist frequency: about 90 dB in the stop band, flat to about
+ * 0.82 of that Nyquist), every row normalised to a sum of 1 in f64, then rounded to f32.
+ * Supported: both rates in 1 .. 384000, L <= 1024, taps <= 2048, L * taps * 4 <= 1 MiB; anything else is FLO_ERR_ARG with a
+ * message that names the offending quantity. Equal rates are not filtered: the result is a copy, bit for bit.
+ * flo_resample_filter: host only, no context: the table [L][taps] (malloc'ed, flo_free; table may be NULL) and the geometry
+ *   in force: a workgroup of the kernel makes tile_outputs consecutive outputs of one clip. err (may be NULL) gets the message.
+ * flo_resample_out_frames: ceil(in_frames * L / M); FLO_ERR_ARG for an unsupported pair.
+ * flo_batch_resample: a new batch of the same mode, channels, quality / level and bit depth at out_rate, every clip
+ *   converted in one launch (enqueued on the ctx stream; flo_batch_sync on either batch orders it). Clip i has
+ *   out_frames(n_interleaved[i] / channels) * channels samples: whole sample-frames are converted, a trailing partial one is
+ *   not carried over. The source batch stays valid and unchanged; a batch of no clips gives a batch of no clips. The result
+ *   of a clip does not depend on the batch around it. The new batch is destroyed like any other, before its context.
+ * flo_resample: one clip from host memory and back (upload, the same kernel, fetch): *out malloc'ed, flo_free. */
+typedef struct flo_resample_info { uint32_t L, M, taps, tile_outputs; } flo_resample_info;
+int flo_resample_filter(uint32_t in_rate, uint32_t out_rate, flo_resample_info *info, float **table, char *err, size_t err_cap);
+int flo_resample_out_frames(uint32_t in_rate, uint32_t out_rate, uint64_t in_frames, uint64_t *out_frames);
+int flo_batch_resample(flo_batch *src, uint32_t out_rate, flo_batch **out);
+int flo_resample(flo_ctx *ctx, const float *pcm, size_t n_interleaved, uint32_t in_rate, uint32_t out_rate, uint8_t channels,
+                 float **out, size_t *n_out_interleaved);
+
 /* ---- spectral similarity: spectral_similarity (core/analysis.rs:395-437, exported as spectral_similarity_score,
  * lib.rs:1357) over fingerprint sets ----------------------------------------------------------------------------------
  * flo_fingerprint is SpectralFingerprint (analysis.rs:10-26): what flo_analyze / flo_batch_analyze_all return in those
