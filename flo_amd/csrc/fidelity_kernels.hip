@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void fid_totals_kernel(FidTotalsArgs A) {
         const FidBlockDev r = next;
         next = load(b0 + 64 + (unsigned long long)lane);
         const unsigned long long b = b0 + (unsigned long long)lane;
-        const bool in = b < nb;
+        const bool in = b < nb;   // (blocks nb .. nd - 1 are all tail, their compared sums 0: `in` bounds the public records' store)
         double v = 0.0;
         bool q = false;
         if (in) {
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void fid_totals_kernel(FidTotalsArgs A) {
             if (r.signal / (double)r.n >= 1e-10) {
                 q = true;
                 v = 60.0;
-                if (r.error > 0.0) {
+                if (r.error != 0.0) {   // (only an error of exactly 0 counts as 60: a NaN error gives a NaN term)
                     v = 10.0 * log10(r.signal / r.error);
                     v = v < -10.0 ? -10.0 : (v > 60.0 ? 60.0 : v);
                 }

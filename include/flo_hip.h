@@ -516,6 +516,12 @@ int flo_fpindex_pairs(flo_fpindex *ix, float threshold, uint64_t cap, uint32_t *
  *   snr_db = 10 log10(signal / error): +inf when error = 0 (silence included), -inf when signal = 0 < error.
  *   seg_snr_db = the mean (sequential sum in block order, then / seg_blocks) over the blocks with signal / n >= 1e-10 of
  *   clamp(10 log10(signal_b / error_b), -10, 60), an error_b of 0 counting as 60; NaN when no block qualifies.
+ * Non-finite samples (NaN, +-inf, in the source or in the decode): the sums carry them as the IEEE additions above give
+ * them (inf - inf in the difference is NaN), and snr_db follows from the sums by the same three cases. A block qualifies
+ * by the same test (a NaN signal_b does not), an error_b that is not exactly 0 never counts as 60, and the clamp of NaN is
+ * NaN, so one such block makes seg_snr_db NaN. peak_error, peak_out and clipped leave NaN terms out: the maxima are
+ * fmax from 0 (an infinite term is a maximum like any other) and NaN is not > 1. Which NaN encoding a field holds is not
+ * defined. A clip's report depends on that clip alone.
  * No float atomics: two calls return identical bits, whatever the split of the work.
  * flo_batch_fidelity, after flo_batch_sync: out[n_clips * channels], clip-major; clip i's block records at
  * blocks[(block_off[i] + b) * channels + c], block_off (n_clips + 1 entries) the running sum of n_blocks; blocks_cap counts
