@@ -17,13 +17,21 @@ broadcast).
   ds_read2_b64                      two accesses, each 4 x 16 contiguous lanes, bank = dword mod 32
   ds_write_b64                      4 x 16 contiguous lanes, bank = dword mod 32
   ds_write_b128                     8 x 8 contiguous lanes, bank = dword mod 32
+  ds_write2_b64                     two ds_write_b64 (assumed by analogy with ds_read2_b64; not measured by itself)
+A lane group none of whose lanes is enabled is still charged its cycle (the counters of the masked band statistics,
+--layout masks, agree with this reading to within two cycles per frame).
 
 The packer wave's LDS work depends on the data (non-zeros per frame, fall-back forms); it is not modelled here: the
 counters' per-frame totals minus this model's transform-wave totals are the packer's share.
 
-  python3 diag/lds_model.py [--rate 44100] [--layout old|new] [--isa lossy_kernels-hip-amdgcn-amd-amdhsa-gfx950.s]
+  python3 diag/lds_model.py [--rate 44100] [--layout old|new|masks] [--isa lossy_kernels-hip-amdgcn-amd-amdhsa-gfx950.s]
 --layout old: the pack rows as the compiler read them before pack_row() (dword pieces, read2_b64, kRowLane's rcount);
---layout new: whole-row reads, rcount from row kRowS10 (the current kernel).
+--layout new: whole-row reads, rcount from row kRowS10;
+--layout masks: new, with the band statistics by lane masks (band_stats_2<., true, true>): no keep / dst rows, one
+  ds_write2_b64 per dirty position below 15 that carries the closing lanes only, the last store as it was.
+  --gather-masks: the three gather groups under their list-length masks too (diag/exp_gather_masks.patch).
+  --skip-empty charges nothing for a lane group with no enabled lane (the other reading of the hardware; the counters
+  say it is the wrong one: DESIGN.md §6).
 With --isa, the ds_* instruction mix of one unrolled frame of the bench kernel is read from the listing and compared
 with the model's site list.
 """
@@ -96,7 +104,10 @@ RULES = {   # kind: (list of accesses, each (lane groups, dwords per lane, banks
     "ds_read2_b32": [(G32, 1, 32), (G32, 1, 32)], "ds_write2_b32": [(G32, 1, 32), (G32, 1, 32)],
     "ds_read2_b64": [(contig(16), 2, 32), (contig(16), 2, 32)],
     "ds_write_b64": [(contig(16), 2, 32)], "ds_write_b128": [(contig(8), 4, 32)],
+    "ds_write2_b64": [(contig(16), 2, 32), (contig(16), 2, 32)],
 }
+SKIP_EMPTY = False
+GATHER_MASKS = False
 
 
 def cost(kind, addrs):
@@ -114,6 +125,8 @@ def cost(kind, addrs):
                 for i in range(dw):
                     d = ad[l] // 4 + i
                     per_bank.setdefault(d % nbank, set()).add(d)
+            if SKIP_EMPTY and not per_bank:
+                continue
             cyc += max([len(v) for v in per_bank.values()] or [1])
             base += 1
     return cyc, cyc - base
@@ -183,16 +196,22 @@ def sites(rate, layout):
                     else:
                         S += [("band statistics", "keep / dst rows (dword pieces)", "ds_read_b32", row(rr + g, 4 * comp[i]))]
                         i += 1
-    else:
+    elif layout == "new":
         S += [("band statistics", "keep / dst rows (whole rows)", "ds_read_b128", row(rr + g)) for rr in (R_KEEP, R_DST) for g in range(4)]
     SL = X + 9216
+    masks = layout == "masks"
     for e in es:
-        def dst(l, e=e):
+        def dst(l, e=e, off=0):
             m = lane_bnd[l]
             if (m >> e) & 1:
-                return SL + 16 * (lane_slot0[l] + bin(m & ((1 << e) - 1)).count("1"))
-            return SL + 16 * (SLOT_CAP + l)   # the lane's trash slot
-        S += [("band statistics", "slot stores", "ds_write_b128", lanes(dst))]
+                return SL + 16 * (lane_slot0[l] + bin(m & ((1 << e) - 1)).count("1")) + off
+            return None if masks else SL + 16 * (SLOT_CAP + l)   # masked off / the lane's trash slot
+        if masks and e == 15:   # every lane closes its last segment: unmasked, the quad as it is
+            S += [("band statistics", "slot store (element 15, all lanes)", "ds_write_b128", lanes(dst))]
+        elif masks:
+            S += [("band statistics", "slot stores (closing lanes)", "ds_write2_b64", [lanes(dst), lanes(lambda l: dst(l, off=8))])]
+        else:
+            S += [("band statistics", "slot stores", "ds_write_b128", lanes(dst))]
     zero = SLOT_CAP + 64
     for u in range(12):
         def src(l, u=u):
@@ -200,6 +219,8 @@ def sites(rate, layout):
             bs0 = band_slot0[b] + (l >> 5)
             bs1 = band_slot0[b + 1] if (l & 31) < 25 else 0
             s = bs0 + 2 * u
+            if masks and GATHER_MASKS and not bs0 + 2 * 4 * (u // 4) < bs1:
+                return None   # the lane's list ends before this group
             return SL + 16 * (s if s < bs1 else zero)
         S += [("band statistics", "slot gathers", "ds_read_b128", lanes(src))]
     for r in range(8):
@@ -236,9 +257,13 @@ def isa_mix(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rate", type=int, default=44100)
-    ap.add_argument("--layout", default="old", choices=["old", "new"])
+    ap.add_argument("--layout", default="old", choices=["old", "new", "masks"])
+    ap.add_argument("--skip-empty", action="store_true")
+    ap.add_argument("--gather-masks", action="store_true")
     ap.add_argument("--isa")
     a = ap.parse_args()
+    global SKIP_EMPTY, GATHER_MASKS
+    SKIP_EMPTY, GATHER_MASKS = a.skip_empty, a.gather_masks
     S = sites(a.rate, a.layout)
     tab = {}
     tot_c = tot_x = 0

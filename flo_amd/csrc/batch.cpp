@@ -330,7 +330,7 @@ static int batch_encode_launch(flo_batch *b) {
             A.part_reg = b->d_part;
             A.parts = fin.parts;
         }
-        rc = timed_launch(c, "lossy_chain2q", [&] { return launch_lossy_chain2q(A, P, c->stream); });
+        rc = timed_launch(c, "lossy_chain2q", [&] { return launch_lossy_chain2q(A, P, b->ts->dev_masks, c->stream); });
         if (rc == FLO_OK) b->epoch = epoch;   // (a launch that did not run zeroed nothing: its epoch is used again)
     } else if (P.form == LossyForm::Chain) {
         LossyArgs A = make_args(b);

@@ -184,7 +184,7 @@ int get_tables(flo_ctx *c, uint32_t sr, float quality, TableSet **out) {
            i_band = add(h.band.data(), h.band.size()), i_bc = add(h.band_count.data(), h.band_count.size() * 4),
            i_s10 = add(h.s10d.data(), h.s10d.size() * 4), i_lb = add(h.lane_bnd.data(), h.lane_bnd.size() * 4),
            i_ls = add(h.lane_slot0.data(), h.lane_slot0.size() * 4), i_bs = add(h.band_slot0.data(), h.band_slot0.size() * 4),
-           i_win = add(h.window.data(), h.window.size() * 4);
+           i_win = add(h.window.data(), h.window.size() * 4), i_masks = add(&h.masks, sizeof(StatMasks));
     hipError_t e = hipMalloc(&t->blob, total);
     if (e != hipSuccess) {
         delete t;
@@ -210,11 +210,12 @@ int get_tables(flo_ctx *c, uint32_t sr, float quality, TableSet **out) {
     t->dev.lane_slot0 = (const uint32_t *)P(i_ls);
     t->dev.band_slot0 = (const uint32_t *)P(i_bs);
     t->dev_window = (const float *)P(i_win);
+    t->dev_masks = (const StatMasks *)P(i_masks);
     t->dev.max_band_slots = h.max_band_slots;
     t->dev.dirty = h.dirty;
     t->dev.smr_thr = h.smr_threshold;
     t->dev.q_transparent = h.q_transparent;
-    if (h.n_slots > kSlotCap || h.max_band_slots > 64) {   // (cannot happen: 64 lanes + 24 band edges, 64 lanes per band)
+    if (h.n_slots > kSlotCap || h.max_band_slots > 64 || !h.masks_ok) {   // (cannot happen: 64 lanes + 24 band edges, 64 lanes per band)
         hipFree(t->blob);
         delete t;
         return fail(c, FLO_ERR_ARG, "band segment table exceeds capacity");

@@ -1050,9 +1050,18 @@ struct StereoLds {
 // band b on lane b and channel 1's on lane 32 + b, which is what the merged masking pass consumes.
 // SO_PRE: the twelve gather addresses (so_pre) and the zero slot were prepared once by the caller (band_stats_2_prepare), whose
 // slot area is not shared with anything else: fifteen instructions per frame less.
-template <uint32_t DIRTY = 0xFFFFu, bool SO_PRE = false>
+// MASKS (with SO_PRE): rows kRowKeep / kRowDst are not read. Which lanes close a segment behind element e is a lane mask
+// in scalar registers (close[e]: StatMasks::close, band_stats_2_masks), and a lane's segments go to consecutive slots
+// from slot_first (band_stats_2_prepare: lane_slot0). Per dirty position, under exec = close[e]: ONE store that carries the
+// closing lanes only, the address advanced by 16, the accumulator restarted by a multiplication with 0 (inf x 0 = NaN, as
+// x 0.0 from the row gave it); the other lanes keep their sums untouched, where the row multiplied them by 1.0. No trash
+// stores. The gathers are as they were (under StatMasks::gather they measured no faster: DESIGN.md §6,
+// diag/exp_gather_masks.patch).
+template <uint32_t DIRTY = 0xFFFFu, bool SO_PRE = false, bool MASKS = false>
 __device__ __forceinline__ void band_stats_2(const int lane, const v2f (&c)[16], float4 *slot, const LossyDevTables &T,
-                                             float &energy1, float &bmax1, const uint32_t *so_pre = nullptr) {
+                                             float &energy1, float &bmax1, const uint32_t *so_pre = nullptr,
+                                             const unsigned long long *close = nullptr, const uint32_t slot_first = 0) {
+    static_assert(!MASKS || SO_PRE, "the masked form takes its addresses from band_stats_2_prepare");
     // Slot addresses as 32-bit LDS offsets from ONE scalar base (as the sum of the clip's LDS base and the member offset
     // the compiler re-added both terms for every access); the accesses go through address-space-3 pointers so that they
     // stay ds_* instructions. A slot is 16 bytes (sums of both channels, maxima of both channels): ONE ds_write_b128 per
@@ -1082,10 +1091,11 @@ __device__ __forceinline__ void band_stats_2(const int lane, const v2f (&c)[16],
     }
     const uint32_t dirty = DIRTY;   // compile-time: straight-line code
     v4f am = {0.f, 0.f, 0.f, 0.f};   // running (sum left, sum right, max left, max right): one register quad, stored as it is
+    uint32_t sa = slot_first;   // MASKS: where this lane's next closed segment goes (set per frame: the slots are reused)
 #pragma unroll
     for (int g = 0; g < 4; g++) {
-        const float4 keep = pack_row(&T.pack[(kRowKeep + g) * 64 + lane]);
-        const float4 dsto = pack_row(&T.pack[(kRowDst + g) * 64 + lane]);
+        const float4 keep = MASKS ? make_float4(0.f, 0.f, 0.f, 0.f) : pack_row(&T.pack[(kRowKeep + g) * 64 + lane]);
+        const float4 dsto = MASKS ? make_float4(0.f, 0.f, 0.f, 0.f) : pack_row(&T.pack[(kRowDst + g) * 64 + lane]);
         const float kp[4] = {keep.x, keep.y, keep.z, keep.w};
         const uint32_t dv[4] = {__float_as_uint(dsto.x), __float_as_uint(dsto.y), __float_as_uint(dsto.z), __float_as_uint(dsto.w)};
 #pragma unroll
@@ -1101,7 +1111,28 @@ __device__ __forceinline__ void band_stats_2(const int lane, const v2f (&c)[16],
                 am.z = max_abs_raw(am.z, c[e].x);
                 am.w = max_abs_raw(am.w, c[e].y);
             }
-            if ((dirty >> e) & 1u) {   // compile-time
+            if (MASKS && ((dirty >> e) & 1u)) {   // compile-time
+                if (e < 15) {
+                    // One statement, so that nothing of the compiler's runs under the narrowed exec. The halves of am are
+                    // operands of their own (a packed multiplication takes a register pair), so the 16 bytes go out as the
+                    // two halves of a ds_write2_b64 (8 array cycles, like ds_write_b128): as one quad operand next to its
+                    // own halves, the store cost a register-pair copy at every position.
+                    v2f lo = am.xy, hi = am.zw;
+                    unsigned long long saved;
+                    asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
+                                 "ds_write2_b64 %[a], %[lo], %[hi] offset1:1\n\t"
+                                 "v_add_u32 %[a], 16, %[a]\n\t"
+                                 "v_pk_mul_f32 %[lo], %[lo], 0 op_sel_hi:[1,0]\n\t"
+                                 "v_pk_mul_f32 %[hi], %[hi], 0 op_sel_hi:[1,0]\n\t"
+                                 "s_mov_b64 exec, %[sv]"
+                                 : [a] "+v"(sa), [lo] "+v"(lo), [hi] "+v"(hi), [sv] "=&s"(saved)
+                                 : [m] "s"(close[e])
+                                 : "memory");
+                    am.xy = lo, am.zw = hi;
+                } else {   // every lane closes its last segment behind element 15 (close[15] is all ones: build_lossy_tables)
+                    *reinterpret_cast<lds_v4f *>((uintptr_t)sa) = am;
+                }
+            } else if ((dirty >> e) & 1u) {   // compile-time
                 *reinterpret_cast<lds_v4f *>((uintptr_t)(s0 + 2u * dv[k])) = am;
                 if (e < 15) {
                     am.xy = am.xy * splat2(kp[k]);
@@ -1151,14 +1182,30 @@ __device__ __forceinline__ void band_stats_2(const int lane, const v2f (&c)[16],
 }
 
 // once per launch, for band_stats_2<., true>: the zero slot and the gather addresses of this lane
-__device__ __forceinline__ void band_stats_2_prepare(const int lane, float4 *slot, const float4 *pack, uint32_t (&so)[12]) {
+// (slot_first, for band_stats_2<., true, true>: the address of the lane's first segment slot)
+__device__ __forceinline__ void band_stats_2_prepare(const int lane, float4 *slot, const float4 *pack, uint32_t (&so)[12],
+                                                     uint32_t &slot_first) {
     const uint32_t s0 = (uint32_t)(uintptr_t)slot;
+    slot_first = s0 + 16u * reinterpret_cast<const uint32_t *>(pack + kRowLane * 64 + lane)[1];
     if (lane < 4) reinterpret_cast<float *>(slot + kZeroSlot)[lane] = 0.f;
 #pragma unroll
     for (int g = 0; g < 3; g++) {
         const float4 lst = pack[(kRowLst + g) * 64 + lane];
         so[4 * g + 0] = s0 + 2u * __float_as_uint(lst.x), so[4 * g + 1] = s0 + 2u * __float_as_uint(lst.y);
         so[4 * g + 2] = s0 + 2u * __float_as_uint(lst.z), so[4 * g + 3] = s0 + 2u * __float_as_uint(lst.w);
+    }
+}
+// once per launch, for band_stats_2<DIRTY, true, true>: the close masks of the positions it masks, out of device memory
+// (a uniform pointer: scalar loads) into scalar registers, where they stay for the launch. Fetched by the transform wave
+// and not passed by value: as kernel arguments they were live from the kernel's entry on, through the packer wave's code,
+// whose scalar registers then spilled to vector lanes.
+template <uint32_t DIRTY>
+__device__ __forceinline__ void band_stats_2_masks(const StatMasks *masks, unsigned long long (&close)[16]) {
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+        const bool used = e < 15 && ((DIRTY >> e) & 1u);   // (behind element 15 every lane closes: stored without a mask)
+        close[e] = used ? masks->close[e] : 0ull;
+        if (used) asm volatile("" : "+s"(close[e]));
     }
 }
 

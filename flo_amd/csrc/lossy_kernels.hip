@@ -539,7 +539,7 @@ constexpr int kPackerPrio = 1;
 // What a launch of one round passes as chain2q_pturns (0: no turns): packers that share a SIMD go first in turn.
 constexpr unsigned kPackerTurns = 1;
 template <bool COEFFS, uint32_t DIRTY, bool DBG>
-__global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArgs A, int clips_per_wg) {
+__global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArgs A, int clips_per_wg, const StatMasks *__restrict__ masks) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63;
@@ -786,8 +786,11 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
     T.pack = reinterpret_cast<const float4 *>(lds_raw);
     // the slot area belongs to band statistics alone in this form: its zero slot is written once and the lane's twelve
     // gather addresses stay in registers (the wave has them to spare now that the quantiser lives in the packer)
-    uint32_t so_pre[12];
-    band_stats_2_prepare(lane, cs.slot, A.T.pack, so_pre);
+    // ... and so do the address of the lane's first slot and the band table's close masks (band_stats_2<., true, true>)
+    uint32_t so_pre[12], slot_first;
+    band_stats_2_prepare(lane, cs.slot, A.T.pack, so_pre, slot_first);
+    unsigned long long close[16];
+    band_stats_2_masks<DIRTY>(masks, close);
     for (;;) {
         wait_counter(&cs.clip_seq, ++seq);
         const unsigned clip = (unsigned)__builtin_amdgcn_readfirstlane((int)cs.clip_cur);
@@ -910,7 +913,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             // band statistics (both channels): channel 0's band b on lane b, channel 1's on lane 32 + b
             float energy1, bmax1;
 #if (FLO_SKIP & 1) == 0
-            band_stats_2<DIRTY, true>(ln, c, cs.slot, T, energy1, bmax1, so_pre);
+            band_stats_2<DIRTY, true, true>(ln, c, cs.slot, T, energy1, bmax1, so_pre, close, slot_first);
 #else
             energy1 = c[0].x + c[5].y;
             bmax1 = c[1].x + c[7].y;
@@ -1872,7 +1875,7 @@ int chain2q_clips_per_wg(int n_clips) {
     return g < 1 ? 1 : g;
 }
 template <bool COEFFS, uint32_t DIRTY, bool DBG>
-static int launch_chain2q_t(const LossyArgs &A, int clips, hipStream_t s) {
+static int launch_chain2q_t(const LossyArgs &A, const StatMasks *masks, int clips, hipStream_t s) {
     int g = chain2q_clips_per_wg(A.n_clips);
     if (clips >= 1 && clips <= FLO_C2X_THREADS / 128) g = clips;   // diagnostic: FLO_CHAIN2X_CLIPS
     const size_t lds = kPackBytesHotT + (size_t)g * sizeof(Clip2qLds);
@@ -1884,17 +1887,18 @@ static int launch_chain2q_t(const LossyArgs &A, int clips, hipStream_t s) {
     // dealing evens the slots out.
     LossyArgs B = A;
     B.chain2q_pturns = (unsigned long long)wgs * (unsigned)g >= (unsigned long long)A.n_clips ? kPackerTurns : 0u;
-    hipLaunchKernelGGL((lossy_chain2q_kernel<COEFFS, DIRTY, DBG>), dim3(wgs), dim3(128 * g), lds, s, B, g);
+    hipLaunchKernelGGL((lossy_chain2q_kernel<COEFFS, DIRTY, DBG>), dim3(wgs), dim3(128 * g), lds, s, B, g, masks);
     FLO_LAUNCH_CHECK();
     return 0;
 }
-int launch_lossy_chain2q(const LossyArgs &A, const LossyPlan &P, hipStream_t s) {
+int launch_lossy_chain2q(const LossyArgs &A, const LossyPlan &P, const StatMasks *masks, hipStream_t s) {
+    if (!masks) return -1;
     assert(P.form == LossyForm::Chain2q && A.nch == 2 && !A.exact);
     switch (P.chain2q) {
-    case Chain2qKernel::InCoeffs: return launch_chain2q_t<true, 0xFFFFu, true>(A, P.chain2q_clips, s);
-    case Chain2qKernel::Debug: return launch_chain2q_t<false, 0xFFFFu, true>(A, P.chain2q_clips, s);
-    case Chain2qKernel::Dirty44k: return launch_chain2q_t<false, kDirty44k, false>(A, P.chain2q_clips, s);
-    case Chain2qKernel::Generic: return launch_chain2q_t<false, 0xFFFFu, false>(A, P.chain2q_clips, s);
+    case Chain2qKernel::InCoeffs: return launch_chain2q_t<true, 0xFFFFu, true>(A, masks, P.chain2q_clips, s);
+    case Chain2qKernel::Debug: return launch_chain2q_t<false, 0xFFFFu, true>(A, masks, P.chain2q_clips, s);
+    case Chain2qKernel::Dirty44k: return launch_chain2q_t<false, kDirty44k, false>(A, masks, P.chain2q_clips, s);
+    case Chain2qKernel::Generic: return launch_chain2q_t<false, 0xFFFFu, false>(A, masks, P.chain2q_clips, s);
     default: return -1;
     }
 }

@@ -80,7 +80,9 @@ inline bool lossy_exact(bool asked, const LossyDevTables &T) { return asked || T
 
 // the launchers launch the kernels the plan names (encode_plan.hpp); they choose only the launch geometry
 int launch_lossy_chain(const LossyArgs &A, const LossyPlan &P, hipStream_t s);
-int launch_lossy_chain2q(const LossyArgs &A, const LossyPlan &P, hipStream_t s);  // stereo only: one lock-step transform wave + one quantiser-and-packer wave per clip
+// stereo only: one lock-step transform wave + one quantiser-and-packer wave per clip. masks: the band table's lane masks
+// in device memory (LossyTablesHost::masks of the table set A.T comes from)
+int launch_lossy_chain2q(const LossyArgs &A, const LossyPlan &P, const StatMasks *masks, hipStream_t s);
 int launch_lossy_frames_pass(const LossyArgs &A, FrameKernel k, hipStream_t s);
 // bytes reserved per frame in the frame-parallel form: header + scale words + every channel's largest sparse blob
 inline unsigned int lossy_slot_bytes(int nch) {

@@ -26,4 +26,14 @@ constexpr int kRowAthN = 44;      // 4 rows: ATH amplitude thresholds of those p
 constexpr int kRowBoN = 48;       // 4 rows: byte offset (16 x band) of those positions into a float4-per-band table
 constexpr int kRowBlk = 52;       // 1 row : dwords 0..7 = bit b set when block k (positions 128 k .. 128 k + 127) holds bins of band b; read uniformly
 constexpr int kPackRows = 53;
+
+// Band statistics of the lock-step stereo chain form (band_stats_2<., ., true>) without rows kRowKeep / kRowDst: the same
+// band table as two sets of 64-bit lane masks (uploaded with the tables; the transform wave holds the close masks in
+// scalar registers). A lane's segment slots are numbered consecutively from its lane_slot0 (kRowLane .y), so the lane
+// that closes its s-th segment stores to slot lane_slot0 + s: one running address per lane, advanced behind every store.
+struct StatMasks {
+    unsigned long long close[16];   // bit l of close[e]: lane l closes a band segment behind element e (its kRowKeep value there is 0.0)
+    unsigned long long gather[3];   // bit l of gather[g]: lane l's slot list (kRowLst) has more than 4 g entries. No kernel
+                                    // reads these: gathers masked by them measured no faster (diag/exp_gather_masks.patch)
+};
 }  // namespace flo

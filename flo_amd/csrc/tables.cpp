@@ -228,6 +228,20 @@ void build_lossy_tables(uint32_t sample_rate, float quality, LossyTablesHost &t)
         PU(kRowS10, 16 + lane / 4, lane % 4, rc);   // the same, as dword 64 + lane of row kRowS10 (one conflict-free ds_read_b32)
         PU(kRowLane, lane, 3, bs0 | (bs1 << 16));
     }
+    // the same bookkeeping as lane masks (StatMasks): who closes a segment behind element e, whose list reaches group g
+    t.masks = StatMasks{};
+    for (int lane = 0; lane < 64; lane++) {
+        for (int e = 0; e < 16; e++)
+            if ((t.lane_bnd[lane] >> e) & 1u) t.masks.close[e] |= 1ull << lane;
+        const int bl = lane & 31;
+        const uint32_t bs0 = t.band_slot0[bl < 25 ? bl : 24] + (uint32_t)(lane >> 5), bs1 = bl < 25 ? t.band_slot0[bl + 1] : 0u;
+        const uint32_t n = bs0 < bs1 ? (bs1 - bs0 + 1u) / 2u : 0u;   // entries of the lane's list: every other slot from bs0
+        for (int g = 0; g < 3; g++)
+            if (n > 4u * (uint32_t)g) t.masks.gather[g] |= 1ull << lane;
+    }
+    uint32_t nonzero = 0;
+    for (int e = 0; e < 16; e++) nonzero |= (t.masks.close[e] != 0) << e;
+    t.masks_ok = nonzero == t.dirty && t.masks.close[15] == ~0ull && t.n_slots <= kSlotCapHost;
 }
 
 }  // namespace flo

@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "pack_rows.h"
+
 namespace flo {
 
 constexpr int kNumBands = 25;
@@ -41,6 +43,8 @@ struct LossyTablesHost {
     int max_band_slots = 0;            // max over bands of slot count
     uint32_t dirty = 0;                // OR of lane_bnd over the lanes: element positions at which some lane closes a segment
     int n_slots = 0;
+    StatMasks masks = {};              // rows kRowKeep / kRowLst as lane masks (pack_rows.h); lane_slot0 is each lane's first slot
+    bool masks_ok = false;             // dirty == {e : masks.close[e] != 0}, every lane closes behind element 15, the slots fit
 };
 
 void build_lossy_tables(uint32_t sample_rate, float quality, LossyTablesHost &t);
