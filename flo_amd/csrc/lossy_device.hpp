@@ -470,6 +470,12 @@ __device__ __forceinline__ void post_rotate_transpose(const int lane, const floa
 // single-channel functions above - same products, same fused multiply-adds, same order - so the coefficients are
 // bit-identical to theirs (the kernel forms are compared byte for byte by the tests).
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));   // a pack row held in registers across frames (one register quad)
+__device__ __forceinline__ v4f pack_row_v(const float4 *p) {   // pack_row, as the native vector
+    v4f v = *reinterpret_cast<const v4f *>(p);
+    asm("" : "+v"(v));
+    return v;
+}
 __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 // (-a) * w.y + (-c) and a * w.y + (-c) on both halves, w.y broadcast by op_sel: the same fused operation as fma2 with a splat
 // of w.y - for the SECOND pair of a 16-byte constant row the compiler copies the component into a fresh register pair
@@ -492,6 +498,18 @@ __device__ __forceinline__ v2f mul2_hi(v2f a, v2f w) {   // a * w.y on both halv
 __device__ __forceinline__ v2f fma2_a_hi_nc(v2f a, v2f w, v2f c) {
     v2f r;
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(r) : "v"(a), "v"(w), "v"(c));
+    return r;
+}
+// (the same with w.x: the multiplier is named inside the instruction, so a twiddle pair that stays in registers across frames
+// is used as it lies - written as splat2(w.x) the copies are loop invariants and are hoisted into registers of their own)
+__device__ __forceinline__ v2f mul2_lo(v2f a, v2f w) {   // a * w.x on both halves
+    v2f r;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(w));
+    return r;
+}
+__device__ __forceinline__ v2f fma2_a_lo_nc(v2f a, v2f w, v2f c) {   // a * w.x - c
+    v2f r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(r) : "v"(a), "v"(w), "v"(c));
     return r;
 }
 __device__ __forceinline__ v2f splat2(float x) { return (v2f){x, x}; }
@@ -669,6 +687,64 @@ __device__ __forceinline__ void post_rotate_transpose_2(const int lane, const v2
             R = fma2(-zi[r], wy, -(zr[r] * wx));
             I = fma2(zi[r], wx, -(zr[r] * wy));
         }
+        w0[144 * r] = make_float2(R.x, R.y);
+        w1[144 * (7 - r)] = make_float2(I.x, I.y);
+    }
+    wave_sync();
+    const float4 *p = reinterpret_cast<const float4 *>(&c2[18 * lane]);
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const float4 v = p[q];
+        c[2 * q] = (v2f){v.x, v.y};
+        c[2 * q + 1] = (v2f){v.z, v.w};
+    }
+    wave_sync();
+}
+
+// The fold in SPLIT form (lossy_chain2q_kernel). In fold_2 every output of row r is made of one product per half-frame:
+// the NEW half (be, bo) gives re for r < 4 and im for r >= 4 (the b-part), the OLD half (ae, ao) the other one (the a-part).
+// A half therefore need not be kept as raw samples until it is the old half: its a-parts are computed when it is folded as
+// the new half, from the window row that is in registers then, and carried as 8 v2f instead of 16. The operations, their
+// operands and their order per component are fold_2's, so (zr, zi) are bit-identical to fold_2 over the same two halves.
+// tw[k] = row kRowTw + k of the pack (the rotation twiddles tw[lane + 64 r], two rows per float4), held by the caller.
+__device__ __forceinline__ v2f fold_a_part(const int r, const v2f he, const v2f ho, const float4 ww) {
+    const v2f wae = splat2(ww.x), wao = splat2(ww.y);
+    return r < 4 ? fma2(ho, wao, -(he * wae)) : fma2(-ho, wao, he * wae);
+}
+// the carry in front of a clip's first frame: the a-parts of the pre-roll's 1024 zeros (encoder.rs:177), by fold_2's own
+// expressions (a zero's sign depends on the window's)
+__device__ __forceinline__ void fold_carry_init_2(const int lane, v2f (&acar)[8], const LossyDevTables &T) {
+#pragma unroll
+    for (int r = 0; r < 8; r++) acar[r] = fold_a_part(r, splat2(0.f), splat2(0.f), T.pack[(kRowWin + r) * 64 + lane]);
+}
+// (ne, no): the new half; acar: in, the old half's a-parts; out, this half's. (ne, no) are dead afterwards.
+__device__ __forceinline__ void fold_carry_2(const int lane, const v2f (&ne)[8], const v2f (&no)[8], v2f (&acar)[8],
+                                             const v4f (&tw)[4], v2f (&zr)[8], v2f (&zi)[8], const LossyDevTables &T) {
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const float4 ww = T.pack[(kRowWin + r) * 64 + lane];
+        const v2f wbe = splat2(ww.z);
+        const v2f whi = {ww.z, ww.w};   // (ww.w enters through fma2_na_hi_nc)
+        const v2f t2 = (r & 1) ? tw[r >> 1].zw : tw[r >> 1].xy;   // (wx, wy) of fold_2
+        const v2f bp = fma2_na_hi_nc(no[r], whi, ne[r] * wbe);
+        const v2f re = r < 4 ? bp : acar[r], im = r < 4 ? acar[r] : bp;
+        zr[r] = fma2_na_hi_nc(im, t2, mul2_lo(re, t2));   // -im wy - re wx
+        zi[r] = fma2_a_hi_nc(re, t2, mul2_lo(im, t2));    //  re wy - im wx
+        acar[r] = fold_a_part(r, ne[r], no[r], ww);
+    }
+}
+
+// post_rotate_transpose_2 with the twiddle rows handed in (tw as in fold_carry_2): the same operations
+__device__ __forceinline__ void post_rotate_transpose_2_tw(const int lane, const v2f (&zr)[8], const v2f (&zi)[8], float2 *c2,
+                                                           v2f (&c)[16], const v4f (&tw)[4]) {
+    const int pl = 2 * lane + 2 * (lane >> 3);
+    float2 *const w0 = c2 + pl;
+    float2 *const w1 = c2 + (1149 - 7 * 144) - pl;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const v2f t2 = (r & 1) ? tw[r >> 1].zw : tw[r >> 1].xy;
+        const v2f R = fma2_na_hi_nc(zi[r], t2, mul2_lo(zr[r], t2));   // -zi wy - zr wx
+        const v2f I = fma2_a_lo_nc(zi[r], t2, mul2_hi(zr[r], t2));    //  zi wx - zr wy
         w0[144 * r] = make_float2(R.x, R.y);
         w1[144 * (7 - r)] = make_float2(I.x, I.y);
     }

@@ -791,6 +791,12 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
     band_stats_2_prepare(lane, cs.slot, A.T.pack, so_pre, slot_first);
     unsigned long long close[16];
     band_stats_2_masks<DIRTY>(masks, close);
+    // the rotation twiddles of the fold and of the post-rotation: per-lane constants of the launch, held in registers
+    v4f tw[4];
+    if (!COEFFS) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) tw[k] = pack_row_v(&T.pack[(kRowTw + k) * 64 + lane]);
+    }
     for (;;) {
         wait_counter(&cs.clip_seq, ++seq);
         const unsigned clip = (unsigned)__builtin_amdgcn_readfirstlane((int)cs.clip_cur);
@@ -800,10 +806,13 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
         const float *pcm = A.pcm + A.clip_off[clip];
 
         float prev = 0.f;   // temporal masking state: channel 0's band b on lane b, channel 1's on lane 32 + b
-        v2f ae[8], ao[8], be[8], bo[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) ae[r] = ao[r] = splat2(0.f);  // pre-roll: 1024 zeros (encoder.rs:177)
-        if (!COEFFS) load_half_fast_2(lane_id_opaque(), pcm, 0, be, bo);   // (opaque: keeps 16 address pairs out of loop-invariant registers)
+        // (ne, no): the half-frame in flight; acar: what the half before it gives to the next fold (fold_carry_2). The carry
+        // starts every clip from the pre-roll's zeros
+        v2f ne[8], no[8], acar[8];
+        if (!COEFFS) {
+            fold_carry_init_2(lane_id_opaque(), acar, T);
+            load_half_fast_2(lane_id_opaque(), pcm, 0, ne, no);   // (opaque: keeps 16 address pairs out of loop-invariant registers)
+        }
         STAMPS_BEGIN();
         // The frame loop is software-pipelined by two phases. (1) The fold of frame h + 1, which only needs PCM that is already
         // in registers, runs at the end of frame h: entering frame h, (zr, zi) hold its folded input, and the half-frame
@@ -813,7 +822,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
         // fills the LDS round trip the wave would otherwise sit out (a wave issues in order). The packer learns a frame's
         // band tables a third of a frame later and takes its coefficients correspondingly early (take_next).
         v2f zr[8], zi[8];
-        if (!COEFFS) fold_2(lane_id_opaque(), ae, ao, be, bo, zr, zi, T);
+        if (!COEFFS) fold_carry_2(lane_id_opaque(), ne, no, acar, tw, zr, zi, T);
         float pend_e = 0.f, pend_m = 0.f;   // band energies / maxima of the frame whose masking pass is pending
         // masking level, temporal masking, scale factors of frame gp (clip frame hp) from its band statistics; publishes them
         auto mask_publish = [&](const int ln, const uint32_t gp, const unsigned hp, const float energy1, const float bmax1,
@@ -850,7 +859,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             if (DBG && A.dbg_sfw && bnd < 25) A.dbg_sfw[((frame0 + hp) * 2 + up) * 25 + bnd] = (unsigned short)sfw1;
             set_counter(&cs.ts_ready, gp + 1);
         };
-        auto frame_body = [&](const unsigned h, v2f (&ne)[8], v2f (&no)[8], v2f (&fe)[8], v2f (&fo)[8]) __attribute__((always_inline)) {
+        auto frame_body = [&](const unsigned h) __attribute__((always_inline)) {
             const int ln = lane_id_opaque();
             const uint32_t g = fbase + h;
             FLO_MARK("frame_begin");
@@ -893,7 +902,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
                 FLO_MARK("fft_done");
                 STAMP(2);
 #if (FLO_SKIP & 4) == 0
-                post_rotate_transpose_2(ln, zr, zi, cs.u.coef2, c, T);
+                post_rotate_transpose_2_tw(ln, zr, zi, cs.u.coef2, c, tw);
 #else
 #pragma unroll
                 for (int e = 0; e < 8; e++) { c[2 * e] = zr[e]; c[2 * e + 1] = zi[e]; }
@@ -926,19 +935,16 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
                 pend_e = energy1, pend_m = bmax1;
                 // the next frame's fold
 #if (FLO_SKIP & 128) == 0
-                fold_2(ln, fe, fo, ne, no, zr, zi, T);
+                fold_carry_2(ln, ne, no, acar, tw, zr, zi, T);
 #else
 #pragma unroll
-                for (int r = 0; r < 8; r++) { zr[r] = fe[r] + ne[r]; zi[r] = fo[r] - no[r]; }
+                for (int r = 0; r < 8; r++) { zr[r] = acar[r] + ne[r]; zi[r] = acar[r] - no[r]; }
 #endif
             }
             FLO_MARK("frame_end");
             STAMP(5);
         };
-        for (unsigned h = 0; h < hops; h += 2) {
-            frame_body(h, ae, ao, be, bo);
-            if (h + 1 < hops) frame_body(h + 1, be, bo, ae, ao);
-        }
+        for (unsigned h = 0; h < hops; h++) frame_body(h);
         if (!COEFFS && hops) {   // the last frame's masking pass has no FFT to hide behind
             const int ln = lane_id_opaque();
             const float4 sd0 = T.pack[kRowS10 * 64], sd1 = T.pack[kRowS10 * 64 + 1];

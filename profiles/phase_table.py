@@ -6,7 +6,9 @@
   python3 profiles/phase_table.py /tmp/lk_marks.s [mangled-name-substring]
 
 The markers pin the schedule (they are memory clobbers), so the counts are those of the marked build, a few per cent
-above the shipped one. Counted per stereo frame (the loop is unrolled by two: both bodies are averaged).
+above the shipped one. Counted per stereo frame: the counts of a phase are divided by the number of frame bodies in
+the listing (one; two while the loop was unrolled by two). What follows the last frame_end marker runs once per clip,
+not per frame (the loop's back edge, the last frame's masking pass, the clip loop): it is listed apart and not summed.
 """
 import collections
 import re
@@ -38,7 +40,11 @@ def main():
     phases = collections.OrderedDict()
     cur = "pre (clip set-up, packer wave)"
     order = []
-    for l in lines[start:end]:
+    bodies = max(1, sum(1 for l in lines[start:end] if l.strip().startswith("; MARK frame_begin")))
+    last_end = max((i for i in range(start, end) if lines[i].strip().startswith("; MARK frame_end")), default=end)
+    for i, l in enumerate(lines[start:end], start):
+        if i == last_end + 1:
+            cur = "post (behind the last frame_end)"
         s = l.strip()
         m = re.match(r"; MARK (\w+)", s)
         if m:
@@ -62,14 +68,15 @@ def main():
     names = {"frame_begin": "prefetch (16 loads), masking rows", "prefetch_done": "fft512 x2 + masking pass (prev. frame)",
              "fft_done": "post-rotation + transpose", "postrot_done": "band_stats_2",
              "bandstats_done": "fold of the next frame (a)", "frame_end": "fold of the next frame (b), loop"}
-    print(f"{'phase':32s} {'VALU':>6s} {'SALU':>6s} {'LDS':>5s} {'VMEM':>5s} {'wait':>5s}   (per stereo frame, mean of the two unrolled bodies)")
+    print(f"{'phase':32s} {'VALU':>6s} {'SALU':>6s} {'LDS':>5s} {'VMEM':>5s} {'wait':>5s}   (per stereo frame, {bodies} frame bod{'y' if bodies == 1 else 'ies'})")
     tot = collections.Counter()
     for ph in order:
         c = phases[ph]
         nm = names.get(ph, ph)
-        div = 1 if ph.startswith("pre (") else 2
+        once = ph.startswith(("pre (", "post ("))
+        div = 1 if once else bodies
         row = {k: c[k] / div for k in ("valu", "salu", "lds", "vmem", "wait")}
-        if not ph.startswith("pre ("):
+        if not once:
             for k, v in row.items():
                 tot[k] += v
         print(f"{nm:32s} {row['valu']:6.0f} {row['salu']:6.0f} {row['lds']:5.0f} {row['vmem']:5.0f} {row['wait']:5.0f}")
