@@ -22,7 +22,7 @@ struct TableSet {
     void *blob = nullptr;  // one device allocation holding every table
     LossyDevTables dev{};
     const float *dev_window = nullptr;  // [2048], decode side
-    const StatMasks *dev_masks = nullptr;  // host.masks on the device (the lock-step stereo chain form's band statistics)
+    const StatMasks *dev_masks = nullptr;  // host.masks on the device (the lock-step stereo chain form's band statistics and bands' hearing floors)
 };
 
 struct ProfRec {

@@ -1358,12 +1358,13 @@ __device__ __forceinline__ void quantise_2(const int lane, const v2f (&c)[16], c
 // truncating conversion, same comparison - so the integers are identical. xd[ch][k] = the i16 of the two positions (even
 // position in the low half): the dword sparse_block_pack takes, no re-dealing.
 typedef float v4f __attribute__((ext_vector_type(4)));
-// alive: bit b set when band b of either channel holds a coefficient above its masking amplitude (the transform wave's
-// ballot of band maximum > threshold); blk[k]: the bands block k has bins of. A block none of whose bands is alive keeps
-// nothing - the keep test is |c| > max(band threshold, ATH) - and is not quantised at all: its dwords are zero.
+// visit (uniform, in a scalar register): bit k set when block k holds bins of a band that is alive, that is whose maximum,
+// in either channel, is above its masking amplitude and above the smallest ATH amplitude of its bins (the transform wave's
+// ballot). A block none of whose bands is alive keeps nothing - the keep test is |c| > max(band threshold, ATH) - and is
+// not visited at all: a scalar bit test, no gathers, no arithmetic, its dwords are zero. The packers skip it on the same bit.
 template <int TSOFF>
 __device__ __forceinline__ void quantise_nat(const v4f (&cf)[8], const uint32_t (&ts_a)[16], const float (&athn)[16],
-                                             const uint32_t alive, const uint32_t (&blk)[8], uint32_t (&xd)[2][8]) {
+                                             const uint32_t visit, uint32_t (&xd)[2][8]) {
     typedef __attribute__((address_space(3))) v4f lds_f4;
     const uint32_t sgn_mask = 0x7FFFFFFFu;
     uint32_t phalf = 0x3EFFFFFFu;
@@ -1399,15 +1400,26 @@ __device__ __forceinline__ void quantise_nat(const v4f (&cf)[8], const uint32_t 
         out0 = r[0];
         out1 = r[1];
     };
+    // (two opaque copies of the mask, one for the gathers and one for the arithmetic: each test is then a scalar bit test in
+    // front of its branch; a condition shared by two branches is kept as a lane mask and re-tested with vector instructions)
+    uint32_t va = visit, vb = visit;
+    asm volatile("" : "+s"(va));
+    asm volatile("" : "+s"(vb));
 #pragma unroll
-    for (int g = 0; g < 4; g++) {   // two blocks, four gathers in flight
+    for (int g = 0; g < 4; g++) {   // two blocks: four gathers in flight where both are alive, a dead block's two are not issued
         uint32_t o00 = 0u, o01 = 0u, o10 = 0u, o11 = 0u;   // [block of the pair][channel]
-        if (alive & (blk[2 * g] | blk[2 * g + 1])) {   // uniform
+        if ((va >> (2 * g)) & 3u) {   // uniform, like every test here
             v4f tb[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) tb[j] = *reinterpret_cast<const lds_f4 *>((uintptr_t)(ts_a[4 * g + j] + (uint32_t)TSOFF));
-            if (alive & blk[2 * g]) block(2 * g, tb[0], tb[1], o00, o01);
-            if (alive & blk[2 * g + 1]) block(2 * g + 1, tb[2], tb[3], o10, o11);
+            if ((va >> (2 * g)) & 1u) {
+                tb[0] = *reinterpret_cast<const lds_f4 *>((uintptr_t)(ts_a[4 * g + 0] + (uint32_t)TSOFF));
+                tb[1] = *reinterpret_cast<const lds_f4 *>((uintptr_t)(ts_a[4 * g + 1] + (uint32_t)TSOFF));
+            }
+            if ((va >> (2 * g + 1)) & 1u) {
+                tb[2] = *reinterpret_cast<const lds_f4 *>((uintptr_t)(ts_a[4 * g + 2] + (uint32_t)TSOFF));
+                tb[3] = *reinterpret_cast<const lds_f4 *>((uintptr_t)(ts_a[4 * g + 3] + (uint32_t)TSOFF));
+            }
+            if ((vb >> (2 * g)) & 1u) block(2 * g, tb[0], tb[1], o00, o01);
+            if ((vb >> (2 * g + 1)) & 1u) block(2 * g + 1, tb[2], tb[3], o10, o11);
         }
         xd[0][2 * g] = o00, xd[1][2 * g] = o01;
         xd[0][2 * g + 1] = o10, xd[1][2 * g + 1] = o11;
@@ -1642,13 +1654,21 @@ __device__ __forceinline__ uint32_t mbcnt64(unsigned long long m) {
 // Cost per non-empty block is independent of how many non-zeros it holds: dense frames cost what sparse ones do.
 // Not handled (the caller takes the general form, which rewrites the blob): more runs than the run table holds, a
 // non-zero run longer than 255 (continuation records).
-__device__ __forceinline__ uint32_t sparse_block_pack(const int lane, const uint32_t (&xd)[8], const uint32_t blob, const uint32_t tab) {
+// visited (uniform): bit k clear = the caller knows block k to be 128 zeros (a block quantise_nat did not visit); such a
+// block costs one scalar bit test and no ballots. Callers that know nothing pass nothing.
+__device__ __forceinline__ uint32_t sparse_block_pack(const int lane, const uint32_t (&xd)[8], const uint32_t blob, const uint32_t tab,
+                                                      const uint32_t visited = 0xFFu) {
     uint32_t nM = 0, nS = 0, W = 0, cz = 0;   // non-zeros, run starts, wide records so far; zeros since the last non-zero
     unsigned long long carry = 0;              // bit 0: the position in front of the block is a non-zero
     const uint32_t tmax = tab + 4u * (uint32_t)(kRunTabEntries - 1);
     const uint32_t pos_l = (uint32_t)(2 * lane);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
+        if (!((visited >> k) & 1u)) {   // uniform: 128 zeros, known without looking
+            cz += 128u;
+            carry = 0;
+            continue;
+        }
         // ballots of the even (low halfword) and odd (high halfword) positions: a 16-bit compare reads the low half only
         unsigned long long E;
         asm("v_cmp_ne_u16_e64 %0, 0, %1" : "=s"(E) : "v"(xd[k]));
@@ -1779,11 +1799,12 @@ __device__ __forceinline__ uint32_t sparse_block_pack(const int lane, const uint
 //      table "first item of record r" the starting lanes fill. No loop over positions, blocks or records.
 // Up to kItemCap non-zeros (more: kSparseFallback, nothing usable written - the caller takes the block form); a run of
 // non-zeros therefore never reaches 255 and no continuation records exist here.
-// tabp: LDS byte address of kPackTabDwords dwords (item list, then the record table).
+// tabp: LDS byte address of kPackTabDwords dwords (item list, then the record table). visited: as in sparse_block_pack.
 constexpr int kItemCap = 128;
 constexpr int kItemTbl = 136;          // dword offset of the record table inside the area
 constexpr int kPackTabDwords = 272;
-__device__ __forceinline__ uint32_t sparse_item_pack(const int lane, const uint32_t (&xd)[8], const uint32_t blob, const uint32_t tabp) {
+__device__ __forceinline__ uint32_t sparse_item_pack(const int lane, const uint32_t (&xd)[8], const uint32_t blob, const uint32_t tabp,
+                                                     const uint32_t visited = 0xFFu) {
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
     const uint32_t list1 = tabp + 4u;   // item r at list1 + 4 r
     const uint32_t pk0 = (uint32_t)(2 * lane + 1) << 16;   // (position + 1) << 16 of the lane's even position in block 0
@@ -1791,6 +1812,7 @@ __device__ __forceinline__ uint32_t sparse_item_pack(const int lane, const uint3
     uint32_t nM = 0;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
+        if (!((visited >> k) & 1u)) continue;   // uniform: 128 zeros, known without looking
         unsigned long long E;
         asm("v_cmp_ne_u16_e64 %0, 0, %1" : "=s"(E) : "v"(xd[k]));
         const unsigned long long O = __ballot(xd[k] > 0xFFFFu);

@@ -448,7 +448,8 @@ struct Clip2qLds {
     float4 ts[2][32];            // [frame parity][band]: amplitude thresholds (left, right), scale factors (left, right)
     __attribute__((aligned(16))) uint8_t stage[kFrameCap + 64 + 256];
     uint16_t sfwh[2][2][32];     // [frame parity][channel][band] scale words
-    uint32_t alive[2][2];        // [frame parity][channel]: bit b = band b holds a coefficient above its masking amplitude
+    uint32_t alive[2][2];        // [frame parity][channel]: bit b = band b's maximum is above its masking amplitude and above the
+                                 // smallest ATH amplitude of its bins (StatMasks::band_ath_floor): clear = the band keeps nothing
     uint32_t pad2[4];
     uint32_t packtab[kPackTabDwords];     // item list + record table of the item-form packer / run table of the block form
     uint32_t coef_ready;         // frames whose coefficients are in coef2
@@ -590,7 +591,10 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
                 ts_a[4 * q + 2] = ts0 + __float_as_uint(b4.z), ts_a[4 * q + 3] = ts0 + __float_as_uint(b4.w);
             }
         }
-        const uint32_t *const blk_g = reinterpret_cast<const uint32_t *>(A.T.pack + kRowBlk * 64);
+        // bands present in each block of 128 positions (row kRowBlk), block (lane & 7)'s on every lane: one register for the
+        // launch. One ballot of it against a frame's alive bands gives, in a scalar register, the blocks the frame visits
+        uint32_t blk_l = reinterpret_cast<const uint32_t *>(A.T.pack + kRowBlk * 64)[lane & 7];
+        asm volatile("" : "+v"(blk_l));
         // the lane's 16 bytes of block k of the coefficient buffer: element 144 k + 2 lane + 2 (lane >> 3)
         const uint32_t cf_a = (uint32_t)(uintptr_t)cs.u.coef2 + 16u * (uint32_t)lane + 16u * ((uint32_t)lane >> 3);
         uint8_t *const stage = cs.stage;
@@ -637,15 +641,6 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
                         have = true;
                     }
                 };
-                // bands present in each block of 128 positions: eight scalars fetched per frame (one s_load, answered by the
-                // scalar cache while this wave waits for its partner) rather than held across the packer's scalar-heavy code
-                uint32_t blk[8];
-                {
-                    const uint32_t *bp = blk_g;
-                    asm volatile("" : "+s"(bp));
-#pragma unroll
-                    for (int q = 0; q < 8; q++) blk[q] = bp[q];
-                }
                 if (!have) {
                     wait_counter(&cs.coef_ready, g + 1);
 #pragma unroll
@@ -662,12 +657,19 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
                 const uint32_t sfw_both = cs.sfwh[par][ln >> 5][ln & 31];   // scale words: lanes 0..24 left, 32..56 right
                 const uint32_t alive = (uint32_t)__builtin_amdgcn_readfirstlane((int)(cs.alive[par][0] | cs.alive[par][1]));
                 uint32_t xd[2][8];   // xd[ch][k] = positions 128 k + 2 lane (low half) and + 1
+                // the blocks the quantiser visits, bit k = block k (lanes k, k + 8, .. vote alike: the low eight bits say it all).
+                // The others are zeros, which the packers take on trust
 #if (FLO_SKIP & 64) == 0
-                if (par) quantise_nat<512>(cf, ts_a, athn, alive, blk, xd);
-                else quantise_nat<0>(cf, ts_a, athn, alive, blk, xd);
+                const uint32_t visited = (uint32_t)__ballot((alive & blk_l) != 0u) & 0xFFu;
+                if (par) quantise_nat<512>(cf, ts_a, athn, visited, xd);
+                else quantise_nat<0>(cf, ts_a, athn, visited, xd);
 #else
+                const uint32_t visited = 0xFFu;
 #pragma unroll
-                for (int q = 0; q < 8; q++) { xd[0][q] = __float_as_uint(cf[q].x) & alive & 0x00010001u; xd[1][q] = __float_as_uint(cf[q].y) & blk[q] & 0x00010001u; }
+                for (int q = 0; q < 8; q++) { xd[0][q] = __float_as_uint(cf[q].x) & alive & 0x00010001u; xd[1][q] = __float_as_uint(cf[q].y) & blk_l & 0x00010001u; }
+#endif
+#ifdef FLO_STAMPS
+                st_sum[7] += (unsigned long long)__builtin_popcount(visited);   // blocks quantised
 #endif
                 have = false;   // cf is free again
                 take_next();
@@ -696,11 +698,11 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
 #pragma unroll
                 for (int ch = 0; ch < 2; ch++) {
 #if (FLO_SKIP & 32) == 0
-                    uint32_t t = sparse_item_pack(ln, xd[ch], f_a + pos + 4u, tab_a);
+                    uint32_t t = sparse_item_pack(ln, xd[ch], f_a + pos + 4u, tab_a, visited);
 #ifdef FLO_STAMPS
                     if (t == kSparseFallback) st_sum[6] += 1;   // channel-frames the item form declined
 #endif
-                    if (t == kSparseFallback) t = sparse_block_pack(ln, xd[ch], f_a + pos + 4u, tab_a);
+                    if (t == kSparseFallback) t = sparse_block_pack(ln, xd[ch], f_a + pos + 4u, tab_a, visited);
 #else
                     uint32_t t = 3u + ((xd[ch][0] | xd[ch][3]) & 1u);
                     FLO_KEEP(xd[ch][1]); FLO_KEEP(xd[ch][2]); FLO_KEEP(xd[ch][4]); FLO_KEEP(xd[ch][5]); FLO_KEEP(xd[ch][6]); FLO_KEEP(xd[ch][7]);
@@ -791,6 +793,10 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
     band_stats_2_prepare(lane, cs.slot, A.T.pack, so_pre, slot_first);
     unsigned long long close[16];
     band_stats_2_masks<DIRTY>(masks, close);
+    // band (lane & 31)'s hearing floor, the smallest ATH amplitude of its bins (+inf on lanes 25..31 and 57..63): one
+    // register for the launch, read by mask_publish's ballot
+    float ath_floor = masks->band_ath_floor[lane & 31];
+    asm volatile("" : "+v"(ath_floor));
     // the rotation twiddles of the fold and of the post-rotation: per-lane constants of the launch, held in registers
     v4f tw[4];
     if (!COEFFS) {
@@ -842,8 +848,11 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
             const float bm = bmax1, tl1 = energy1 * 1e-3f + rcount + sd0.x + sd1.y, sfv1 = bm * 100.f + 1.f;
             const uint32_t sfw1 = __float_as_uint(tl1) >> 16;
 #endif
-            // bands with anything above their masking amplitude: channel 0's on bits 0..24, channel 1's on bits 32..56
-            const unsigned long long al = __ballot(bnd < 25 && bm > tl1);
+            // bands that can keep anything: channel 0's on bits 0..24, channel 1's on bits 32..56. A kept coefficient is above
+            // max(masking amplitude, its bin's ATH amplitude), so the band's maximum is above both the masking amplitude and the
+            // band's smallest ATH amplitude. Two compares, not one against the maximum of the two: a NaN masking amplitude
+            // compares false and leaves the band dead, a maximum would drop the NaN
+            const unsigned long long al = __ballot(bnd < 25 && bm > tl1 && bm > ath_floor);
             if (bnd < 25) {
                 typedef __attribute__((address_space(3))) float lds_f32;
                 const uint32_t ts_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)cs.ts[gp & 1u]);

@@ -35,5 +35,10 @@ struct StatMasks {
     unsigned long long close[16];   // bit l of close[e]: lane l closes a band segment behind element e (its kRowKeep value there is 0.0)
     unsigned long long gather[3];   // bit l of gather[g]: lane l's slot list (kRowLst) has more than 4 g entries. No kernel
                                     // reads these: gathers masked by them measured no faster (diag/exp_gather_masks.patch)
+    // Not a lane mask, but fetched the same way (once per launch, by the transform wave, lane l taking entry l & 31):
+    // the smallest ATH amplitude threshold (ath_lin) over band b's bins; +inf for a band without bins and for entries
+    // 25..31. A band whose maximum is not above it keeps nothing whatever its masking amplitude says (the keep test is
+    // |c| > max(masking amplitude, ath_lin[k])), so its ballot bit in Clip2qLds::alive stays clear.
+    float band_ath_floor[32];
 };
 }  // namespace flo

@@ -239,6 +239,12 @@ void build_lossy_tables(uint32_t sample_rate, float quality, LossyTablesHost &t)
         for (int g = 0; g < 3; g++)
             if (n > 4u * (uint32_t)g) t.masks.gather[g] |= 1ull << lane;
     }
+    // the hearing floor of each band: the smallest ATH amplitude threshold among its bins (+inf: no bins, no such band)
+    for (int b = 0; b < 32; b++) t.masks.band_ath_floor[b] = INFINITY;
+    for (int k = 0; k < kHop; k++) {
+        float &f = t.masks.band_ath_floor[t.band[k]];
+        if (t.ath_lin[k] < f) f = t.ath_lin[k];
+    }
     uint32_t nonzero = 0;
     for (int e = 0; e < 16; e++) nonzero |= (t.masks.close[e] != 0) << e;
     t.masks_ok = nonzero == t.dirty && t.masks.close[15] == ~0ull && t.n_slots <= kSlotCapHost;

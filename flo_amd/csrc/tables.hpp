@@ -43,7 +43,8 @@ struct LossyTablesHost {
     int max_band_slots = 0;            // max over bands of slot count
     uint32_t dirty = 0;                // OR of lane_bnd over the lanes: element positions at which some lane closes a segment
     int n_slots = 0;
-    StatMasks masks = {};              // rows kRowKeep / kRowLst as lane masks (pack_rows.h); lane_slot0 is each lane's first slot
+    StatMasks masks = {};              // rows kRowKeep / kRowLst as lane masks (pack_rows.h); lane_slot0 is each lane's first slot;
+                                       // and band_ath_floor[32], the minimum of ath_lin over each band's bins
     bool masks_ok = false;             // dirty == {e : masks.close[e] != 0}, every lane closes behind element 15, the slots fit
 };
 
