@@ -2,7 +2,13 @@
 // arithmetic of resample_plan.hpp that the kernel shares): where every output lies, how many a clip has, that the tiles of a
 // batch make every output exactly once and nothing else, and that what a tile stages fits the LDS the kernel may take.
 // Prints "ok <checks>" and returns 0, or names the first case that fails.
+// With the argument "dump" it reads lines "in_rate out_rate n_in ..." from stdin and prints, per line, the plan's fields and
+// "n_out:tiles" of every clip length, or "rejected: <message>" (tests/test_resample_model_cpu.py compares them with
+// tests/resample_model.py). With the argument "check" it reads rate pairs from stdin and runs the geometry, count and table
+// checks below on each (every pair must be a supported one), then prints "ok <checks>".
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -161,7 +167,55 @@ static bool check_table(const ResamplePlan &P) {
     return true;
 }
 
-int main() {
+// one line of stdin per rate pair: "in_rate out_rate n_in n_in ..."
+static int dump() {
+    char *line = nullptr;
+    size_t cap = 0;
+    while (getline(&line, &cap, stdin) > 0) {
+        char *s = line;
+        const unsigned long long a = strtoull(s, &s, 10), b = strtoull(s, &s, 10);
+        ResamplePlan P;
+        std::string err;
+        if (a > 0xFFFFFFFFull || b > 0xFFFFFFFFull || !resample_plan((uint32_t)a, (uint32_t)b, P, err)) {
+            printf("rejected: %s\n", err.c_str());
+            continue;
+        }
+        printf("%u %u %u %u %u %u %u %u %u %u %u %u %u |", P.L, P.M, P.taps, P.shift, P.slots, P.lanes_per_phase, P.phases_per_wave, P.chunks,
+               P.block, P.units, P.span, P.lds_elems, P.tile_outputs);
+        std::vector<uint64_t> n_out;
+        for (;;) {
+            char *end;
+            const unsigned long long n_in = strtoull(s, &end, 10);
+            if (end == s) break;
+            s = end;
+            uint64_t n = 0;
+            if (!resample_out_frames(P, n_in, n)) return fprintf(stderr, "out_frames(%llu)\n", n_in), 1;
+            n_out.push_back(n);
+        }
+        std::vector<uint32_t> pre;
+        if (!resample_tiles(P, n_out.data(), n_out.size(), pre)) return fprintf(stderr, "tiles\n"), 1;
+        for (size_t i = 0; i < n_out.size(); i++) printf(" %llu:%u", (unsigned long long)n_out[i], pre[i + 1] - pre[i]);
+        printf("\n");
+    }
+    free(line);
+    return 0;
+}
+
+static int check_pairs() {
+    unsigned a, b;
+    while (scanf("%u %u", &a, &b) == 2) {
+        ResamplePlan P;
+        std::string err;
+        if (!resample_plan(a, b, P, err)) return fprintf(stderr, "%u -> %u: %s\n", a, b, err.c_str()), 1;
+        if (!check_out_frames(P) || !check_geometry(P) || !check_table(P)) return 1;
+    }
+    printf("ok %d\n", g_checks);
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "dump")) return dump();
+    if (argc > 1 && !strcmp(argv[1], "check")) return check_pairs();
     if (!check_pos()) return 1;
     const uint32_t pairs[][2] = {{48000, 44100}, {44100, 48000}, {96000, 44100}, {8000, 44100}, {44100, 8000}, {44100, 22050},
                                  {22050, 44100}, {48000, 48000}, {44100, 44101}, {384000, 8000}};
