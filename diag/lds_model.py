@@ -24,13 +24,15 @@ A lane group none of whose lanes is enabled is still charged its cycle (the coun
 The packer wave's LDS work depends on the data (non-zeros per frame, fall-back forms); it is not modelled here: the
 counters' per-frame totals minus this model's transform-wave totals are the packer's share.
 
-  python3 diag/lds_model.py [--rate 44100] [--layout old|new|masks|carry] [--isa lossy_kernels-hip-amdgcn-amd-amdhsa-gfx950.s]
+  python3 diag/lds_model.py [--rate 44100] [--layout old|new|masks|carry|fftrows] [--isa lossy_kernels-hip-amdgcn-amd-amdhsa-gfx950.s]
 --layout old: the pack rows as the compiler read them before pack_row() (dword pieces, read2_b64, kRowLane's rcount);
 --layout new: whole-row reads, rcount from row kRowS10;
 --layout masks: new, with the band statistics by lane masks (band_stats_2<., true, true>): no keep / dst rows, one
   ds_write2_b64 per dirty position below 15 that carries the closing lanes only, the last store as it was.
 --layout carry: masks, with the rotation twiddles (rows kRowTw) in registers for the launch: the fold and the
-  post-rotation read no twiddle row (fold_carry_2, post_rotate_transpose_2_tw); the shipped layout.
+  post-rotation read no twiddle row (fold_carry_2, post_rotate_transpose_2_tw).
+--layout fftrows: carry, with the FFT's twiddles (rows kRowF1 / kRowF2) in registers for the launch too: the FFT reads no
+  constant row (fft512_2_tw); the shipped layout.
   --gather-masks: the three gather groups under their list-length masks too (diag/exp_gather_masks.patch).
   --skip-empty charges nothing for a lane group with no enabled lane (the other reading of the hardware; the counters
   say it is the wrong one: DESIGN.md §6).
@@ -152,6 +154,8 @@ def sites(rate, layout):
     else:
         S += [("frame", "rcount: kRowS10 dword 64 + lane", "ds_read_b32", lanes(lambda l: R_S10 * ROW + 256 + 4 * l))]
     for ph, rr in (("fft pass 1", R_F1), ("fft pass 2", R_F2)):
+        if layout == "fftrows":   # (the eight kRowF1 / kRowF2 rows stay in registers for the launch: fft512_2_tw)
+            continue
         S += [(ph, "twiddle rows", "ds_read_b128", row(rr + k)) for k in range(3)]
         S += [(ph, "twiddle row 4 (.xy)", "ds_read_b64", row(rr + 3))]
     X = 0x10000   # clip block (the offset of an instruction's common base does not change its banks)
@@ -174,7 +178,7 @@ def sites(rate, layout):
         if layout == "old" or r % 2 == 0:
             if layout == "old":
                 S += [("post-rotation", "twiddle rows (half rows)", "ds_read_b64", row(R_TW + r // 2, 8 * (r & 1)))]
-            elif layout != "carry":   # (carry: the four kRowTw rows stay in registers for the launch)
+            elif layout not in ("carry", "fftrows"):   # (carry: the four kRowTw rows stay in registers for the launch)
                 S += [("post-rotation", "twiddle rows", "ds_read_b128", row(R_TW + r // 2))]
         S += [("post-rotation", "transpose writes (2m)", "ds_write_b64", lanes(lambda l: X + 8 * (pl(l) + 144 * r)))]
         S += [("post-rotation", "transpose writes (1023-2m)", "ds_write_b64", lanes(lambda l: X + 8 * (1149 - pl(l) - 144 * r)))]
@@ -201,7 +205,7 @@ def sites(rate, layout):
     elif layout == "new":
         S += [("band statistics", "keep / dst rows (whole rows)", "ds_read_b128", row(rr + g)) for rr in (R_KEEP, R_DST) for g in range(4)]
     SL = X + 9216
-    masks = layout in ("masks", "carry")
+    masks = layout in ("masks", "carry", "fftrows")
     for e in es:
         def dst(l, e=e, off=0):
             m = lane_bnd[l]
@@ -230,7 +234,7 @@ def sites(rate, layout):
     if layout == "old":
         for k in range(4):
             S += [("fold", "twiddle rows (read2_b64)", "ds_read2_b64", [row(R_TW + k), row(R_TW + k, 8)])]
-    elif layout != "carry":
+    elif layout not in ("carry", "fftrows"):
         S += [("fold", "twiddle rows", "ds_read_b128", row(R_TW + k)) for k in range(4)]
     return S
 
@@ -259,7 +263,7 @@ def isa_mix(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rate", type=int, default=44100)
-    ap.add_argument("--layout", default="old", choices=["old", "new", "masks", "carry"])
+    ap.add_argument("--layout", default="old", choices=["old", "new", "masks", "carry", "fftrows"])
     ap.add_argument("--skip-empty", action="store_true")
     ap.add_argument("--gather-masks", action="store_true")
     ap.add_argument("--isa")

@@ -614,6 +614,62 @@ __device__ __forceinline__ void fft512_2(const int lane, v2f (&zr)[8], v2f (&zi)
     dft8_2(zr, zi);
 }
 
+// cmul_2 / cmul_2_pair with the twiddle (wr, wi) as one pair of a row that stays in registers across frames: both multipliers
+// are named by op_sel inside the instruction (see mul2_lo), the operations, operands and order per component are cmul_2's
+__device__ __forceinline__ void cmul_2_tw(v2f &xr, v2f &xi, v2f w) {
+    const v2f r = fma2_a_lo_nc(xr, w, mul2_hi(xi, w));   // xr wr - xi wi
+    const v2f i = fma2_a_hi_c(xr, w, mul2_lo(xi, w));    // xr wi + xi wr
+    xr = r;
+    xi = i;
+}
+// fft512_2 in the chain form (lossy_chain2q_kernel): the twiddle rows handed in, f1[kk] = row kRowF1 + kk and f2[kk] = row
+// kRowF2 + kk of the pack as the lane reads them, loaded once per launch by the caller. No constant row is read in here;
+// (zr, zi) are bit-identical to fft512_2's.
+template <typename F = NoShadow>
+__device__ __forceinline__ void fft512_2_tw(const int lane, v2f (&zr)[8], v2f (&zi)[8], float4 *x4, const v4f (&f1)[4],
+                                            const v4f (&f2)[4], F &&shadow = F()) {
+    dft8_2(zr, zi);
+#pragma unroll
+    for (int kk = 0; kk < 4; kk++) {
+        cmul_2_tw(zr[2 * kk + 1], zi[2 * kk + 1], f1[kk].xy);
+        if (kk < 3) cmul_2_tw(zr[2 * kk + 2], zi[2 * kk + 2], f1[kk].zw);
+    }
+    {
+        const int nb = lane >> 3, nc = lane & 7;
+#pragma unroll
+        for (int ka = 0; ka < 8; ka++) x4[(8 * ka + nc) * kXchStride + nb] = make_float4(zr[ka].x, zr[ka].y, zi[ka].x, zi[ka].y);
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const float4 v = x4[lane * kXchStride + r];
+            zr[r] = (v2f){v.x, v.y};
+            zi[r] = (v2f){v.z, v.w};
+        }
+        shadow();
+        wave_sync();
+    }
+    dft8_2(zr, zi);
+#pragma unroll
+    for (int kk = 0; kk < 4; kk++) {
+        cmul_2_tw(zr[2 * kk + 1], zi[2 * kk + 1], f2[kk].xy);
+        if (kk < 3) cmul_2_tw(zr[2 * kk + 2], zi[2 * kk + 2], f2[kk].zw);
+    }
+    {
+        const int ka = lane >> 3, nc = lane & 7;
+#pragma unroll
+        for (int kb = 0; kb < 8; kb++) x4[(ka + 8 * kb) * kXchStride + nc] = make_float4(zr[kb].x, zr[kb].y, zi[kb].x, zi[kb].y);
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const float4 v = x4[lane * kXchStride + r];
+            zr[r] = (v2f){v.x, v.y};
+            zi[r] = (v2f){v.z, v.w};
+        }
+        wave_sync();
+    }
+    dft8_2(zr, zi);
+}
+
 // half-frame of a stereo clip as float2 loads: he[r] / ho[r] = (left, right) of the lane's even / odd sample of row r
 // Byte offsets (half_offsets x 8): rows r < 4 even 4096 + 16 lane + 1024 r, odd 4088 - 16 lane - 1024 r; rows r >= 4 even
 // 16 lane + 1024 (r - 4), odd 8184 - 16 lane - 1024 (r - 4). With va = 16 lane and vb = 16 (63 - lane) every load is

@@ -799,9 +799,16 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
     asm volatile("" : "+v"(ath_floor));
     // the rotation twiddles of the fold and of the post-rotation: per-lane constants of the launch, held in registers
     v4f tw[4];
+    // ... and the FFT's: rows kRowF1 + 0..3 and kRowF2 + 0..3 as fft512_2 reads them (fft512_2_tw). They live in the registers
+    // that hold the half-frame in flight outside the FFT: the prefetch is issued behind it
+    v4f f1[4], f2[4];
     if (!COEFFS) {
 #pragma unroll
         for (int k = 0; k < 4; k++) tw[k] = pack_row_v(&T.pack[(kRowTw + k) * 64 + lane]);
+#pragma unroll
+        for (int k = 0; k < 4; k++) f1[k] = pack_row_v(&T.pack[(kRowF1 + k) * 64 + lane]);
+#pragma unroll
+        for (int k = 0; k < 4; k++) f2[k] = pack_row_v(&T.pack[(kRowF2 + k) * 64 + lane]);
     }
     for (;;) {
         wait_counter(&cs.clip_seq, ++seq);
@@ -822,7 +829,7 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
         STAMPS_BEGIN();
         // The frame loop is software-pipelined by two phases. (1) The fold of frame h + 1, which only needs PCM that is already
         // in registers, runs at the end of frame h: entering frame h, (zr, zi) hold its folded input, and the half-frame
-        // after next is loaded at the TOP of the frame into the registers the last fold freed. (2) The masking pass of
+        // after next is loaded BEHIND the frame's FFT into the registers the last fold freed. (2) The masking pass of
         // frame h - one long dependent chain on 50 lanes (logarithm, DPP maxima, exponential, division), 6.6 % of the launch
         // when it runs by itself - is deferred into frame h + 1's FFT, behind the issue of the first exchange's reads: it
         // fills the LDS round trip the wave would otherwise sit out (a wave issues in order). The packer learns a frame's
@@ -894,15 +901,11 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
                 for (int q = 0; q < 8; q++) p[q] = make_float4(c[2 * q].x, c[2 * q].y, c[2 * q + 1].x, c[2 * q + 1].y);
                 wave_sync();
             } else {
-                // the half-frame after next, into the registers the last fold freed; consumed at the end of this frame.
-                // Unconditional, also behind the last frame (the batch allocates one spare half-frame per clip)
-                load_half_fast_2(ln, pcm, (long long)(h + 1) * 1024, ne, no);
-                FLO_MARK("prefetch_done");
                 STAMP(1);
                 if ((uint32_t)__builtin_amdgcn_readfirstlane((int)consumed_early) < g) wait_counter(&cs.consumed, g);
                 STAMP(7);
 #if (FLO_SKIP & 8) == 0
-                fft512_2(ln, zr, zi, cs.u.xch4, T, [&]() __attribute__((always_inline)) {
+                fft512_2_tw(ln, zr, zi, cs.u.xch4, f1, f2, [&]() __attribute__((always_inline)) {
                     if (h > 0) mask_publish(ln, g - 1u, h - 1u, pend_e, pend_m, rcount, sd0, sd1);   // uniform
                 });
 #else
@@ -910,6 +913,12 @@ __global__ __launch_bounds__(FLO_C2X_THREADS) void lossy_chain2q_kernel(LossyArg
 #endif
                 FLO_MARK("fft_done");
                 STAMP(2);
+                // the half-frame after next, into the registers the last fold freed: issued behind the FFT, so that (ne, no) are
+                // dead across it (its registers hold the FFT's twiddle rows there), and consumed at the end of this frame - the
+                // post-rotation and the band statistics are what answers the loads. Unconditional, also behind the last frame
+                // (the batch allocates one spare half-frame per clip)
+                load_half_fast_2(ln, pcm, (long long)(h + 1) * 1024, ne, no);
+                FLO_MARK("prefetch_done");
 #if (FLO_SKIP & 4) == 0
                 post_rotate_transpose_2_tw(ln, zr, zi, cs.u.coef2, c, tw);
 #else

@@ -1,6 +1,7 @@
 // pack_rows.h — row numbers of the per-lane constant pack (float4[row][64]; see LossyDevTables in lossy_device.hpp).
 // Shared by the host builder (tables.cpp, plain C++) and the device code. The rows are ordered by who reads them:
 //   rows below kPackRowsHotT : what the transform wave of lossy_chain2q_kernel reads every frame (its LDS copy);
+//                              kRowTw, kRowF1 and kRowF2 it reads from that copy once per launch, into registers;
 //   rows below kPackRowsHot  : plus the quantiser rows of the forms whose transform wave also quantises;
 //   the rows behind them are read from global memory by the few tables / kernels that need them.
 #pragma once

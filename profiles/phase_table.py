@@ -6,7 +6,8 @@
   python3 profiles/phase_table.py /tmp/lk_marks.s [mangled-name-substring]
 
 The markers pin the schedule (they are memory clobbers), so the counts are those of the marked build, a few per cent
-above the shipped one. Counted per stereo frame: the counts of a phase are divided by the number of frame bodies in
+above the shipped one. A frame loop the compiler laid out rotated (latch in front of the header) is recognised and
+counted in program order. Counted per stereo frame: the counts of a phase are divided by the number of frame bodies in
 the listing (one; two while the loop was unrolled by two). What follows the last frame_end marker runs once per clip,
 not per frame (the loop's back edge, the last frame's masking pass, the clip loop): it is listed apart and not summed.
 """
@@ -42,8 +43,28 @@ def main():
     order = []
     bodies = max(1, sum(1 for l in lines[start:end] if l.strip().startswith("; MARK frame_begin")))
     last_end = max((i for i in range(start, end) if lines[i].strip().startswith("; MARK frame_end")), default=end)
+    # A rotated frame loop (the compiler lays the latch - the tail of the band statistics and the next frame's fold - out in
+    # front of the loop header, so frame_end precedes frame_begin in the listing): the loop's code runs from the latch's
+    # label to the label the latch leaves the loop for; between the latch's label and the first marker lies the end of the
+    # phase behind the LAST marker of the listing, and what follows the exit label runs once per clip.
+    marks = [(i, re.match(r"; MARK (\w+)", lines[i].strip()).group(1)) for i in range(start, end) if lines[i].strip().startswith("; MARK ")]
+    first = {n: min(i for i, m in marks if m == n) for n in {m for _, m in marks}}
+    rotated = "frame_end" in first and "frame_begin" in first and first["frame_end"] < first["frame_begin"]
+    loop_start = post_start = None
+    if rotated:
+        label_at = lambda i: max(j for j in range(start, i + 1) if re.match(r"\.LBB\d+_\d+:", lines[j]))
+        loop_start, header = label_at(marks[0][0]), label_at(first["frame_begin"])
+        leave = next(lines[j] for j in range(header - 1, loop_start, -1) if lines[j].strip().startswith("s_cbranch"))
+        exit_label = leave.split()[1]
+        post_start = next(j for j in range(start, end) if lines[j].startswith(exit_label + ":"))
+        assert post_start > marks[-1][0], "the loop's exit lies behind its last marker"
     for i, l in enumerate(lines[start:end], start):
-        if i == last_end + 1:
+        if rotated:
+            if i == loop_start:
+                cur = marks[-1][1]
+            elif i == post_start:
+                cur = "post (behind the frame loop)"
+        elif i == last_end + 1:
             cur = "post (behind the last frame_end)"
         s = l.strip()
         m = re.match(r"; MARK (\w+)", s)
@@ -60,13 +81,19 @@ def main():
         phases.setdefault(cur, collections.Counter())[k] += 1
         if cur not in order:
             order.append(cur)
+    if rotated:   # program order: the header's phase first, the latch's phases last
+        seq = [m for _, m in marks]
+        k = seq.index("frame_begin")
+        prog = seq[k:] + seq[:k]
+        order = [o for o in order if o.startswith("pre (")] + [m for m in prog if m in order] + [o for o in order if o.startswith("post (")]
     # instructions after marker X and before marker Y belong to phase Y
     # (round 4: the frame loop is software-pipelined - the next frame's fold runs at the end of a frame, the masking pass of the
     # previous frame inside the FFT, behind the first exchange)
     # what FOLLOWS each marker (round 4: the frame loop is software-pipelined - the next frame's fold runs at the end of a
     # frame, the masking pass of the previous frame inside the FFT, behind the first exchange)
-    names = {"frame_begin": "prefetch (16 loads), masking rows", "prefetch_done": "fft512 x2 + masking pass (prev. frame)",
-             "fft_done": "post-rotation + transpose", "postrot_done": "band_stats_2",
+    # (the prefetch is issued behind the FFT: frame_begin, fft_done, prefetch_done, postrot_done, ...)
+    names = {"frame_begin": "masking rows, fft512 x2 + masking pass (prev. frame)", "fft_done": "prefetch (16 loads)",
+             "prefetch_done": "post-rotation + transpose", "postrot_done": "band_stats_2",
              "bandstats_done": "fold of the next frame (a)", "frame_end": "fold of the next frame (b), loop"}
     print(f"{'phase':32s} {'VALU':>6s} {'SALU':>6s} {'LDS':>5s} {'VMEM':>5s} {'wait':>5s}   (per stereo frame, {bodies} frame bod{'y' if bodies == 1 else 'ies'})")
     tot = collections.Counter()
