@@ -16,3 +16,4 @@ from .api import resample, resample_filter, resample_many, resample_out_frames  
 from .api import (FINGERPRINT_DTYPE, FingerprintIndex, extract_dominant_frequencies, fingerprint_array,  # noqa: F401
                   fingerprints_from_files, spectral_similarity)
 from .api import FIDELITY_BLOCK_DTYPE, FIDELITY_DTYPE, compare, fidelity_dict  # noqa: F401
+from .api import debug_pool_fill  # noqa: F401

@@ -583,6 +583,15 @@ class Ladder:
             pass
 
 
+def debug_pool_fill(byte):
+    """Test hook (flo_debug_pool_fill): fill every pool block and pinned download buffer with `byte` (0 .. 255) as it is handed
+    out; None turns the fill off. Process-wide. Returns the previous setting (None: off)."""
+    if byte is not None and not 0 <= int(byte) <= 255:
+        raise ValueError("byte must be None or 0 .. 255")
+    prev = _native.lib().flo_debug_pool_fill(-1 if byte is None else int(byte))
+    return None if prev < 0 else prev
+
+
 _default_ctx = None
 
 

@@ -164,7 +164,10 @@ __global__ __launch_bounds__(256) void anb_peak_kernel(AN_BATCH_PARAMS) {
         const unsigned c = item / tiles, tile = item % tiles;
         const unsigned long long n_ch = A.n > c ? (A.n - c + ch - 1) / ch : 0;
         const unsigned long long t0 = (unsigned long long)tile * kAnTile;
-        if (t0 >= n_ch) continue;   // (uniform)
+        if (t0 >= n_ch) {           // (uniform) a shorter channel's empty last tile: the reduction reads every pair
+            if (tid < 2) A.peak_part[2ull * ((unsigned long long)c * tiles + tile) + tid] = 0.0;
+            continue;
+        }
         __syncthreads();            // (the previous tile's readers are done with xt and wmax)
         for (unsigned i = tid; i < kFirSpan; i += 256) {
             const long long f = (long long)t0 - kAnHalo + (long long)i;

@@ -321,7 +321,10 @@ __device__ __forceinline__ void an_peak_body(const AnalysisArgs &A, unsigned til
     const unsigned long long frames = A.n / ch;
     const unsigned long long n_ch = A.n > c ? (A.n - c + ch - 1) / ch : 0;
     const unsigned long long t0 = (unsigned long long)tile * kAnTile;
-    if (t0 >= n_ch) return;
+    if (t0 >= n_ch) {   // a shorter channel's empty last tile: the reduction reads every pair, and nothing clears them
+        if (tid < 2) A.peak_part[2ull * ((unsigned long long)c * tiles + tile) + tid] = 0.0;
+        return;
+    }
     if (tid < 49) taps[tid] = A.tp_coef[tid];
     for (unsigned i = tid; i < kAnTile + 2 * kAnHalo + 8; i += 256) {
         const long long f = (long long)t0 - kAnHalo + (long long)i;

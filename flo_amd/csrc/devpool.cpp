@@ -1,6 +1,8 @@
 // devpool.cpp — see devpool.hpp
 #include "devpool.hpp"
 
+#include "../../include/flo_hip.h"
+
 #include <map>
 #include <mutex>
 #include <unordered_map>
@@ -26,7 +28,15 @@ size_t size_class(size_t n) {
     const size_t step = p >> 3;
     return (n + step - 1) / step * step;
 }
+// The block is about to be handed out: nothing uses it yet (blocks come back only once their work has completed), and the
+// null-stream memset is over before any of the contexts' non-blocking streams can touch it.
+hipError_t debug_fill(void *p, size_t cls, int byte) {
+    hipError_t e = hipMemset(p, byte, cls);
+    return e != hipSuccess ? e : hipDeviceSynchronize();
+}
 }  // namespace
+
+std::atomic<int> g_pool_fill{-1};
 
 hipError_t pool_alloc(void **p, size_t bytes) {
     *p = nullptr;
@@ -41,8 +51,15 @@ hipError_t pool_alloc(void **p, size_t bytes) {
             *p = it->second.back();
             it->second.pop_back();
             g_cached -= cls;
-            return hipSuccess;
         }
+    }
+    const int fill = g_pool_fill.load(std::memory_order_relaxed);
+    if (*p) {
+        if (fill >= 0 && (e = debug_fill(*p, cls, fill)) != hipSuccess) {
+            pool_free(*p);
+            *p = nullptr;
+        }
+        return e;
     }
     e = hipMalloc(p, cls);
     if (e == hipErrorOutOfMemory) {   // give the cache back to the driver and try once more
@@ -50,9 +67,15 @@ hipError_t pool_alloc(void **p, size_t bytes) {
         e = hipMalloc(p, cls);
     }
     if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(g_mu);
-    g_live[*p] = Block{dev, cls};
-    return hipSuccess;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        g_live[*p] = Block{dev, cls};
+    }
+    if (fill >= 0 && (e = debug_fill(*p, cls, fill)) != hipSuccess) {
+        pool_free(*p);
+        *p = nullptr;
+    }
+    return e;
 }
 
 void pool_free(void *p) {
@@ -92,3 +115,8 @@ void pool_trim() {
 }
 
 }  // namespace flo
+
+extern "C" int flo_debug_pool_fill(int byte) {
+    if (byte < -1 || byte > 255) return flo::g_pool_fill.load(std::memory_order_relaxed);
+    return flo::g_pool_fill.exchange(byte, std::memory_order_relaxed);
+}

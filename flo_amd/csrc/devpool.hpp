@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include <atomic>
+
 namespace flo {
 
 constexpr size_t kMaxCachedBlock = (size_t)256 << 20;
@@ -18,6 +20,8 @@ constexpr size_t kMaxCachedTotal = (size_t)2 << 30;
 hipError_t pool_alloc(void **p, size_t bytes);   // on the current device
 void pool_free(void *p);                          // any device
 void pool_trim();                                 // release every cached block of every device (tests, shutdown)
+// flo_debug_pool_fill's setting: -1 off, 0 .. 255 the byte every block handed out (here and by stager_pinned_get) is set to
+extern std::atomic<int> g_pool_fill;
 template <class T>
 hipError_t pool_alloc(T **p, size_t bytes) { return pool_alloc(reinterpret_cast<void **>(p), bytes); }
 

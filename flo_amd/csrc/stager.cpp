@@ -1,6 +1,8 @@
 // stager.cpp — see stager.hpp
 #include "stager.hpp"
 
+#include "devpool.hpp"
+
 #include <cstdlib>
 
 #include <atomic>
@@ -139,9 +141,11 @@ void stager_destroy(Stager *s) {
 }
 
 void *stager_pinned_get(Stager *s, size_t bytes, std::string &err) {
+    const int fill = g_pool_fill.load(std::memory_order_relaxed);   // flo_debug_pool_fill
     for (auto &b : s->blocks)
         if (!b.in_use && b.cap >= bytes) {
             b.in_use = true;
+            if (fill >= 0) memset(b.p, fill, b.cap);
             return b.p;
         }
     Stager::PinBlock nb;
@@ -151,6 +155,7 @@ void *stager_pinned_get(Stager *s, size_t bytes, std::string &err) {
         return nullptr;
     }
     nb.in_use = true;
+    if (fill >= 0) memset(nb.p, fill, nb.cap);
     s->blocks.push_back(nb);
     return nb.p;
 }

@@ -604,6 +604,12 @@ int flo_ctx_profile_query(flo_ctx *ctx, const char *kernel, double *total_ms, ui
 int flo_ctx_profile_reset(flo_ctx *ctx);
 /* test hook: force the lossy kernel form (0 auto, 1 .. 5 as in flo_batch_encode) */
 int flo_ctx_force_path(flo_ctx *ctx, int which);
+/* test hook, process-wide: while byte is 0 .. 255 every block the device pool hands out (fresh or recycled) is set to that
+ * byte over its whole size class before it is returned (null-stream memset + device synchronise), and every recycled
+ * pinned download buffer over its capacity; -1 turns the fill off, which is the state at start. Returns the previous
+ * setting (any other argument changes nothing). Results never depend on it: every byte read is written first. Off,
+ * the allocation path pays one relaxed atomic load. */
+int flo_debug_pool_fill(int byte);
 /* stream handle (hipStream_t) of the context, for callers that enqueue their own work around the encode */
 void *flo_ctx_stream(flo_ctx *ctx);
 

@@ -212,6 +212,8 @@ def paths(g):
         tiles = ((n + ch - 1) // ch + TILE - 1) // TILE
         p.add("tiles=%s" % ("1" if tiles == 1 else "many"))
         p.add("last_tile=%s" % ("full" if ((n + ch - 1) // ch) % TILE == 0 else "part"))
+        # the tiles are counted from the longest channel: behind a partial frame a shorter channel may have none of the last
+        p.add("a_channels_last_tile_empty=%d" % int((frames + TILE - 1) // TILE < tiles))
     elif kp == "warmup":
         p.add("warmup_n_seg=%s" % ("2" if g["n_seg"] == 2 else "over_2"))
         p.add("warmup_seg_frames=%s" % ("65536" if g["seg_frames"] == EXACT_FRAMES else "8_hop"))
@@ -252,7 +254,8 @@ PATHS = {
                     "warmup_n_seg=2", "warmup_n_seg=over_2", "warmup_seg_frames=65536", "warmup_seg_frames=8_hop",
                     "one_walk=short", "one_walk=over_65536_frames", "one_walk=hop_0",
                     "ch=1", "ch=2", "ch=3_to_63", "ch=64", "ch=over_64", "partial_frame=0", "partial_frame=1"],
-    "peak tiles": ["tiles=1", "tiles=many", "last_tile=full", "last_tile=part"],
+    "peak tiles": ["tiles=1", "tiles=many", "last_tile=full", "last_tile=part", "a_channels_last_tile_empty=0",
+                   "a_channels_last_tile_empty=1"],
     "sum of squares": ["sumsq=one_segment", "sumsq=chain", "sq_chunks_mod64=0", "sq_chunks_mod64=1", "sq_chunks_mod64=other",
                        "sq_last_chunk=full", "sq_last_chunk=part"],
     "blake3": ["b3_chunks=%d" % c for c in list(range(1, 10)) + [127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025]] +
@@ -441,6 +444,10 @@ def cases():
         for at in (0, 5, 23, fr - 24, fr - 6, fr - 1):
             add(f"spike {path} frame {at}", "peak", sr, ch, fr * ch, (lambda fr=fr, ch=ch, at=at: _spike(fr, ch, at, at, 0)))
         add(f"spike {path} in the trailing partial frame", "peak", sr, ch, fr * ch + 1, (lambda fr=fr, ch=ch: _spike(fr, ch, 9, fr, 0, extra=1)))
+    # 33 x 2048 whole frames and channel 0's lone sample behind them: tile 33 exists for channel 0 alone, and the reduction reads
+    # channel 1's pair of it all the same
+    add("stereo, 33 tiles and one sample (the last tile of channel 1 is empty)", "peak", 44100, 2, 2 * 33 * TILE + 1,
+        lambda: _spike(33 * TILE, 2, 11, 33 * TILE, 0, extra=1))
     add("spike three channels, the last channel, partial frame behind", "peak", 22050, 3, 70000 * 3 + 2, lambda: _spike(70000, 3, 4, 34 * TILE, 2, extra=2))
     # sum of squares
     add("16-bit material 2.5 M samples", "sumsq", 44100, 2, 2_500_000, lambda: _pcm16(2_500_000, 1))
