@@ -13,6 +13,7 @@ from .api import encode_lossy_many, encode_many, encode_with_bitrate_many  # noq
 from .api import DEFAULT_RATE_GRID, encode_to_bitrate, encode_to_bitrate_many, rate_pick, size_curve  # noqa: F401
 from .api import Ladder, encode_ladder, encode_ladder_many  # noqa: F401
 from .api import resample, resample_filter, resample_many, resample_out_frames  # noqa: F401
+from .api import normalize, normalize_gain, normalize_lookahead, normalize_many, true_peak  # noqa: F401
 from .api import (FINGERPRINT_DTYPE, FingerprintIndex, extract_dominant_frequencies, fingerprint_array,  # noqa: F401
                   fingerprints_from_files, spectral_similarity)
 from .api import FIDELITY_BLOCK_DTYPE, FIDELITY_DTYPE, compare, fidelity_dict  # noqa: F401

@@ -46,6 +46,7 @@ EXPORTS = [
     "flo_batch_encode_ladder", "flo_ladder_shape", "flo_ladder_file_bytes", "flo_ladder_fetch", "flo_ladder_device_files",
     "flo_ladder_destroy", "flo_encode_batch_ladder",
     "flo_resample_filter", "flo_resample_out_frames", "flo_batch_resample", "flo_resample",
+    "flo_batch_true_peak", "flo_normalize_gain", "flo_normalize_lookahead", "flo_batch_normalize", "flo_normalize",
 ]
 
 
@@ -100,6 +101,21 @@ class Fidelity(C.Structure):   # flo_fidelity: one channel of one clip
 
 class ResampleInfo(C.Structure):   # flo_resample_info
     _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("taps", C.c_uint32), ("tile_outputs", C.c_uint32)]
+
+
+NORM_GAIN, NORM_LIMIT = 0, 1
+NORM_STATUS_SILENT, NORM_STATUS_NONFINITE = 1, 2
+
+
+class NormalizeOpts(C.Structure):   # flo_normalize_opts
+    _fields_ = [("target_lufs", C.c_double), ("ceiling_dbtp", C.c_double), ("max_gain_db", C.c_double), ("mode", C.c_uint32),
+                ("lookahead_frames", C.c_uint32)]
+
+
+class NormalizeReport(C.Structure):   # flo_normalize_report
+    _fields_ = [("input_lufs", C.c_double), ("input_true_peak_dbtp", C.c_double), ("gain_db", C.c_double),
+                ("ceiling_reduction_db", C.c_double), ("input_true_peak", C.c_float), ("gain", C.c_float), ("status", C.c_uint32),
+                ("min_gain_q24", C.c_uint32), ("limited_frames", C.c_uint64)]
 
 
 class FloError(RuntimeError):
@@ -266,5 +282,10 @@ def lib():
     L.flo_resample_out_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
     L.flo_batch_resample.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
     L.flo_resample.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint8, C.POINTER(vp), C.POINTER(sz)]
+    L.flo_batch_true_peak.argtypes = [vp, vp]
+    L.flo_normalize_gain.argtypes = [C.c_double, C.c_double, C.c_float, C.POINTER(NormalizeOpts), C.POINTER(NormalizeReport), C.c_char_p, sz]
+    L.flo_normalize_lookahead.argtypes = [C.c_uint32, C.POINTER(NormalizeOpts), C.POINTER(C.c_uint32), C.c_char_p, sz]
+    L.flo_batch_normalize.argtypes = [vp, C.POINTER(NormalizeOpts), C.POINTER(vp), C.POINTER(NormalizeReport)]
+    L.flo_normalize.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint8, C.POINTER(NormalizeOpts), C.POINTER(vp), C.POINTER(NormalizeReport)]
     _LIB = L
     return L

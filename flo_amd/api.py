@@ -12,6 +12,7 @@ Errors surface as FloError(message), the analogue of FloResult<T> = Result<T, St
 """
 import ctypes as C
 import enum
+import math
 import weakref
 from typing import NamedTuple
 
@@ -151,6 +152,29 @@ class Context:
         res = np.frombuffer(C.string_at(out.value, n.value * 4), np.float32).copy() if n.value else np.zeros(0, np.float32)
         self._L.flo_free(out)
         return res
+
+    def normalize(self, samples, sample_rate, channels, target_lufs=-14.0, ceiling_dbtp=-1.0, limit=False, lookahead_ms=1.5,
+                  max_gain_db=30.0):
+        """flo_normalize: (the interleaved f32 clip at target_lufs under ceiling_dbtp, its report): one upload, the batch's
+        measurements and kernel, one fetch. Whole sample-frames come back"""
+        p = _f32(samples)
+        opts = _normalize_opts(sample_rate, target_lufs, ceiling_dbtp, limit, lookahead_ms, max_gain_db)
+        out, rep = C.c_void_p(), _native.NormalizeReport()
+        self._chk(self._L.flo_normalize(self._h, p.ctypes.data, p.size, sample_rate, channels, C.byref(opts), C.byref(out), C.byref(rep)))
+        n = p.size // channels * channels
+        res = np.frombuffer(C.string_at(out.value, n * 4), np.float32).copy() if n else np.zeros(0, np.float32)
+        self._L.flo_free(out)
+        return res, _normalize_report(rep)
+
+    def true_peak(self, samples, sample_rate, channels) -> float:
+        """the clip's 4x oversampled peak in dBTP (Batch.true_peaks of a batch of this clip)"""
+        p = _f32(samples)
+        b = Batch(self, MODE_LOSSLESS, [p.size], sample_rate, channels, 0)
+        try:
+            self._chk(self._L.flo_batch_upload(b._h, 0, p.ctypes.data))
+            return float(b.true_peaks()[0])
+        finally:
+            b.close()
 
     def upload_path(self):
         """(path large host uploads take on this host, GB/s the probe measured for pageable-direct, for the pinned ring)"""
@@ -400,6 +424,27 @@ class Batch:
         self.ctx._chk(self._L.flo_batch_resample(self._h, out_rate, C.byref(h)))
         lens = [resample_out_frames(self.sample_rate, out_rate, n // self.channels) * self.channels for n in self.n_interleaved]
         return Batch(self.ctx, self._made[0], lens, out_rate, self.channels, self._made[1], _handle=h)
+
+    def true_peaks(self, linear=False) -> np.ndarray:
+        """flo_batch_true_peak: every clip's 4x oversampled peak (the 1 -> 4 interpolator of the sample-rate conversion, the
+        samples themselves included), in one launch: dBTP as f64 (20 log10, -150 at or below 1e-9), or the f32 values"""
+        lin = np.zeros(max(self.n_clips, 1), np.float32)
+        self.ctx._chk(self._L.flo_batch_true_peak(self._h, lin.ctypes.data))
+        lin = lin[:self.n_clips]
+        return lin if linear else np.array([_dbtp(v) for v in lin], np.float64)
+
+    def normalize(self, target_lufs=-14.0, ceiling_dbtp=-1.0, limit=False, lookahead_ms=1.5, max_gain_db=30.0):
+        """flo_batch_normalize: (a new batch of the same mode, rate, channels, quality / level and bit depth, one report per
+        clip). Every clip is brought to target_lufs by its own gain; without `limit` the gain is lowered where the clip's
+        true peak would pass ceiling_dbtp, with it the full gain is applied and a limiter that looks lookahead_ms ahead
+        holds the ceiling. Whole sample-frames are processed; this batch stays valid and unchanged"""
+        opts = _normalize_opts(self.sample_rate, target_lufs, ceiling_dbtp, limit, lookahead_ms, max_gain_db)
+        h = C.c_void_p()
+        reps = (_native.NormalizeReport * max(self.n_clips, 1))()
+        self.ctx._chk(self._L.flo_batch_normalize(self._h, C.byref(opts), C.byref(h), reps))
+        lens = [n // self.channels * self.channels for n in self.n_interleaved]
+        out = Batch(self.ctx, self._made[0], lens, self.sample_rate, self.channels, self._made[1], _handle=h)
+        return out, [_normalize_report(reps[i]) for i in range(self.n_clips)]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1231,6 +1276,77 @@ def resample_many(clips, in_rate, out_rate, channels, ctx: Context = None):
         r = b.resample(out_rate)
         try:
             return [r.download_pcm(i) for i in range(r.n_clips)]
+        finally:
+            r.close()
+    finally:
+        b.close()
+
+
+def _dbtp(linear) -> float:
+    v = float(linear)
+    return 20.0 * math.log10(v) if v > 1e-9 else (v if v != v else -150.0)
+
+
+def normalize_lookahead(sample_rate, lookahead_frames=0) -> int:
+    """flo_normalize_lookahead: the limiter's look-ahead in frames at sample_rate: lookahead_frames (at most 1024), or for 0
+    max(1, round(0.0015 * sample_rate)). Host only: needs no device"""
+    opts = _native.NormalizeOpts(-14.0, -1.0, 30.0, _native.NORM_GAIN, int(lookahead_frames))
+    n, err = C.c_uint32(), C.create_string_buffer(256)
+    if _native.lib().flo_normalize_lookahead(sample_rate, C.byref(opts), C.byref(n), err, 256) != 0:
+        raise FloError(err.value.decode())
+    return int(n.value)
+
+
+def _normalize_opts(sample_rate, target_lufs, ceiling_dbtp, limit, lookahead_ms, max_gain_db):
+    """flo_normalize_opts of the keyword arguments: 1.5 ms is the library's own default (lookahead_frames 0), any other
+    look-ahead is rounded to frames here"""
+    frames = 0 if float(lookahead_ms) == 1.5 else max(1, int(math.floor(float(lookahead_ms) * sample_rate / 1000.0 + 0.5)))
+    return _native.NormalizeOpts(float(target_lufs), float(ceiling_dbtp), float(max_gain_db),
+                                 _native.NORM_LIMIT if limit else _native.NORM_GAIN, frames)
+
+
+def _normalize_report(r) -> dict:
+    status = "non-finite" if r.status & _native.NORM_STATUS_NONFINITE else "silent" if r.status & _native.NORM_STATUS_SILENT else ""
+    return dict(input_lufs=r.input_lufs, input_true_peak=float(r.input_true_peak), input_true_peak_dbtp=r.input_true_peak_dbtp,
+                gain=float(r.gain), gain_db=r.gain_db, ceiling_reduction_db=r.ceiling_reduction_db, status=status, status_bits=int(r.status),
+                limited_frames=int(r.limited_frames), min_gain_q24=int(r.min_gain_q24),
+                min_gain_db=20.0 * math.log10(r.min_gain_q24 / 16777216.0) if r.min_gain_q24 else -150.0)
+
+
+def normalize_gain(integrated_lufs, sample_peak_dbfs, true_peak_linear, target_lufs=-14.0, ceiling_dbtp=-1.0, limit=False,
+                   max_gain_db=30.0, lookahead_frames=0) -> dict:
+    """flo_normalize_gain: the report of one clip from its measurements alone (limited_frames and min_gain_q24 are the
+    kernel's and stay at their start values). Host only: needs no device"""
+    opts = _native.NormalizeOpts(float(target_lufs), float(ceiling_dbtp), float(max_gain_db),
+                                 _native.NORM_LIMIT if limit else _native.NORM_GAIN, int(lookahead_frames))
+    rep, err = _native.NormalizeReport(), C.create_string_buffer(256)
+    if _native.lib().flo_normalize_gain(integrated_lufs, sample_peak_dbfs, true_peak_linear, C.byref(opts), C.byref(rep), err, 256) != 0:
+        raise FloError(err.value.decode())
+    return _normalize_report(rep)
+
+
+def true_peak(samples, sample_rate, channels) -> float:
+    """the interleaved f32 clip's 4x oversampled peak in dBTP, measured on the device (Context.true_peak on the default context)"""
+    return default_context().true_peak(samples, sample_rate, channels)
+
+
+def normalize(samples, sample_rate, channels, **kw):
+    """(the interleaved f32 clip at the target level, its report): Context.normalize on the default context"""
+    return default_context().normalize(samples, sample_rate, channels, **kw)
+
+
+def normalize_many(clips, sample_rate, channels, ctx: Context = None, **kw):
+    """every clip brought to the target level: one batch, one pass; (a list of f32 arrays, the reports). Keywords as
+    Batch.normalize"""
+    c = ctx or default_context()
+    ps = [_f32(x) for x in clips]
+    b = Batch(c, MODE_LOSSLESS, [p.size for p in ps], sample_rate, channels, 0)
+    try:
+        for i, p in enumerate(ps):
+            c._chk(c._L.flo_batch_upload(b._h, i, p.ctypes.data))
+        r, reports = b.normalize(**kw)
+        try:
+            return [r.download_pcm(i) for i in range(r.n_clips)], reports
         finally:
             r.close()
     finally:

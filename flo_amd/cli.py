@@ -3,8 +3,9 @@
 Mirrors the reference CLI (reflo/src/main.rs:19-93, 218-420): the same sub-commands, options, quality names and
 printed fields for the parts that sit on this repository's path -
     encode  <in.wav> <out.flo> [--level N] [--lossy | --transform] [--quality low|medium|high|veryhigh|transparent]
-                               [--bitrate KBPS] [--target-kbps KBPS] [--rate HZ]
+                               [--bitrate KBPS] [--target-kbps KBPS] [--rate HZ] [--lufs N [--ceiling D] [--limit]]
     resample <in.wav> <out.wav> --rate HZ
+    normalize <in.wav> <out.wav> --lufs N [--ceiling D] [--limit]
     curve   <in.wav> [--json]
     ladder  <in.wav> <outdir> --qualities Q0,Q1,... [--json]
     decode  <in.flo> <out.wav>
@@ -33,6 +34,9 @@ file, META included, stays within N kbps over the clip's duration.
 one transform pass on the device (flo_batch_encode_ladder): each file is what `encode --lossy --quality Qj` writes.
 `resample` and `encode --rate N` (not in reflo) convert the audio to N Hz on the device first (flo_resample: a polyphase
 Kaiser-windowed sinc, include/flo_hip.h); the encode then analyses and encodes the converted audio, and header and META carry N.
+`normalize` and `encode --lufs N` (not in reflo) bring the audio to N LUFS under a true-peak ceiling of D dBTP (default -1) on
+the device (flo_normalize): by a gain that the ceiling may lower, or with --limit by the full gain and a look-ahead limiter.
+In `encode` this comes after --rate and before the analysis, so META describes the audio that is encoded.
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
 """
@@ -64,12 +68,27 @@ def _wav_source_format(audio_bytes: bytes) -> str:
     return "UNKNOWN"
 
 
-def _read_at_rate(audio_bytes: bytes, rate, ctx=None):
-    """the WAV's samples, converted to `rate` Hz on the device when one is given and differs"""
+def _read_at_rate(audio_bytes: bytes, rate, ctx=None, level=None):
+    """the WAV's samples, converted to `rate` Hz on the device when one is given and differs, then normalised when `level`
+    (a dict of Context.normalize's keywords) is given"""
     samples, sr, ch = read_wav_bytes(audio_bytes)
     if rate is not None and int(rate) != sr:
         samples, sr = (ctx or api.default_context()).resample(samples, sr, int(rate), ch), int(rate)
+    if level is not None:
+        samples, _ = (ctx or api.default_context()).normalize(samples, sr, ch, **level)
     return samples, sr, ch
+
+
+def level_options(lufs, ceiling=-1.0, limit=False):
+    """Context.normalize's keywords for --lufs / --ceiling / --limit, or None without --lufs"""
+    return None if lufs is None else dict(target_lufs=float(lufs), ceiling_dbtp=float(ceiling), limit=bool(limit))
+
+
+def normalize_wav(audio_bytes: bytes, lufs, ceiling=-1.0, limit=False, ctx=None):
+    """(wav, report): the WAV at `lufs` LUFS under `ceiling` dBTP, as the 32-bit float WAV `decode` writes"""
+    samples, sr, ch = read_wav_bytes(audio_bytes)
+    out, report = (ctx or api.default_context()).normalize(samples, sr, ch, **level_options(lufs, ceiling, limit))
+    return write_wav_bytes(out, sr, ch), report
 
 
 def resample_wav(audio_bytes: bytes, rate, ctx=None) -> bytes:
@@ -79,10 +98,11 @@ def resample_wav(audio_bytes: bytes, rate, ctx=None) -> bytes:
 
 
 def encode_from_audio(audio_bytes: bytes, level=5, lossy=False, quality=0.6, bitrate=None, ctx=None, title=None, artist=None,
-                      album=None, encoding_time=None, rate=None) -> bytes:
-    """reflo::encode_from_audio (reflo/src/lib.rs:183-306) for WAV input; rate: convert to that sample rate first."""
+                      album=None, encoding_time=None, rate=None, normalize=None) -> bytes:
+    """reflo::encode_from_audio (reflo/src/lib.rs:183-306) for WAV input; rate: convert to that sample rate first;
+    normalize: then bring to that level (level_options)."""
     c = ctx or api.default_context()
-    samples, sr, ch = _read_at_rate(audio_bytes, rate, c)
+    samples, sr, ch = _read_at_rate(audio_bytes, rate, c, normalize)
     level = min(int(level), 9)
     is_lossy = bool(lossy or bitrate is not None)
     quality = min(max(float(quality), 0.0), 1.0)
@@ -94,9 +114,9 @@ def encode_from_audio(audio_bytes: bytes, level=5, lossy=False, quality=0.6, bit
     return api.Encoder(sr, ch, 16, c).with_compression(level).encode(samples, mb)
 
 
-def encode_to_target(audio_bytes: bytes, target_kbps, title=None, artist=None, album=None, encoding_time=None, rate=None):
+def encode_to_target(audio_bytes: bytes, target_kbps, title=None, artist=None, album=None, encoding_time=None, rate=None, normalize=None):
     """(file, info): the WAV encoded at the best quality of api.DEFAULT_RATE_GRID whose whole file fits target_kbps"""
-    samples, sr, ch = _read_at_rate(audio_bytes, rate)
+    samples, sr, ch = _read_at_rate(audio_bytes, rate, level=normalize)
     shown = int(target_kbps) if float(target_kbps).is_integer() else target_kbps
     mb = meta.cli_metadata(samples.size, sr, ch, _wav_source_format(audio_bytes), True, 0.0, shown, 5, title, artist, album,
                            encoding_time)
@@ -271,6 +291,13 @@ def main(argv=None) -> int:
     e.add_argument("--title", default=None, help="Title metadata")
     e.add_argument("--artist", default=None, help="Artist metadata")
     e.add_argument("--album", default=None, help="Album metadata")
+    nm = sub.add_parser("normalize", help="Bring a WAV file to a loudness under a true-peak ceiling on the device")
+    nm.add_argument("input")
+    nm.add_argument("output")
+    for p_, need in ((e, False), (nm, True)):
+        p_.add_argument("--lufs", type=float, default=None, required=need, help="Target integrated loudness in LUFS")
+        p_.add_argument("--ceiling", type=float, default=-1.0, help="True-peak ceiling in dBTP (default -1)")
+        p_.add_argument("--limit", action="store_true", help="Apply the full gain and hold the ceiling with a look-ahead limiter")
     rs = sub.add_parser("resample", help="Convert a WAV file to another sample rate on the device")
     rs.add_argument("input")
     rs.add_argument("output")
@@ -324,10 +351,13 @@ def main(argv=None) -> int:
             if a.rate is not None and a.rate != sr:
                 print(f"Converting to {a.rate} Hz...")
                 samples, sr, ch = _read_at_rate(audio, a.rate)
+            level = level_options(a.lufs, a.ceiling, a.limit)
+            if level is not None:
+                print(f"Normalising to {a.lufs:g} LUFS under {a.ceiling:g} dBTP{' (limiter)' if a.limit else ''}...")
             lossy = a.lossy or a.transform
             if a.target_kbps is not None:
                 print(f"Encoding to flo (lossy, at most {a.target_kbps:g} kbps, measured)...")
-                flo, info = encode_to_target(audio, a.target_kbps, a.title, a.artist, a.album, rate=a.rate)
+                flo, info = encode_to_target(audio, a.target_kbps, a.title, a.artist, a.album, rate=a.rate, normalize=level)
                 secs = samples.size / ch / sr
                 print(f"  Quality: {info['quality']:.4f} (candidate {info['index']}){'' if info['fits'] else ' - the target is below the smallest file'}")
                 print(f"  Achieved: {(len(flo) * 8 / 1000 / secs) if secs else 0.0:.1f} kbps ({len(flo)} of {info['target_bytes']} bytes)")
@@ -341,10 +371,10 @@ def main(argv=None) -> int:
                         return 1
                     q = QUALITY[a.quality.lower()]
                     print(f"Encoding to flo (lossy, {a.quality} quality)...")
-                flo = encode_from_audio(audio, a.level, True, q if q is not None else 0.6, a.bitrate, None, a.title, a.artist, a.album, rate=a.rate)
+                flo = encode_from_audio(audio, a.level, True, q if q is not None else 0.6, a.bitrate, None, a.title, a.artist, a.album, rate=a.rate, normalize=level)
             else:
                 print("Encoding to flo (lossless)...")
-                flo = encode_from_audio(audio, a.level, title=a.title, artist=a.artist, album=a.album, rate=a.rate)
+                flo = encode_from_audio(audio, a.level, title=a.title, artist=a.artist, album=a.album, rate=a.rate, normalize=level)
             open(a.output, "wb").write(flo)
             original = int(samples.size * 4)
             print("Done!")
@@ -360,6 +390,25 @@ def main(argv=None) -> int:
             print(f"Converting to {a.rate} Hz...")
             wav = resample_wav(audio, a.rate)
             open(a.output, "wb").write(wav)
+            print("Done!")
+            print(f"  Output: {a.output}")
+        elif a.command == "normalize":
+            print(f"Reading {a.input}...")
+            audio = open(a.input, "rb").read()
+            samples, sr, ch = read_wav_bytes(audio)
+            print(f"  Sample rate: {sr} Hz")
+            print(f"  Channels: {ch}")
+            print(f"  Duration: {samples.size / ch / sr:.2f}s")
+            print(f"Normalising to {a.lufs:g} LUFS under {a.ceiling:g} dBTP{' (limiter)' if a.limit else ''}...")
+            wav, r = normalize_wav(audio, a.lufs, a.ceiling, a.limit)
+            open(a.output, "wb").write(wav)
+            print(f"  Input: {r['input_lufs']:.2f} LUFS, true peak {r['input_true_peak_dbtp']:.2f} dBTP")
+            if r["status"]:
+                print(f"  Copied unchanged: {r['status']}")
+            else:
+                print(f"  Gain: {r['gain_db']:+.2f} dB" + (f" ({r['ceiling_reduction_db']:.2f} dB taken off by the ceiling)" if r["ceiling_reduction_db"] else ""))
+                if a.limit:
+                    print(f"  Limited frames: {r['limited_frames']} (deepest {r['min_gain_db']:.2f} dB)")
             print("Done!")
             print(f"  Output: {a.output}")
         elif a.command == "decode":

@@ -462,6 +462,66 @@ int flo_batch_resample(flo_batch *src, uint32_t out_rate, flo_batch **out);
 int flo_resample(flo_ctx *ctx, const float *pcm, size_t n_interleaved, uint32_t in_rate, uint32_t out_rate, uint8_t channels,
                  float **out, size_t *n_out_interleaved);
 
+/* ---- loudness normalisation and true-peak limiting: a resident batch becomes a resident batch at a target level -------------
+ * (no counterpart in the reference; DESIGN 4.14 has the definition in full.)
+ * The measure: with h the 1 -> 4 interpolator of the sample-rate conversion (flo_resample_filter(1, 4): 4 rows of 64 taps),
+ * e_q[n, c] = the f32 FMA chain over k = 0 .. 63 of h[q][k] * y[n + k - 31, c] from 0, y zero outside the clip: bit for bit
+ * output 4n + q of a conversion to four times the rate. p[n] = max over c of max(|y[n, c]|, max_q |e_q[n, c]|).
+ * flo_analysis::true_peak_dbtp is another quantity (the reference's 49-tap figure) and stays as it is.
+ * flo_batch_true_peak: linear[i] = max_n p[n] of clip i with y = x, whole sample-frames only; 0 for a clip without frames,
+ *   NaN (0x7FC00000) where a sample or an envelope value is NaN. Synchronous.
+ * flo_normalize_gain: host only, no context. The gain of one clip from its integrated loudness (flo_analysis::integrated_lufs),
+ *   its sample peak (flo_analysis::sample_peak_dbfs) and its true peak (flo_batch_true_peak): gain_db = target_lufs -
+ *   integrated, clamped to +- max_gain_db; C = (float)10^(ceiling_dbtp / 20); gain = (float)10^(gain_db / 20). In
+ *   FLO_NORM_GAIN mode the gain is lowered until true_peak * gain <= C (1 - 2^-15) in f64 (the margin covers the roundings, so
+ *   the output's own true peak is at most C); in FLO_NORM_LIMIT mode the limiter holds the
+ *   ceiling, and the gain is lowered only until true_peak * gain <= 2^100, so that nothing overflows. A clip whose sample
+ *   peak is -150 (silent) and a clip with a non-finite loudness, sample peak or true peak are copied unchanged: gain 1 and a
+ *   status flag. opts NULL means the defaults: -14 LUFS, -1 dBTP, FLO_NORM_GAIN, look-ahead 0, max_gain_db 30.
+ *   FLO_ERR_ARG with a message in err (may be NULL) that names the quantity: a non-finite target_lufs or ceiling_dbtp, a
+ *   ceiling_dbtp outside -60 .. 60, a max_gain_db outside 0 .. 120, an unknown mode, lookahead_frames above 1024.
+ * flo_normalize_lookahead: the look-ahead A in frames at `rate`: opts->lookahead_frames, or for 0 max(1, round(0.0015 * rate));
+ *   FLO_ERR_ARG with a message that names lookahead_frames when that is above 1024.
+ * FLO_NORM_GAIN: out[n, c] = fl32(x[n, c] * gain): one rounding, linear.
+ * FLO_NORM_LIMIT: y = fl32(x * gain); r[n] = 2^24 where p[n] <= C, else (uint32)((C / p[n]) * 16777216.0f), IEEE division,
+ *   truncated; m[k] = min r[k - A .. k + A], r outside the clip counting as 2^24; S[n] = sum m[n - A .. n + A];
+ *   s[n] = S[n] div (2A + 1); z[n, c] = fl32(y[n, c] * ((float)s[n] * 2^-24)). s[n] <= r[n], so no sample of z exceeds C by
+ *   more than the two roundings (C (1 + 2^-22)); the oversampled peak of z passes C only through the modulation of s
+ *   (DESIGN 4.14 has the measured figures). Every step behind p is integer arithmetic.
+ * flo_batch_normalize: a new batch of the same mode, rate, channels, quality / level and bit depth; clip i has its whole
+ *   sample-frames (a trailing partial one is not carried over). The loudness of every clip comes from
+ *   flo_batch_analyze_all, the true peak from flo_batch_true_peak, then one launch makes every clip. The source batch stays
+ *   valid and unchanged; a batch of no clips gives a batch of no clips; the result of a clip does not depend on the batch
+ *   around it. reports (may be NULL): [n_clips]. Synchronous: the new batch is complete on return.
+ * flo_normalize: one clip from host memory and back: *out (n_interleaved / channels whole frames) malloc'ed, flo_free.
+ * FLO_NORM_NO_SKIP in the environment (read per call, any value but "0") makes every tile of a LIMIT launch take the long
+ *   path: a tile whose staged samples cannot reach the ceiling otherwise stores y without computing p. Same bits. */
+#define FLO_NORM_GAIN 0
+#define FLO_NORM_LIMIT 1
+#define FLO_NORM_STATUS_SILENT 1u      /* sample_peak_dbfs is -150: copied */
+#define FLO_NORM_STATUS_NONFINITE 2u   /* a non-finite loudness, sample peak or true peak: copied */
+typedef struct flo_normalize_opts {
+    double target_lufs, ceiling_dbtp, max_gain_db;
+    uint32_t mode, lookahead_frames;
+} flo_normalize_opts;
+typedef struct flo_normalize_report {
+    double input_lufs;              /* the integrated loudness the gain was computed from */
+    double input_true_peak_dbtp;    /* 20 log10 of input_true_peak, -150 at or below 1e-9 */
+    double gain_db;                 /* 20 log10 of gain */
+    double ceiling_reduction_db;    /* what the ceiling (GAIN mode) or the overflow guard took off the clamped gain_db; >= 0 */
+    float input_true_peak, gain;    /* linear */
+    uint32_t status;                /* FLO_NORM_STATUS_* */
+    uint32_t min_gain_q24;          /* LIMIT mode: the smallest s[n], 2^24 = unity (2^24 in GAIN mode and for a copied clip) */
+    uint64_t limited_frames;        /* LIMIT mode: frames with s[n] < 2^24 */
+} flo_normalize_report;
+int flo_batch_true_peak(flo_batch *b, float *linear);
+int flo_normalize_gain(double integrated_lufs, double sample_peak_dbfs, float true_peak_linear, const flo_normalize_opts *opts,
+                       flo_normalize_report *report, char *err, size_t err_cap);
+int flo_normalize_lookahead(uint32_t rate, const flo_normalize_opts *opts, uint32_t *frames, char *err, size_t err_cap);
+int flo_batch_normalize(flo_batch *src, const flo_normalize_opts *opts, flo_batch **out, flo_normalize_report *reports);
+int flo_normalize(flo_ctx *ctx, const float *pcm, size_t n_interleaved, uint32_t sample_rate, uint8_t channels,
+                  const flo_normalize_opts *opts, float **out, flo_normalize_report *report);
+
 /* ---- spectral similarity: spectral_similarity (core/analysis.rs:395-437, exported as spectral_similarity_score,
  * lib.rs:1357) over fingerprint sets ----------------------------------------------------------------------------------
  * flo_fingerprint is SpectralFingerprint (analysis.rs:10-26): what flo_analyze / flo_batch_analyze_all return in those
