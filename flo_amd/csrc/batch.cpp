@@ -7,9 +7,7 @@
 #include <cstring>
 
 #include "batch_internal.hpp"
-#include "container_kernels.hpp"
-#include "devpool.hpp"
-#include "lossy_kernels.hpp"
+#include "curve_pass.hpp"
 
 static size_t lossy_max_frame_bytes(int ch) { return 12 + 50 * (size_t)ch + (size_t)ch * (4 + 2064); }
 
@@ -46,7 +44,7 @@ extern "C" void flo_batch_destroy(flo_batch *b) {
     hipStreamSynchronize(b->ctx->stream);
     void *ptrs[] = {b->d_pcm, b->d_plan, b->d_hops, b->d_out, b->d_frame_size, b->d_clip_bytes, b->d_crc, b->d_part, b->d_at,
                     b->d_sprev, b->d_slots, b->d_frame_off, b->d_dbg_coeffs, b->d_dbg_q, b->d_dbg_sfw, b->d_pack_plan, b->d_next, b->d_bmax, b->d_coef,
-                    b->d_crc_ready, b->d_done_q, b->d_inf_mark, b->d_resample};
+                    b->d_crc_ready, b->d_done_q, b->d_inf_mark, b->d_resample, b->d_stamps};
     for (void *p : ptrs)
         if (p) pool_free(p);
     if (b->ev_pack_plan) hipEventDestroy(b->ev_pack_plan);
@@ -86,8 +84,7 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
             // hops * 1024 sample-frames (the reference pads the same way, encoder.rs:177-185), so the chain kernels
             // load whole half-frames without bounds checks; one more half-frame lets them prefetch unconditionally
             // behind the last frame (the values are never used)
-            const uint64_t hops = (b->clip_nsf[i] + 1024 + 1023) / 1024;
-            alloc = (hops + 1) * 1024 * ch;
+            alloc = (lossy_hops(b->clip_nsf[i]) + 1) * 1024 * ch;
             if (alloc < n_interleaved[i]) alloc = n_interleaved[i];
         }
         off += (alloc + 3) & ~(uint64_t)3;
@@ -98,25 +95,16 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
         flo_batch_destroy(b);
         return code;
     };
-#define BCHK(expr)                                                                                  \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            fail(c, e_ == hipErrorOutOfMemory ? FLO_ERR_NOMEM : FLO_ERR_DEVICE,                     \
-                 std::string(#expr) + ": " + hipGetErrorString(e_));                                \
-            return bail(e_ == hipErrorOutOfMemory ? FLO_ERR_NOMEM : FLO_ERR_DEVICE);                \
-        }                                                                                           \
-    } while (0)
-    BCHK(pool_alloc(&b->d_pcm, (b->total_floats + 4) * sizeof(float)));
+    HIPCHK_OR(c, pool_alloc(&b->d_pcm, (b->total_floats + 4) * sizeof(float)), bail);
     if (mode == FLO_MODE_LOSSY) {   // the zero padding behind every clip (the clips themselves are written by the caller)
         if (n_clips <= 8) {
             for (size_t i = 0; i < n_clips; i++) {
                 const uint64_t used = b->clip_nsf[i] * ch;
                 const uint64_t end = (i + 1 < n_clips ? b->clip_off[i + 1] : b->total_floats) + (i + 1 < n_clips ? 0 : 4);
-                BCHK(hipMemsetAsync(b->d_pcm + b->clip_off[i] + used, 0, (end - b->clip_off[i] - used) * sizeof(float), c->stream));
+                HIPCHK_OR(c, hipMemsetAsync(b->d_pcm + b->clip_off[i] + used, 0, (end - b->clip_off[i] - used) * sizeof(float), c->stream), bail);
             }
         } else {
-            BCHK(hipMemsetAsync(b->d_pcm, 0, (b->total_floats + 4) * sizeof(float), c->stream));
+            HIPCHK_OR(c, hipMemsetAsync(b->d_pcm, 0, (b->total_floats + 4) * sizeof(float), c->stream), bail);
         }
     }
     if (mode == FLO_MODE_LOSSY) {
@@ -130,17 +118,14 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
         uint64_t f = 0, o = 0;
         const size_t mfb = lossy_max_frame_bytes(ch);
         for (size_t i = 0; i < n_clips; i++) {
-            uint64_t h = (b->clip_nsf[i] + 1024 + 1023) / 1024;  // encoder.rs:177-179
+            const uint64_t h = lossy_hops(b->clip_nsf[i]);
             b->hops[i] = (uint32_t)h;
             b->clip_frame0[i] = f;
             f += h;
-            // header + TOC of the finished file sit right in front of the (16-byte aligned) DATA chunk
-            const uint64_t head = 74 + 20 * h;
-            o += (head + 15) & ~(uint64_t)15;
-            b->out_off[i] = o;
-            b->file_off[i] = o - head;
-            b->out_cap[i] = ((h * mfb + 64) + 15) & ~(uint64_t)15;
-            o += b->out_cap[i];
+            b->out_cap[i] = align16(h * mfb + 64);
+            const FilePlace at = place_file(o, h, b->out_cap[i]);
+            b->out_off[i] = at.data_off;
+            b->file_off[i] = at.file_off;
         }
         b->total_frames = f;
         b->out_bytes = o;
@@ -151,15 +136,15 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
             plan[2 * n_clips + i] = b->clip_frame0[i];
             plan[3 * n_clips + i] = b->out_off[i];
         }
-        BCHK(pool_alloc(&b->d_plan, (plan.size() + 1) * 8));
-        BCHK(pool_alloc(&b->d_hops, (n_clips + 1) * 4));
-        BCHK(pool_alloc(&b->d_out, b->out_bytes + 64));
-        BCHK(pool_alloc(&b->d_frame_size, (b->total_frames + 1) * 4));
-        BCHK(pool_alloc(&b->d_clip_bytes, (n_clips + 1) * 8));
-        BCHK(pool_alloc(&b->d_crc, (n_clips + 1) * 4));
-        BCHK(pool_alloc(&b->d_next, 32));
-        BCHK(hipMemsetAsync(b->d_next, 0, 32, c->stream));   // once: every launch then zeroes its successor's counters
-        BCHK(pool_alloc(&b->d_part, (n_clips * finish_parts(n_clips) + 1) * 4));
+        HIPCHK_OR(c, pool_alloc(&b->d_plan, (plan.size() + 1) * 8), bail);
+        HIPCHK_OR(c, pool_alloc(&b->d_hops, (n_clips + 1) * 4), bail);
+        HIPCHK_OR(c, pool_alloc(&b->d_out, b->out_bytes + 64), bail);
+        HIPCHK_OR(c, pool_alloc(&b->d_frame_size, (b->total_frames + 1) * 4), bail);
+        HIPCHK_OR(c, pool_alloc(&b->d_clip_bytes, (n_clips + 1) * 8), bail);
+        HIPCHK_OR(c, pool_alloc(&b->d_crc, (n_clips + 1) * 4), bail);
+        HIPCHK_OR(c, pool_alloc(&b->d_next, 32), bail);
+        HIPCHK_OR(c, hipMemsetAsync(b->d_next, 0, 32, c->stream), bail);   // once: every launch then zeroes its successor's counters
+        HIPCHK_OR(c, pool_alloc(&b->d_part, (n_clips * finish_parts(n_clips) + 1) * 4), bail);
         if (n_clips) {
             // from pinned memory on the context's stream, in front of everything that will use them: a synchronous (or
             // pageable "asynchronous") copy would wait for whatever this context's other batches have in flight
@@ -171,8 +156,8 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
             }
             memcpy(b->pin_plan, plan.data(), plan.size() * 8);
             memcpy(b->pin_plan + 4 * n_clips, b->hops.data(), n_clips * 4);
-            BCHK(hipMemcpyAsync(b->d_plan, b->pin_plan, plan.size() * 8, hipMemcpyHostToDevice, c->stream));
-            BCHK(hipMemcpyAsync(b->d_hops, b->pin_plan + 4 * n_clips, n_clips * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK_OR(c, hipMemcpyAsync(b->d_plan, b->pin_plan, plan.size() * 8, hipMemcpyHostToDevice, c->stream), bail);
+            HIPCHK_OR(c, hipMemcpyAsync(b->d_hops, b->pin_plan + 4 * n_clips, n_clips * 4, hipMemcpyHostToDevice, c->stream), bail);
         }
         // the frame-parallel scratch up front when auto picks that form (a forced form allocates at its first encode)
         if ((rc = alloc_frame_scratch(b, lossy_plan(b, 0, 0))) != FLO_OK) return bail(rc);
@@ -186,7 +171,6 @@ extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size
             return bail(FLO_ERR_NOMEM);
         }
     }
-#undef BCHK
     *out = b;
     return FLO_OK;
 }
@@ -290,17 +274,12 @@ static int batch_encode_launch(flo_batch *b) {
         return rc == 0 ? FLO_OK : fail(c, FLO_ERR_DEVICE, "lossless encode: " + err);
     }
     if (!b->total_frames) return FLO_OK;
-    // a caller who wrote all n_interleaved floats through flo_batch_clip_device_ptr left a partial sample-frame in the
-    // zero padding behind the clip: it is not part of the clip (encoder.rs:174)
-    for (size_t i = 0; i < b->n_clips; i++) {
-        const uint64_t part = b->n_il[i] % b->ch;
-        if (part) HIPCHK(c, hipMemsetAsync(b->d_pcm + b->clip_off[i] + b->clip_nsf[i] * b->ch, 0, part * sizeof(float), c->stream));
-    }
+    int rc = batch_zero_partial_frames(b);
+    if (rc != FLO_OK) return rc;
     const LossyPlan &P = b->plan;
     unsigned max_frames = 0;
     for (auto h : b->hops) max_frames = h > max_frames ? h : max_frames;
     const FinishPlan fin = plan_finish(b->n_clips, max_frames, P.crc_ready);
-    int rc;
     b->sizes_queued = false;
     if (P.form == LossyForm::Chain2q) {   // stereo: one lock-step transform wave + one quantiser-and-packer wave per clip
 #ifdef FLO_STAMPS
@@ -349,28 +328,14 @@ static int batch_encode_launch(flo_batch *b) {
     }
     if (rc != FLO_OK) return rc;
     // header, TOC and CRC32 of every clip, in front of its DATA chunk (writer.rs:132-224; encoder.rs:229-238 parameters)
-    FinishArgs F{};
-    F.out = b->d_out;
-    F.data_off = (const unsigned long long *)(b->d_plan + 3 * b->n_clips);
-    F.clip_bytes = (const unsigned long long *)b->d_clip_bytes;
-    F.clip_frame0 = (const unsigned long long *)(b->d_plan + 2 * b->n_clips);
-    F.clip_frames = b->d_hops;
-    F.frame_size = b->d_frame_size;
-    F.frame_samples = nullptr;
-    F.const_samples = 1024;
-    F.sample_rate = b->sr;
-    F.flags = (unsigned short)(0x01 | ((unsigned)b->ts->host.q_level << 8));
-    F.channels = b->ch;
-    F.bit_depth = 16;
-    F.level = 5;
-    F.n_clips = (int)b->n_clips;
+    FinishArgs F = lossy_finish_args(b, b->d_out, (const unsigned long long *)(b->d_plan + 3 * b->n_clips), (const unsigned long long *)b->d_clip_bytes,
+                                     (const unsigned long long *)(b->d_plan + 2 * b->n_clips), b->d_hops, b->d_frame_size, b->n_clips,
+                                     (unsigned short)(0x01 | ((unsigned)b->ts->host.q_level << 8)), b->d_part, max_frames);
     F.crc_out = b->d_crc;
-    F.part_reg = b->d_part;
     if (P.crc_ready) {
         F.crc_ready = b->d_crc_ready;
         F.epoch = b->epoch;
     }
-    F.max_frames = max_frames;
     if ((rc = timed_launch(c, "finish_files", [&] { return launch_finish_files(F, fin, c->stream); })) != FLO_OK) return rc;
     if (P.crc_ready) {   // the sizes come back behind finish_files: flo_batch_sync waits once and copies nothing from the device
         if (!b->pin_sizes) {
@@ -534,7 +499,7 @@ extern "C" int flo_batch_device_files(flo_batch *b, const uint8_t **base, const 
     if (!b->synced) return fail(b->ctx, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
     if (b->mode == FLO_MODE_LOSSY) {
         if (b->h_file_bytes.size() != b->n_clips) b->h_file_bytes.resize(b->n_clips);
-        for (size_t i = 0; i < b->n_clips; i++) b->h_file_bytes[i] = 74 + 20 * (uint64_t)b->hops[i] + b->h_clip_bytes[i];
+        for (size_t i = 0; i < b->n_clips; i++) b->h_file_bytes[i] = head_bytes(b->hops[i]) + b->h_clip_bytes[i];
         if (base) *base = b->d_out;
         if (offsets) *offsets = b->file_off.data();
         if (sizes) *sizes = b->h_file_bytes.data();
@@ -555,12 +520,7 @@ static int pack_impl(flo_batch *b, bool files, void *dst_device, size_t dst_cap,
     const uint64_t *offs, *sizes;
     int rc = files ? flo_batch_device_files(b, &base, &offs, &sizes) : flo_batch_device_streams(b, &base, &offs, &sizes);
     if (rc != FLO_OK) return rc;
-    uint64_t pos = 0;
-    for (size_t i = 0; i < b->n_clips; i++) {
-        offsets[i] = pos;
-        pos += (sizes[i] + 15) & ~(uint64_t)15;
-    }
-    offsets[b->n_clips] = pos;
+    const uint64_t pos = offsets[b->n_clips] = packed_offsets(sizes, b->n_clips, offsets);
     if (pos > dst_cap) return fail(c, FLO_ERR_ARG, "packed stream buffer too small");
     if (!b->n_clips || !pos) return FLO_OK;
     if (!b->d_pack_plan) {
@@ -598,26 +558,14 @@ extern "C" int flo_batch_fetch(flo_batch *b, size_t clip, const uint8_t *meta, s
     flo_ctx *c = b->ctx;
     if (!b->synced) return fail(c, FLO_ERR_STATE, "call flo_batch_encode + flo_batch_sync first");
     HIPCHK(c, hipSetDevice(c->device));
+    // the file was finished on the device; a lossless file's bit depth is the caller's (echoed into the header)
     if (b->mode == FLO_MODE_LOSSLESS) {
-        std::string err;
-        int rc = lossless_fetch(b->ll, clip, b->bit_depth, meta, meta_len, out, out_len, err);
-        return rc == 0 ? FLO_OK : fail(c, FLO_ERR_DEVICE, "lossless fetch: " + err);
+        size_t n;
+        const uint8_t *d_file = lossless_file(b->ll, clip, &n);
+        return fetch_file(c, d_file, n, meta, meta_len, b->bit_depth, "lossless fetch", out, out_len);
     }
-    // the file was finished on the device: copy it, append META and patch meta_size (header bytes 62..69)
-    const size_t head = 74 + 20 * (size_t)b->hops[clip];
-    const size_t n = head + (size_t)b->h_clip_bytes[clip];
-    uint8_t *f = (uint8_t *)malloc(n + meta_len ? n + meta_len : 1);
-    if (!f) return fail(c, FLO_ERR_NOMEM, "malloc failed");
-    hipError_t e = hipMemcpy(f, b->d_out + b->file_off[clip], n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        free(f);
-        return fail(c, FLO_ERR_DEVICE, std::string("fetch: ") + hipGetErrorString(e));
-    }
-    if (meta_len) memcpy(f + n, meta, meta_len);
-    for (int i = 0; i < 8; i++) f[62 + i] = (uint8_t)((uint64_t)meta_len >> (8 * i));
-    *out = f;
-    *out_len = n + meta_len;
-    return FLO_OK;
+    return fetch_file(c, b->d_out + b->file_off[clip], (size_t)(head_bytes(b->hops[clip]) + b->h_clip_bytes[clip]), meta, meta_len, -1, "fetch",
+                      out, out_len);
 }
 
 // ------------------------------------------------------------------------------------------------ one-shot API
@@ -706,8 +654,7 @@ extern "C" int flo_encode_batch(flo_ctx *c, int mode, size_t n_clips, const floa
         const uint8_t *base;
         const uint64_t *offs, *sizes;
         if ((r = flo_batch_device_files(k.b, &base, &offs, &sizes)) != FLO_OK) return r;
-        uint64_t need = 16;
-        for (size_t i = 0; i < k.count; i++) need += (sizes[i] + 15) & ~(uint64_t)15;
+        const uint64_t need = 16 + packed_offsets(sizes, k.count, nullptr);
         if (pool_alloc(&k.d_packed, need) != hipSuccess) return fail(c, FLO_ERR_NOMEM, "packed output buffer");
         k.po.resize(k.count + 1);
         if ((r = flo_batch_pack_files(k.b, k.d_packed, need, k.po.data())) != FLO_OK) return r;
@@ -729,16 +676,15 @@ extern "C" int flo_encode_batch(flo_ctx *c, int mode, size_t n_clips, const floa
         if (hipEventCreateWithFlags(&k.up, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&k.enc, hipEventDisableTiming) != hipSuccess)
             return cleanup(fail(c, FLO_ERR_DEVICE, "hipEventCreate"));
         // (errors leave through cleanup(): the chunks' batches, pinned blocks and events are released, outs[] stays empty)
-        auto ordered = [&](hipError_t e, const char *what) { return e == hipSuccess ? FLO_OK : fail(c, FLO_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
         // the batch's padding memset ran on the ctx stream: the uploads must land behind it
-        if ((rc = ordered(hipEventRecord(k.enc, c->stream), "hipEventRecord")) != FLO_OK) return cleanup(rc);
-        if ((rc = ordered(hipStreamWaitEvent(c->up_stream, k.enc, 0), "hipStreamWaitEvent")) != FLO_OK) return cleanup(rc);
+        HIPCHK_OR(c, hipEventRecord(k.enc, c->stream), cleanup);
+        HIPCHK_OR(c, hipStreamWaitEvent(c->up_stream, k.enc, 0), cleanup);
         if ((rc = batch_upload_all(k.b, pcm + k.first, c->up_stream)) != FLO_OK) return cleanup(rc);
         const double tc = tnow();
-        if ((rc = ordered(hipEventRecord(k.up, c->up_stream), "hipEventRecord")) != FLO_OK) return cleanup(rc);
-        if ((rc = ordered(hipStreamWaitEvent(c->stream, k.up, 0), "hipStreamWaitEvent")) != FLO_OK) return cleanup(rc);
+        HIPCHK_OR(c, hipEventRecord(k.up, c->up_stream), cleanup);
+        HIPCHK_OR(c, hipStreamWaitEvent(c->stream, k.up, 0), cleanup);
         if ((rc = flo_batch_encode(k.b, 0)) != FLO_OK) return cleanup(rc);
-        if ((rc = ordered(hipEventRecord(k.enc, c->stream), "hipEventRecord")) != FLO_OK) return cleanup(rc);   // this chunk's files are finished behind this point
+        HIPCHK_OR(c, hipEventRecord(k.enc, c->stream), cleanup);   // this chunk's files are finished behind this point
         k.encoded = true;
         const double td = tnow();
         if (ci > 0 && (rc = take(chunks[ci - 1])) != FLO_OK) return cleanup(rc);
@@ -786,7 +732,7 @@ static int encode_one(flo_ctx *c, int mode, const float *pcm, size_t n, uint32_t
         // ONE round trip behind the kernels instead of two (sizes, then the file): the size word and a generous guess of the
         // file (768 bytes per frame; q = 0.55 makes about 420) come back together into pinned memory; a longer file fetches
         // its remainder afterwards
-        const size_t head = 74 + 20 * (size_t)b->hops[0];
+        const size_t head = (size_t)head_bytes(b->hops[0]);
         size_t est = head + 768 * (size_t)b->hops[0];
         if (est > head + (size_t)b->out_cap[0]) est = head + (size_t)b->out_cap[0];
         std::string err;
@@ -820,8 +766,7 @@ static int encode_one(flo_ctx *c, int mode, const float *pcm, size_t n, uint32_t
                             free(f);
                             rc = fail(c, FLO_ERR_DEVICE, std::string("one-shot fetch: ") + hipGetErrorString(e));
                         } else {
-                            if (meta_len) memcpy(f + n, meta, meta_len);
-                            for (int i = 0; i < 8; i++) f[62 + i] = (uint8_t)((uint64_t)meta_len >> (8 * i));   // meta_size
+                            attach_meta(f, n, meta, meta_len);
                             *out = f;
                             *out_len = n + meta_len;
                         }

@@ -1,6 +1,6 @@
 // batch_internal.hpp — the device-resident batch (flo_batch_*, include/flo_hip.h) as the library's source files see it:
-// batch.cpp makes, encodes and releases it; decode.cpp, fidelity.cpp, analysis.cpp, dist.cpp, stages.cpp, stream.cpp and
-// rate.cpp read it; resample.cpp makes one from another. Not part of the C ABI.
+// batch.cpp makes, encodes and releases it; decode.cpp, fidelity.cpp, analysis.cpp, dist.cpp, stages.cpp, stream.cpp,
+// rate.cpp, ladder.cpp and curve_pass.cpp read it; resample.cpp makes one from another. Not part of the C ABI.
 #pragma once
 #include <vector>
 
@@ -19,7 +19,7 @@ struct flo_batch {
     TableSet *ts = nullptr;
     // plan (host)
     std::vector<uint64_t> n_il, clip_off, clip_nsf, clip_frame0, out_off, out_cap;
-    std::vector<uint64_t> file_off, h_file_bytes;   // finished file = [file_off, file_off + 74 + 20 frames + DATA)
+    std::vector<uint64_t> file_off, h_file_bytes;   // finished file = [file_off, file_off + head_bytes(frames) + DATA)
     std::vector<uint32_t> hops;
     uint64_t total_frames = 0, total_floats = 0, out_bytes = 0;
     // device

@@ -11,7 +11,7 @@ namespace flo {
 
 struct FinishArgs {
     uint8_t *out;                           // the batch's output buffer
-    const unsigned long long *data_off;     // [n_clips] DATA chunk start (16-byte aligned); the file starts 74 + 20 frames before
+    const unsigned long long *data_off;     // [n_clips] DATA chunk start (16-byte aligned); the file starts head_bytes(frames) before
     const unsigned long long *clip_bytes;   // [n_clips] DATA chunk length (written by the encode kernels)
     const unsigned long long *clip_frame0;  // [n_clips] first frame of the clip among all frames
     const unsigned int *clip_frames;        // [n_clips] frames per clip

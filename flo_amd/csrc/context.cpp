@@ -13,6 +13,22 @@ int fail(flo_ctx *c, int code, const std::string &msg) {
     return code;
 }
 
+int fetch_file(flo_ctx *c, const uint8_t *d_file, size_t n, const uint8_t *meta, size_t meta_len, int bit_depth, const char *what,
+               uint8_t **out, size_t *out_len) {
+    uint8_t *f = (uint8_t *)malloc(n + meta_len ? n + meta_len : 1);
+    if (!f) return fail(c, FLO_ERR_NOMEM, "malloc failed");
+    hipError_t e = hipMemcpy(f, d_file, n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        free(f);
+        return fail(c, FLO_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    attach_meta(f, n, meta, meta_len);
+    if (bit_depth >= 0) set_bit_depth(f, (uint8_t)bit_depth);
+    *out = f;
+    *out_len = n + meta_len;
+    return FLO_OK;
+}
+
 extern "C" const char *flo_last_create_error(void) { return g_create_err.c_str(); }
 extern "C" const char *flo_last_error(const flo_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 extern "C" void flo_free(void *p) { free(p); }

@@ -11,6 +11,7 @@
 #include "../../include/flo_hip.h"
 #include "analysis_kernels.hpp"
 #include "fidelity_kernels.hpp"
+#include "file_layout.hpp"
 #include "lossy_device.hpp"
 #include "stager.hpp"
 #include "tables.hpp"
@@ -96,6 +97,18 @@ int lossy_stream_end(flo_stream *s);
         if (e_ != hipSuccess)                                                                           \
             return fail(ctx, FLO_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));        \
     } while (0)
+// ... for functions that must release something on the way out: returns leave(code), and tells out-of-memory apart
+#define HIPCHK_OR(ctx, expr, leave)                                                                     \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return leave(fail(ctx, e_ == hipErrorOutOfMemory ? FLO_ERR_NOMEM : FLO_ERR_DEVICE,          \
+                              std::string(#expr) + ": " + hipGetErrorString(e_)));                      \
+    } while (0)
+// A finished file out of device memory (n bytes at d_file) as a malloc'd block with META attached (file_layout.hpp);
+// bit_depth >= 0 goes into the header as well. Errors read "<what>: <HIP's text>" (context.cpp)
+int fetch_file(flo_ctx *c, const uint8_t *d_file, size_t n, const uint8_t *meta, size_t meta_len, int bit_depth, const char *what,
+               uint8_t **out, size_t *out_len);
 // folds every finished profiling bracket (wait: every bracket) into the per-kernel sums (context.cpp)
 int profile_drain(flo_ctx *c, bool wait);
 // the constant tables of one sample rate (made on first use, kept by the context; context.cpp)

@@ -62,9 +62,7 @@ struct RcclBackend {
         const uint64_t *offs, *sizes;
         int rc = flo_batch_device_files(b, &base, &offs, &sizes);
         if (rc != FLO_OK) return rc;
-        uint64_t n = 0;
-        for (size_t i = 0; i < b->n_clips; i++) n += (sizes[i] + 15) & ~(uint64_t)15;
-        *need = n;
+        *need = packed_offsets(sizes, b->n_clips, nullptr);
         return FLO_OK;
     }
     int pack(flo_batch *b, Buffer &dst, uint64_t *bytes) {

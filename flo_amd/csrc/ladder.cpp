@@ -1,9 +1,9 @@
 // ladder.cpp — quality ladders (flo_batch_encode_ladder, flo_ladder_*, flo_encode_batch_ladder): every clip of a lossy
 // batch as a finished file at each of K qualities, from ONE transform pass. Host code only: the kernel that packs a frame
-// at every rung is lossy_ladder_kernel (ladder_kernels.hip), the partition into groups and the resident layout are
-// ladder_plan.cpp.
+// at every rung is lossy_ladder_kernel (ladder_kernels.hip), the partition into groups is ladder_plan.cpp, the files'
+// places are file_layout.hpp.
 //
-// Per group of consecutive clips: pass 1 and the scan of the frame-parallel form (as flo_batch_size_curve drives them),
+// Per group of consecutive clips: pass 1 and the scan of the frame-parallel form (curve_pass.cpp, shared with flo_batch_size_curve),
 // then lossy_ladder_kernel into [rung][frame] slots. The kernel also adds up every (rung, clip)'s DATA bytes; those come
 // back to the host - ONE synchronisation per group - and size the group's work buffer exactly. The existing frame-offsets
 // and compaction kernels then run once over all rungs of the group: (rung, clip) is presented to them as a clip of its
@@ -15,11 +15,7 @@
 #include <cstring>
 #include <deque>
 
-#include "batch_internal.hpp"
-#include "container_kernels.hpp"
-#include "devmem.hpp"
-#include "ladder_plan.hpp"
-#include "lossy_kernels.hpp"
+#include "curve_pass.hpp"
 
 struct flo_ladder {
     flo_ctx *ctx = nullptr;
@@ -70,127 +66,72 @@ extern "C" int flo_batch_encode_ladder(flo_batch *b, size_t n_q, const float *qu
         return FLO_OK;
     }
     auto leave = [&](int code) {
-        if (code != FLO_OK) flo_ladder_destroy(l);   // (the stream is idle by then: QuiesceOnExit runs on the way out as well)
+        if (code != FLO_OK) {
+            hipStreamSynchronize(c->stream);   // the ladder's files go back to the pool: nothing may still write them
+            flo_ladder_destroy(l);
+        }
         return code;
     };
-#define LCHK(expr)                                                                                         \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) {                                                                            \
-            hipStreamSynchronize(c->stream);                                                               \
-            return leave(fail(c, e_ == hipErrorOutOfMemory ? FLO_ERR_NOMEM : FLO_ERR_DEVICE,               \
-                              std::string(#expr) + ": " + hipGetErrorString(e_)));                         \
-        }                                                                                                  \
-    } while (0)
-    // a partial sample-frame written through flo_batch_clip_device_ptr is not part of the clip (as flo_batch_encode)
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t part = b->n_il[i] % b->ch;
-        if (part) LCHK(hipMemsetAsync(b->d_pcm + b->clip_off[i] + b->clip_nsf[i] * b->ch, 0, part * sizeof(float), c->stream));
-    }
-    // per-rung constants: the tables an encode at that quality gets (get_tables -> build_lossy_tables)
-    CurveArgs C{};
-    C.n_q = (int)K;
+    int rc = batch_zero_partial_frames(b);
+    if (rc != FLO_OK) return leave(rc);
+    CurveArgs C;
     LadderLevels levels{};   // the header's quality level of every rung (batch.cpp: flags = 0x01 | q_level << 8)
-    for (size_t j = 0; j < K; j++) {
-        TableSet *ts = nullptr;
-        int rc = get_tables(c, b->sr, qualities[j], &ts);
-        if (rc != FLO_OK) return leave(rc);
-        if (j == 0) C.A.T = ts->dev;
-        C.smr_thr[j] = ts->dev.smr_thr;
-        C.ath[j] = ts->dev.pack_g + kRowAth * 64;
-        if (lossy_exact(b->exact != 0, ts->dev)) C.exact_mask |= 1u << j;
-        if (ts->dev.q_transparent) C.qtrans_mask |= 1u << j;
-        levels.level[j] = (unsigned char)ts->host.q_level;
-    }
+    if ((rc = curve_args_fill(b, K, qualities, C, levels.level)) != FLO_OK) return leave(rc);
     const unsigned slot_bytes = lossy_slot_bytes(ch);
-    const std::vector<LadderGroup> groups = ladder_partition(b->hops.data(), n, ladder_frame_bytes(ch, K, slot_bytes), ladder_group_bytes());
-    uint64_t max_frames = 0;
+    const std::vector<ClipGroup> groups = partition_clips(b->hops.data(), n, ladder_frame_bytes(ch, K, slot_bytes), ladder_group_bytes());
     size_t max_parts = 1;
-    std::vector<uint64_t> rel(n);
-    for (const LadderGroup &g : groups) {
+    for (const ClipGroup &g : groups) {
         if (g.frames * K > 0x7FFFFFFFull) return leave(fail(c, FLO_ERR_ARG, "a clip too long for a ladder of this many rungs"));
-        max_frames = g.frames > max_frames ? g.frames : max_frames;
         const size_t parts = K * g.count * finish_parts(K * g.count);
         max_parts = parts > max_parts ? parts : max_parts;
-        uint64_t f = 0;
-        for (size_t i = 0; i < g.count; i++) {
-            rel[g.first + i] = f;
-            f += b->hops[g.first + i];
-        }
     }
     // (rung, clip) as the compaction and finish kernels see it: a clip of its own, rung-major inside its group; group g's
     // entries are [K * g.first, K * (g.first + g.count))
     const size_t V = n * K;
     std::vector<uint64_t> v_frame0(V), v_out(V), v_data(V);
     std::vector<uint32_t> v_hops(V);
-    for (const LadderGroup &g : groups)
-        for (size_t j = 0; j < K; j++)
-            for (size_t i = 0; i < g.count; i++) {
-                const size_t v = K * g.first + j * g.count + i;
-                v_frame0[v] = j * g.frames + rel[g.first + i];
-                v_hops[v] = b->hops[g.first + i];
-            }
-    DevBuf<float> d_at, d_sprev, d_bmax;
-    DevBuf<unsigned long long> d_inf;   // LossyArgs::inf_mark, a tag per group
-    DevBuf<unsigned long long> d_rel, d_sizes, d_vframe0, d_vout, d_vbytes, d_foff, d_pack;
+    LevelRows R;
+    DevBuf<unsigned long long> d_sizes, d_vframe0, d_vout, d_vbytes, d_foff, d_pack;
     DevBuf<unsigned int> d_vhops, d_fsize, d_part;
     DevBuf<uint8_t> d_slots;
     std::deque<DevBuf<uint8_t>> work;   // per group: its finished files at their DATA-aligned places, until the last move
     QuiesceOnExit quiesce(c);
-    if (!d_at.alloc(max_frames * ch * 32) || !d_inf.alloc(n * ch * 32) || !d_sprev.alloc(max_frames * ch * 32) || (ch == 2 && !d_bmax.alloc(max_frames * ch * 32)) ||
-        !d_rel.alloc(n) || !d_sizes.alloc(V) || !d_vframe0.alloc(V) || !d_vout.alloc(V) || !d_vbytes.alloc(V) || !d_vhops.alloc(V) ||
-        !d_part.alloc(max_parts + 1) || !d_foff.alloc(max_frames * K + 1) || !d_fsize.alloc(max_frames * K + 1) ||
-        !d_pack.alloc(3 * V) || !d_slots.alloc((size_t)max_frames * K * slot_bytes))
+    if (!R.alloc(b, groups) || !d_sizes.alloc(V) || !d_vframe0.alloc(V) || !d_vout.alloc(V) || !d_vbytes.alloc(V) || !d_vhops.alloc(V) ||
+        !d_part.alloc(max_parts + 1) || !d_foff.alloc(R.max_frames * K + 1) || !d_fsize.alloc(R.max_frames * K + 1) ||
+        !d_pack.alloc(3 * V) || !d_slots.alloc((size_t)R.max_frames * K * slot_bytes))
         return leave(fail(c, FLO_ERR_NOMEM, "ladder scratch"));
-    LCHK(hipMemcpyAsync(d_rel.p, rel.data(), n * 8, hipMemcpyHostToDevice, c->stream));
-    LCHK(hipMemcpyAsync(d_vframe0.p, v_frame0.data(), V * 8, hipMemcpyHostToDevice, c->stream));
-    LCHK(hipMemcpyAsync(d_vhops.p, v_hops.data(), V * 4, hipMemcpyHostToDevice, c->stream));
-    LCHK(hipMemsetAsync(d_sizes.p, 0, V * 8, c->stream));
-    LCHK(hipMemsetAsync(d_inf.p, 0, n * ch * 32 * 8, c->stream));
-    const unsigned long long *plan = (const unsigned long long *)b->d_plan;
-    const FrameKernel pass1 = ch == 1 ? FrameKernel::Mono1 : ch == 2 ? FrameKernel::Pair1 : FrameKernel::Multi1;
+    for (const ClipGroup &g : groups)
+        for (size_t j = 0; j < K; j++)
+            for (size_t i = 0; i < g.count; i++) {
+                const size_t v = K * g.first + j * g.count + i;
+                v_frame0[v] = j * g.frames + R.rel[g.first + i];
+                v_hops[v] = b->hops[g.first + i];
+            }
+    if ((rc = R.enqueue_clear(b)) != FLO_OK) return leave(rc);
+    HIPCHK_OR(c, hipMemcpyAsync(d_vframe0.p, v_frame0.data(), V * 8, hipMemcpyHostToDevice, c->stream), leave);
+    HIPCHK_OR(c, hipMemcpyAsync(d_vhops.p, v_hops.data(), V * 4, hipMemcpyHostToDevice, c->stream), leave);
+    HIPCHK_OR(c, hipMemsetAsync(d_sizes.p, 0, V * 8, c->stream), leave);
+    C.A.slots = d_slots.p;
+    C.A.frame_size = d_fsize.p;
     std::vector<uint64_t> src_off(V);   // the files inside their group's work buffer
-    for (const LadderGroup &g : groups) {
+    for (const ClipGroup &g : groups) {
         const size_t base = K * g.first, vg = K * g.count;
-        LossyArgs &A = C.A;
-        A.pcm = b->d_pcm;
-        A.clip_off = plan + g.first;
-        A.clip_nsf = plan + n + g.first;
-        A.clip_frame0 = d_rel.p + g.first;
-        A.clip_hops = b->d_hops + g.first;
-        A.nch = ch;
-        A.n_clips = (int)g.count;
-        A.total_frames = g.frames;
-        A.max_hops = g.max_hops;
-        A.a_t = d_at.p;
-        A.bmax_t = d_bmax.p;
-        A.s_prev_out = d_sprev.p;
-        A.s_prev = d_sprev.p;
-        A.inf_mark = d_inf.p;
-        A.inf_tag++;   // (inf_tag shares its storage with epoch, which nothing sets on this struct: frame-parallel launches only)
-        A.slots = d_slots.p;
-        A.slot_bytes = slot_bytes;
-        A.frame_size = d_fsize.p;
-        int rc;
-        if ((rc = timed_launch(c, "ladder_bands", [&] { return launch_lossy_frames_pass(A, pass1, c->stream); })) != FLO_OK) return leave(rc);
-        if ((rc = timed_launch(c, "ladder_scan", [&] { return launch_lossy_scan(A, c->stream); })) != FLO_OK) return leave(rc);
-        if ((rc = timed_launch(c, "lossy_ladder", [&] { return launch_lossy_ladder(C, d_at.p, d_sprev.p, d_sizes.p + base, c->stream); })) != FLO_OK)
+        if ((rc = level_rows_pass(b, C, R, g, "ladder_bands", "ladder_scan")) != FLO_OK) return leave(rc);
+        if ((rc = timed_launch(c, "lossy_ladder", [&] { return launch_lossy_ladder(C, R.d_at.p, R.d_sprev.p, d_sizes.p + base, c->stream); })) != FLO_OK)
             return leave(rc);
         // the group's DATA sizes -> its work buffer, exactly: every file's header + TOC right in front of its aligned DATA
-        LCHK(hipMemcpyAsync(v_data.data() + base, d_sizes.p + base, vg * 8, hipMemcpyDeviceToHost, c->stream));
-        LCHK(hipStreamSynchronize(c->stream));
+        HIPCHK_OR(c, hipMemcpyAsync(v_data.data() + base, d_sizes.p + base, vg * 8, hipMemcpyDeviceToHost, c->stream), leave);
+        HIPCHK_OR(c, hipStreamSynchronize(c->stream), leave);
         uint64_t o = 0;
         for (size_t v = base; v < base + vg; v++) {
-            const uint64_t head = 74 + 20 * (uint64_t)v_hops[v];
-            o += (head + 15) & ~(uint64_t)15;
-            v_out[v] = o;
-            src_off[v] = o - head;
-            o += (v_data[v] + 15) & ~(uint64_t)15;
+            const FilePlace at = place_file(o, v_hops[v], v_data[v]);
+            v_out[v] = at.data_off;
+            src_off[v] = at.file_off;
         }
         work.emplace_back();
         if (!work.back().alloc(o + 64)) return leave(fail(c, FLO_ERR_NOMEM, "ladder files"));
-        LCHK(hipMemcpyAsync(d_vout.p + base, v_out.data() + base, vg * 8, hipMemcpyHostToDevice, c->stream));
-        LossyArgs B = A;
+        HIPCHK_OR(c, hipMemcpyAsync(d_vout.p + base, v_out.data() + base, vg * 8, hipMemcpyHostToDevice, c->stream), leave);
+        LossyArgs B = C.A;
         B.clip_frame0 = d_vframe0.p + base;
         B.clip_hops = d_vhops.p + base;
         B.n_clips = (int)vg;
@@ -207,23 +148,8 @@ extern "C" int flo_batch_encode_ladder(flo_batch *b, size_t n_q, const float *qu
         // header, TOC and CRC32 of every file of the group in one finish (the rungs' files differ in one header byte, the quality
         // level, which a launch of its own then sets)
         const FinishPlan fin = plan_finish(vg, g.max_hops, false);
-        FinishArgs F{};
-        F.out = work.back().p;
-        F.data_off = d_vout.p + base;
-        F.clip_bytes = d_vbytes.p + base;
-        F.clip_frame0 = d_vframe0.p + base;
-        F.clip_frames = d_vhops.p + base;
-        F.frame_size = d_fsize.p;
-        F.frame_samples = nullptr;
-        F.const_samples = 1024;
-        F.sample_rate = b->sr;
-        F.flags = 0x01;
-        F.channels = b->ch;
-        F.bit_depth = 16;
-        F.level = 5;
-        F.n_clips = (int)vg;
-        F.part_reg = d_part.p;
-        F.max_frames = g.max_hops;
+        const FinishArgs F = lossy_finish_args(b, work.back().p, d_vout.p + base, d_vbytes.p + base, d_vframe0.p + base, d_vhops.p + base,
+                                               d_fsize.p, vg, 0x01, d_part.p, g.max_hops);
         if ((rc = timed_launch(c, "ladder_finish", [&] { return launch_finish_files(F, fin, c->stream); })) != FLO_OK) return leave(rc);
         rc = timed_launch(c, "ladder_levels", [&] {
             return launch_ladder_header_levels(work.back().p, d_vout.p + base, d_vhops.p + base, (unsigned)g.count, (unsigned)vg, levels, c->stream);
@@ -232,35 +158,34 @@ extern "C" int flo_batch_encode_ladder(flo_batch *b, size_t n_q, const float *qu
     }
     // what stays resident: the files' exact bytes, rung-major, 16-byte aligned
     std::vector<uint64_t> dst_off(V), fsz(V);
-    for (const LadderGroup &g : groups)
+    for (const ClipGroup &g : groups)
         for (size_t j = 0; j < K; j++)
             for (size_t i = 0; i < g.count; i++) {
                 const size_t v = K * g.first + j * g.count + i;
-                l->size[j * n + g.first + i] = 74 + 20 * (uint64_t)v_hops[v] + v_data[v];
+                l->size[j * n + g.first + i] = head_bytes(v_hops[v]) + v_data[v];
             }
-    const uint64_t total = ladder_layout(l->size.data(), V, l->off.data());
-    LCHK(pool_alloc(&l->d_files, total + 16));
-    for (const LadderGroup &g : groups)
+    const uint64_t total = packed_offsets(l->size.data(), V, l->off.data());
+    HIPCHK_OR(c, pool_alloc(&l->d_files, total + 16), leave);
+    for (const ClipGroup &g : groups)
         for (size_t j = 0; j < K; j++)
             for (size_t i = 0; i < g.count; i++) {
                 const size_t v = K * g.first + j * g.count + i;
                 dst_off[v] = l->off[j * n + g.first + i];
                 fsz[v] = l->size[j * n + g.first + i];
             }
-    LCHK(hipMemcpyAsync(d_pack.p, src_off.data(), V * 8, hipMemcpyHostToDevice, c->stream));
-    LCHK(hipMemcpyAsync(d_pack.p + V, dst_off.data(), V * 8, hipMemcpyHostToDevice, c->stream));
-    LCHK(hipMemcpyAsync(d_pack.p + 2 * V, fsz.data(), V * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK_OR(c, hipMemcpyAsync(d_pack.p, src_off.data(), V * 8, hipMemcpyHostToDevice, c->stream), leave);
+    HIPCHK_OR(c, hipMemcpyAsync(d_pack.p + V, dst_off.data(), V * 8, hipMemcpyHostToDevice, c->stream), leave);
+    HIPCHK_OR(c, hipMemcpyAsync(d_pack.p + 2 * V, fsz.data(), V * 8, hipMemcpyHostToDevice, c->stream), leave);
     size_t gi = 0;
-    for (const LadderGroup &g : groups) {
+    for (const ClipGroup &g : groups) {
         const size_t base = K * g.first, vg = K * g.count;
         const uint8_t *src = work[gi++].p;
-        int rc = timed_launch(c, "ladder_pack", [&] {
+        rc = timed_launch(c, "ladder_pack", [&] {
             return launch_pack_streams(src, d_pack.p + base, d_pack.p + V + base, d_pack.p + 2 * V + base, (int)vg, l->d_files, c->stream);
         });
         if (rc != FLO_OK) return leave(rc);
     }
-    LCHK(hipStreamSynchronize(c->stream));
-#undef LCHK
+    HIPCHK_OR(c, hipStreamSynchronize(c->stream), leave);
     *out = l;
     return FLO_OK;
 }
@@ -283,21 +208,8 @@ extern "C" int flo_ladder_fetch(flo_ladder *l, size_t clip, size_t rung, const u
     if (!l || clip >= l->n_clips || rung >= l->n_q || !out || !out_len || (meta_len && !meta)) return FLO_ERR_ARG;
     flo_ctx *c = l->ctx;
     HIPCHK(c, hipSetDevice(c->device));
-    // the file was finished on the device: copy it, append META and patch meta_size (header bytes 62..69), as flo_batch_fetch
     const size_t k = rung * l->n_clips + clip;
-    const size_t n = (size_t)l->size[k];
-    uint8_t *f = (uint8_t *)malloc(n + meta_len ? n + meta_len : 1);
-    if (!f) return fail(c, FLO_ERR_NOMEM, "malloc failed");
-    hipError_t e = hipMemcpy(f, l->d_files + l->off[k], n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        free(f);
-        return fail(c, FLO_ERR_DEVICE, std::string("ladder fetch: ") + hipGetErrorString(e));
-    }
-    if (meta_len) memcpy(f + n, meta, meta_len);
-    for (int i = 0; i < 8; i++) f[62 + i] = (uint8_t)((uint64_t)meta_len >> (8 * i));
-    *out = f;
-    *out_len = n + meta_len;
-    return FLO_OK;
+    return fetch_file(c, l->d_files + l->off[k], (size_t)l->size[k], meta, meta_len, -1, "ladder fetch", out, out_len);
 }
 
 extern "C" int flo_ladder_device_files(flo_ladder *l, size_t rung, const uint8_t **base, const uint64_t **offsets, const uint64_t **sizes) {

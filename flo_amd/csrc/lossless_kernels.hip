@@ -1110,13 +1110,10 @@ LosslessPlan *lossless_plan_create(const std::vector<uint64_t> &n_il, const std:
             cap += 6 + (uint64_t)ch * (4 + 56 + 2ull * fr.plane_stride);
             p->frames.push_back(fr);
         }
-        // header + TOC of the finished file sit right in front of the (16-byte aligned) DATA chunk
-        const uint64_t head = 74 + 20 * nf;
-        out += (head + 15) & ~15ull;
-        p->clip_out_off[i] = out;
-        p->clip_file_off[i] = out - head;
-        p->clip_out_cap[i] = (cap + 8 + 15) & ~15ull;
-        out += p->clip_out_cap[i];
+        p->clip_out_cap[i] = align16(cap + 8);
+        const FilePlace at = place_file(out, nf, p->clip_out_cap[i]);
+        p->clip_out_off[i] = at.data_off;
+        p->clip_file_off[i] = at.file_off;
     }
     p->clip_first_frame[p->n_clips] = (uint32_t)p->frames.size();
     p->out_bytes = out;
@@ -1277,7 +1274,7 @@ int lossless_device_streams(LosslessPlan *p, const uint8_t **base, const uint64_
 int lossless_device_files(LosslessPlan *p, const uint8_t **base, const uint64_t **offsets, const uint64_t **sizes) {
     p->h_file_bytes.resize(p->n_clips);
     for (size_t i = 0; i < p->n_clips; i++)
-        p->h_file_bytes[i] = 74 + 20 * (uint64_t)(p->clip_first_frame[i + 1] - p->clip_first_frame[i]) + p->h_clip_bytes[i];
+        p->h_file_bytes[i] = head_bytes(p->clip_first_frame[i + 1] - p->clip_first_frame[i]) + p->h_clip_bytes[i];
     if (base) *base = p->d_out;
     if (offsets) *offsets = p->clip_file_off.data();
     if (sizes) *sizes = p->h_file_bytes.data();
@@ -1340,28 +1337,9 @@ int lossless_describe(LosslessPlan *p, std::vector<LosslessFrameInfo> &frames, s
     return 0;
 }
 
-int lossless_fetch(LosslessPlan *p, size_t clip, uint8_t bit_depth, const uint8_t *meta, size_t meta_len, uint8_t **out,
-                   size_t *out_len, std::string &err) {
-    // the file was finished on the device: copy it, append META, patch bit_depth (header byte 13) and meta_size (62..69)
-    const size_t nf = p->clip_first_frame[clip + 1] - p->clip_first_frame[clip];
-    const size_t n = 74 + 20 * nf + (size_t)p->h_clip_bytes[clip];
-    uint8_t *f = (uint8_t *)malloc(n + meta_len);
-    if (!f) {
-        err = "malloc failed";
-        return -1;
-    }
-    hipError_t e = hipMemcpy(f, p->d_out + p->clip_file_off[clip], n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        free(f);
-        err = hipGetErrorString(e);
-        return -1;
-    }
-    if (meta_len) memcpy(f + n, meta, meta_len);
-    f[13] = bit_depth;
-    for (int i = 0; i < 8; i++) f[62 + i] = (uint8_t)((uint64_t)meta_len >> (8 * i));
-    *out = f;
-    *out_len = n + meta_len;
-    return 0;
+const uint8_t *lossless_file(const LosslessPlan *p, size_t clip, size_t *n) {
+    *n = (size_t)(head_bytes(p->clip_first_frame[clip + 1] - p->clip_first_frame[clip]) + p->h_clip_bytes[clip]);
+    return p->d_out + p->clip_file_off[clip];
 }
 
 }  // namespace flo

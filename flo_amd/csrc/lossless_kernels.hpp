@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+#include "file_layout.hpp"   // where the plan puts every clip's finished file
+
 namespace flo {
 
 struct LosslessPlan;
@@ -35,7 +37,7 @@ struct LosslessFrameInfo {
 };
 int lossless_describe(LosslessPlan *p, std::vector<LosslessFrameInfo> &frames, std::vector<LosslessWrapperInfo> &wrappers,
                       const uint8_t **base, std::string &err);
-int lossless_fetch(LosslessPlan *p, size_t clip, uint8_t bit_depth, const uint8_t *meta, size_t meta_len, uint8_t **out,
-                   size_t *out_len, std::string &err);
+// one clip's finished file (header + TOC + DATA, bit depth 16, no META) in device memory, after lossless_collect
+const uint8_t *lossless_file(const LosslessPlan *p, size_t clip, size_t *n);
 
 }  // namespace flo

@@ -1784,7 +1784,7 @@ __global__ __launch_bounds__(64) void sparse_only_kernel(const short *q, unsigne
 
 // Copy every clip's DATA chunk or finished file into one caller-provided buffer, back to back at 16-byte aligned
 // offsets (the packed form handed to the RCCL gather). Destinations are 16-byte aligned; sources need not be (a
-// finished file starts 74 + 20 frames bytes in front of its aligned DATA chunk): each 16-byte unit is assembled from the
+// finished file starts head_bytes(frames) bytes in front of its aligned DATA chunk): each 16-byte unit is assembled from the
 // two aligned units that cover it, and the bytes behind a clip's last byte are written as zeros. The aligned reads stay
 // inside the batch's output allocation (it starts aligned and ends with slack).
 __global__ void pack_streams_kernel(const uint8_t *src, const unsigned long long *src_off, const unsigned long long *dst_off,

@@ -3,9 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "batch_internal.hpp"
-#include "devmem.hpp"
-#include "lossy_kernels.hpp"
+#include "curve_pass.hpp"
 #include "rate_select.hpp"
 
 // scratch of one group of clips: the frame-parallel levels (a_t, s_prev; band maxima for the stereo pass 1), read per call
@@ -26,82 +24,21 @@ extern "C" int flo_batch_size_curve(flo_batch *b, size_t n_q, const float *quali
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = b->n_clips, K = n_q;
     const int ch = b->ch;
-    // a partial sample-frame written through flo_batch_clip_device_ptr is not part of the clip (as flo_batch_encode)
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t part = b->n_il[i] % b->ch;
-        if (part) HIPCHK(c, hipMemsetAsync(b->d_pcm + b->clip_off[i] + b->clip_nsf[i] * b->ch, 0, part * sizeof(float), c->stream));
-    }
-    // per-candidate constants: the tables an encode at that quality gets (get_tables -> build_lossy_tables)
-    CurveArgs C{};
-    C.n_q = (int)K;
-    for (size_t j = 0; j < K; j++) {
-        TableSet *ts = nullptr;
-        int rc = get_tables(c, b->sr, qualities[j], &ts);
-        if (rc != FLO_OK) return rc;
-        if (j == 0) C.A.T = ts->dev;
-        C.smr_thr[j] = ts->dev.smr_thr;
-        C.ath[j] = ts->dev.pack_g + kRowAth * 64;
-        if (lossy_exact(b->exact != 0, ts->dev)) C.exact_mask |= 1u << j;
-        if (ts->dev.q_transparent) C.qtrans_mask |= 1u << j;
-    }
+    int rc = batch_zero_partial_frames(b);
+    if (rc != FLO_OK) return rc;
+    CurveArgs C;
+    if ((rc = curve_args_fill(b, K, qualities, C, nullptr)) != FLO_OK) return rc;
     // groups of consecutive clips whose scratch stays under the limit (a clip larger than the limit is a group of its own)
-    const size_t per_frame = (size_t)ch * 32 * sizeof(float);
-    const int n_bufs = ch == 2 ? 3 : 2;
-    const size_t limit = size_curve_group_bytes();
-    struct Group {
-        size_t first, count;
-        uint64_t frames;
-        unsigned max_hops;
-    };
-    std::vector<Group> groups;
-    std::vector<uint64_t> rel(n);
-    uint64_t max_frames = 0;
-    for (size_t i = 0; i < n;) {
-        Group g{i, 0, 0, 0};
-        while (i < n && (g.count == 0 || (g.frames + b->hops[i]) * per_frame * n_bufs <= limit)) {
-            rel[i] = g.frames;
-            g.frames += b->hops[i];
-            g.max_hops = b->hops[i] > g.max_hops ? b->hops[i] : g.max_hops;
-            g.count++;
-            i++;
-        }
-        max_frames = g.frames > max_frames ? g.frames : max_frames;
-        groups.push_back(g);
-    }
-    DevBuf<float> d_at, d_sprev, d_bmax;
-    DevBuf<unsigned long long> d_inf;   // LossyArgs::inf_mark, a tag per group
-    DevBuf<unsigned long long> d_rel, d_sizes;
+    const std::vector<ClipGroup> groups = partition_clips(b->hops.data(), n, level_row_bytes(b->ch), size_curve_group_bytes());
+    LevelRows R;
+    DevBuf<unsigned long long> d_sizes;
     QuiesceOnExit quiesce(c);
-    if (!d_at.alloc(max_frames * ch * 32) || !d_inf.alloc(n * ch * 32) || !d_sprev.alloc(max_frames * ch * 32) || (ch == 2 && !d_bmax.alloc(max_frames * ch * 32)) ||
-        !d_rel.alloc(n) || !d_sizes.alloc(n * K))
-        return fail(c, FLO_ERR_NOMEM, "size curve scratch");
-    HIPCHK(c, hipMemcpyAsync(d_rel.p, rel.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+    if (!R.alloc(b, groups) || !d_sizes.alloc(n * K)) return fail(c, FLO_ERR_NOMEM, "size curve scratch");
+    if ((rc = R.enqueue_clear(b)) != FLO_OK) return rc;
     HIPCHK(c, hipMemsetAsync(d_sizes.p, 0, n * K * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_inf.p, 0, n * ch * 32 * 8, c->stream));
-    const unsigned long long *plan = (const unsigned long long *)b->d_plan;
-    const FrameKernel pass1 = ch == 1 ? FrameKernel::Mono1 : ch == 2 ? FrameKernel::Pair1 : FrameKernel::Multi1;
-    for (const Group &g : groups) {
-        LossyArgs &A = C.A;
-        A.pcm = b->d_pcm;
-        A.clip_off = plan + g.first;
-        A.clip_nsf = plan + n + g.first;
-        A.clip_frame0 = d_rel.p + g.first;
-        A.clip_hops = b->d_hops + g.first;
-        A.nch = ch;
-        A.n_clips = (int)g.count;
-        A.total_frames = g.frames;
-        A.max_hops = g.max_hops;
-        A.a_t = d_at.p;
-        A.bmax_t = d_bmax.p;
-        A.s_prev_out = d_sprev.p;
-        A.s_prev = d_sprev.p;
-        A.inf_mark = d_inf.p;
-        A.inf_tag++;   // (inf_tag shares its storage with epoch, which nothing sets on this struct: frame-parallel launches only)
-        A.slot_bytes = lossy_slot_bytes(ch);
-        int rc;
-        if ((rc = timed_launch(c, "curve_bands", [&] { return launch_lossy_frames_pass(A, pass1, c->stream); })) != FLO_OK) return rc;
-        if ((rc = timed_launch(c, "curve_scan", [&] { return launch_lossy_scan(A, c->stream); })) != FLO_OK) return rc;
-        if ((rc = timed_launch(c, "size_curve", [&] { return launch_lossy_curve(C, d_at.p, d_sprev.p, d_sizes.p + g.first * K, c->stream); })) != FLO_OK)
+    for (const ClipGroup &g : groups) {
+        if ((rc = level_rows_pass(b, C, R, g, "curve_bands", "curve_scan")) != FLO_OK) return rc;
+        if ((rc = timed_launch(c, "size_curve", [&] { return launch_lossy_curve(C, R.d_at.p, R.d_sprev.p, d_sizes.p + g.first * K, c->stream); })) != FLO_OK)
             return rc;
     }
     std::vector<uint64_t> sparse(n * K);
@@ -111,7 +48,7 @@ extern "C" int flo_batch_size_curve(flo_batch *b, size_t n_q, const float *quali
     // length word per channel; per file the header and the TOC
     for (size_t i = 0; i < n; i++) {
         const uint64_t h = b->hops[i];
-        const uint64_t fixed = 74 + 20 * h + h * (12 + 54 * (uint64_t)ch);
+        const uint64_t fixed = head_bytes(h) + h * (12 + 54 * (uint64_t)ch);
         for (size_t j = 0; j < K; j++) file_bytes[i * K + j] = fixed + sparse[i * K + j];
     }
     return FLO_OK;
@@ -172,7 +109,7 @@ extern "C" int flo_encode_batch_to_size(flo_ctx *c, size_t n_clips, const float 
         const uint64_t ml = meta ? meta_lens[i] : 0;
         const RatePick p = rate_pick(n_q, qualities, &sizes[i * n_q], target_bytes[i] >= ml ? target_bytes[i] - ml : 0);
         chosen[i] = p.index;
-        // (a META longer than the target leaves a budget of 0, which no file meets: even an empty clip's is 74 + 20 + ... bytes)
+        // (a META longer than the target leaves a budget of 0, which no file meets: even an empty clip's has a header and one frame)
         fits[i] = p.fits;
         by_q[p.index].push_back(i);
     }

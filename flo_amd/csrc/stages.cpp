@@ -71,19 +71,19 @@ static int analyze_common(flo_ctx *c, const float *pcm, size_t n, const float *i
         if (rc != FLO_OK) return done(rc);
         uint32_t n_toc = 0;
         uint64_t toc_size = 0, data_size = 0;
-        bool ok = len >= 74;
+        bool ok = len >= kFileHeaderBytes;
         if (ok) {
             memcpy(&toc_size, file + 38, 8);
             memcpy(&data_size, file + 46, 8);
             memcpy(&n_toc, file + 70, 4);
-            ok = n_toc == hops && toc_size == 4 + 20 * (uint64_t)hops && 70 + toc_size + data_size <= len;
+            ok = n_toc == hops && toc_size == 4 + kTocEntryBytes * hops && 70 + toc_size + data_size <= len;
         }
         if (ok && data_size > data_cap) {
             flo_free(file);
             return done(fail(c, FLO_ERR_ARG, "output buffer too small"));
         }
         if (ok) {
-            for (size_t h = 0; frame_sizes && h < hops; h++) memcpy(&frame_sizes[h], file + 74 + 20 * h + 12, 4);
+            for (size_t h = 0; frame_sizes && h < hops; h++) memcpy(&frame_sizes[h], file + head_bytes(h) + 12, 4);
             if (data_size) memcpy(data, file + 70 + toc_size, data_size);
             *data_len = data_size;
         }

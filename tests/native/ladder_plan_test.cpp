@@ -1,18 +1,19 @@
-// ladder_plan_test.cpp — the partition of a quality ladder's clips into groups and the resident layout of its files
-// (flo_amd/csrc/ladder_plan.cpp) on the host. Prints "ok <checks>" and returns 0, or names the first case that fails.
+// ladder_plan_test.cpp — the partition of a batch's clips into groups for the passes over candidate qualities, and the
+// scratch per frame that sizes the groups (flo_amd/csrc/ladder_plan.cpp) on the host. (The layout of the files:
+// file_layout_test.cpp.) Prints "ok <checks>" and returns 0, or names the first case that fails.
 #include <cstdio>
 #include <vector>
 
 #include "../../flo_amd/csrc/ladder_plan.hpp"
 
-using flo::LadderGroup;
+using flo::ClipGroup;
 
 static int g_checks = 0;
 
 // every clip in exactly one group, in order; a group stays under the limit unless it holds one clip; the group's frame
 // count and longest clip are what its clips say; `want` = the expected clips per group
 static bool expect(const char *what, const std::vector<uint32_t> &hops, uint64_t per_frame, uint64_t limit, const std::vector<size_t> &want) {
-    const std::vector<LadderGroup> g = flo::ladder_partition(hops.data(), hops.size(), per_frame, limit);
+    const std::vector<ClipGroup> g = flo::partition_clips(hops.data(), hops.size(), per_frame, limit);
     g_checks++;
     bool ok = g.size() == want.size();
     const uint64_t cap = per_frame ? limit / per_frame : UINT64_MAX;   // frames * per_frame <= limit, without the product
@@ -34,7 +35,7 @@ static bool expect(const char *what, const std::vector<uint32_t> &hops, uint64_t
     ok = ok && next == hops.size();
     if (!ok) {
         fprintf(stderr, "%s: groups", what);
-        for (const LadderGroup &x : g) fprintf(stderr, " [%zu +%zu: %llu frames]", x.first, x.count, (unsigned long long)x.frames);
+        for (const ClipGroup &x : g) fprintf(stderr, " [%zu +%zu: %llu frames]", x.first, x.count, (unsigned long long)x.frames);
         fprintf(stderr, "\n");
     }
     return ok;
@@ -66,15 +67,12 @@ int main() {
     ok &= flo::ladder_frame_bytes(1, 1, 4352) == 4352 + 12 + 128 * 2;
     ok &= flo::ladder_frame_bytes(8, 32, 17040) == 32ull * (17040 + 12) + 8 * 128 * 2;
 
-    // layout: offsets are multiples of 16, files do not overlap, sizes of 0 take no room
-    {
-        const std::vector<uint64_t> sizes = {94, 0, 16, 17, 4096, 1};
-        std::vector<uint64_t> off(sizes.size());
-        const uint64_t total = flo::ladder_layout(sizes.data(), sizes.size(), off.data());
-        g_checks++;
-        const std::vector<uint64_t> want = {0, 96, 96, 112, 144, 4240};
-        ok &= off == want && total == 4256;
-    }
+    // the level rows alone (all the scratch of a size curve's frame); 26 stereo frames fit into 20 KiB, 27 do not (the group
+    // sizes tests/test_gpu_rate.py's test_groups_of_clips_give_the_same_array counts on)
+    g_checks += 3;
+    ok &= flo::level_row_bytes(2) == 768 && flo::level_row_bytes(1) == 256;
+    ok &= flo::level_row_bytes(2) * 26 <= 20 * 1024 && 20 * 1024 < flo::level_row_bytes(2) * 27;
+    ok &= flo::ladder_frame_bytes(2, 16, 4352) == 16 * (4352 + 12) + flo::level_row_bytes(2);
     if (!ok) return 1;
     printf("ok %d\n", g_checks);
     return 0;

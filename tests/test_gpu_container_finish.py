@@ -15,6 +15,9 @@ Its clips are silent: a lossy file with non-zero coefficients equals the oracle'
 not byte for byte. container_model.tone_case, 34 tone clips among 256, has a test of its own with checks 1 and 2 and the
 four makers' agreement, with the path names taken from the DATA lengths the device returned, and asserts that those
 lengths still take the two NT = 64 paths that only an odd length reaches.
+
+What the host does to a finished file on the way out (META appended, meta_size and a lossless file's bit depth patched)
+is checked for the three fetchers at the end.
 """
 import zlib
 
@@ -135,3 +138,45 @@ def test_tone_clips_in_the_chain_form_equal_the_model_under_every_maker(ctx):
     assert {"nt64:one_byte", "nt256:one_byte", "layout:one_byte_over_a_boundary"} <= tail_paths[0] | paths_of(first, 5, False)[0]
     assert "nt64:last63" in tail_paths[1]
     assert {"nt64:last63", "nt64:one_byte"} <= set().union(*tail_paths)
+
+
+@pytest.mark.parametrize("kind", ["lossless", "lossy", "ladder"])
+def test_fetch_appends_meta_and_patches_the_header(ctx, kind):
+    """Every fetcher (flo_batch_fetch of a lossless and of a lossy batch, flo_ladder_fetch): the file fetched with META is
+    the file fetched without, with META behind it and its length at bytes 62 .. 69; a lossless file's byte 13 is the
+    batch's bit depth."""
+    import struct
+
+    import numpy as np
+
+    import flo_amd
+    rng = np.random.default_rng(7)
+    pcm = [(0.25 * rng.standard_normal(2 * n)).astype(np.float32) for n in (1, 1025, 3000)]
+    metas = [b"", b"\x80", bytes(range(256)) + bytes(44)]
+    mode = flo_amd.MODE_LOSSLESS if kind == "lossless" else flo_amd.MODE_LOSSY
+    b = flo_amd.Batch(ctx, mode, [p.size for p in pcm], 44100, 2, {"lossless": 5, "lossy": 0.55, "ladder": 0.35}[kind])
+    lad = None
+    try:
+        for i, p in enumerate(pcm):
+            b.upload(i, p)
+        if kind == "ladder":
+            lad = b.encode_ladder([0.35, 1.0])
+            fetchers = [lambda m, i=i, j=j: lad.fetch(i, j, m) for i in range(3) for j in range(2)]
+        else:
+            if kind == "lossless":
+                b.set_bit_depth(24)
+            b.encode(0)
+            b.sync()
+            fetchers = [lambda m, i=i: b.fetch(i, m) for i in range(3)]
+        for k, fetch in enumerate(fetchers):
+            plain = fetch(b"")
+            assert flofile.parse(plain).crc_valid, (kind, k)
+            assert plain[62:70] == bytes(8), (kind, k)
+            if kind == "lossless":
+                assert plain[13] == 24, (kind, k)
+            for m in metas:
+                assert fetch(m) == plain[:62] + struct.pack("<Q", len(m)) + plain[70:] + m, (kind, k, len(m))
+    finally:
+        if lad is not None:
+            lad.close()
+        b.close()

@@ -1,5 +1,5 @@
 """The host side of quality ladders on CPU: flo_amd/csrc/ladder_plan.cpp (the partition of a batch's clips into groups whose
-scratch stays under a limit, and the resident layout of the files) against the cases of tests/native/ladder_plan_test.cpp,
+scratch stays under a limit, and that scratch per frame) against the cases of tests/native/ladder_plan_test.cpp,
 built here with g++, sanitizers on; the new symbols in the header, the export list and the Python package."""
 import os
 import re
