@@ -17,4 +17,4 @@ from .api import normalize, normalize_gain, normalize_lookahead, normalize_many,
 from .api import (FINGERPRINT_DTYPE, FingerprintIndex, extract_dominant_frequencies, fingerprint_array,  # noqa: F401
                   fingerprints_from_files, spectral_similarity)
 from .api import FIDELITY_BLOCK_DTYPE, FIDELITY_DTYPE, compare, fidelity_dict  # noqa: F401
-from .api import debug_pool_fill  # noqa: F401
+from .api import debug_delay_enqueue, debug_pool_fill, debug_stream_delay, debug_stream_delays  # noqa: F401

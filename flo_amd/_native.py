@@ -23,7 +23,7 @@ EXPORTS = [
     "flo_batch_device_streams", "flo_batch_pack_streams", "flo_batch_decode",
     "flo_batch_device_files", "flo_batch_pack_files",
     "flo_ctx_profile_enable", "flo_ctx_profile_query", "flo_ctx_profile_reset", "flo_ctx_force_path", "flo_ctx_stream",
-    "flo_debug_pool_fill",
+    "flo_debug_pool_fill", "flo_debug_stream_delay", "flo_debug_stream_delays", "flo_debug_delay_enqueue",
     "flo_mdct_forward", "flo_lossy_analyze", "flo_lossy_quantize", "flo_lossy_quantize_smr", "flo_sparse_pack",
     "flo_lossy_pack_frames",
     "flo_dist_unique_id", "flo_dist_create", "flo_dist_destroy", "flo_dist_gather_submit", "flo_dist_gather_flush",
@@ -175,6 +175,10 @@ def lib():
     L.flo_ctx_profile_reset.argtypes = [vp]
     L.flo_ctx_force_path.argtypes = [vp, C.c_int]
     L.flo_debug_pool_fill.argtypes = [C.c_int]
+    L.flo_debug_stream_delay.argtypes = [C.c_int]
+    L.flo_debug_stream_delays.argtypes = []
+    L.flo_debug_stream_delays.restype = C.c_uint64
+    L.flo_debug_delay_enqueue.argtypes = [vp, C.c_int]
     L.flo_ctx_stream.argtypes = [vp]
     L.flo_ctx_stream.restype = vp
     L.flo_mdct_forward.argtypes = [vp, vp, sz, vp]

@@ -637,6 +637,32 @@ def debug_pool_fill(byte):
     return None if prev < 0 else prev
 
 
+def debug_stream_delay(us):
+    """Test hook (flo_debug_stream_delay): queue a delay of about `us` microseconds (0 .. 5000) in front of every launch of
+    the library's and behind every wait for an event on its own streams; None turns it off. Process-wide. Returns the
+    previous setting (None: off)."""
+    if us is not None and not 0 <= int(us) <= 5000:
+        raise ValueError("us must be None or 0 .. 5000")
+    prev = _native.lib().flo_debug_stream_delay(-1 if us is None else int(us))
+    return None if prev < 0 else prev
+
+
+def debug_stream_delays():
+    """The number of delays queued so far in this process (flo_debug_stream_delays)."""
+    return int(_native.lib().flo_debug_stream_delays())
+
+
+def debug_delay_enqueue(stream, us):
+    """Queue one delay of about `us` microseconds (0 .. 5000) on `stream` (a hipStream_t as an integer, or an object with
+    .cuda_stream such as a torch stream), whatever the switch says (flo_debug_delay_enqueue)."""
+    if not 0 <= int(us) <= 5000:
+        raise ValueError("us must be 0 .. 5000")
+    handle = getattr(stream, "cuda_stream", stream)
+    rc = _native.lib().flo_debug_delay_enqueue(int(handle) if handle else None, int(us))
+    if rc != 0:
+        raise RuntimeError("flo_debug_delay_enqueue failed (%d)" % rc)
+
+
 _default_ctx = None
 
 

@@ -12,6 +12,7 @@
 // device, in the host's order of additions, so that only O(blocks + peaks) per clip comes back.
 // Compiled with -ffp-contract=off.
 #include "analysis_device.hpp"
+#include "stream_delay.hpp"
 
 namespace flo {
 
@@ -329,7 +330,7 @@ int launch_analysis_batch(const AnBatchArgs &G, const unsigned long long (&total
     if (side) {
         if (hipEventRecord(side->fork, s) != hipSuccess) return -1;
         for (int i = 0; i < 3; i++)
-            if (hipStreamWaitEvent(side->st[i], side->fork, 0) != hipSuccess) return -1;
+            if (hipStreamWaitEvent(side->st[i], side->fork, 0) != hipSuccess || stream_delay(side->st[i]) != hipSuccess) return -1;
         s1 = side->st[0], s2 = side->st[1], s3 = side->st[2];
     }
     auto grid = [&](int L) { return dim3((unsigned)total[L]); };
@@ -382,6 +383,7 @@ int launch_analysis_batch(const AnBatchArgs &G, const unsigned long long (&total
     if (side)
         for (int i = 0; i < 3; i++)
             if (hipEventRecord(side->join[i], side->st[i]) != hipSuccess || hipStreamWaitEvent(s, side->join[i], 0) != hipSuccess) return -1;
+    if (side && stream_delay(s) != hipSuccess) return -1;   // behind the joins (flo_debug_stream_delay)
     return 0;
 }
 

@@ -12,6 +12,7 @@
 // segment (65 536 frames; 65 536 interleaved samples for the sum of squares), in segments with a filter warm-up beyond (see "order-bound scans" below); only order-free work
 // (maxima, the hash tree, butterflies, the FIR outputs) is spread over lanes. Compiled with -ffp-contract=off.
 #include "analysis_device.hpp"
+#include "stream_delay.hpp"
 
 namespace flo {
 
@@ -46,7 +47,7 @@ int launch_analysis(const AnalysisArgs &A, hipStream_t s, const AnalysisSide *si
     if (side && A.n) {
         if (hipEventRecord(side->fork, s) != hipSuccess) return -1;
         for (int i = 0; i < 3; i++)
-            if (hipStreamWaitEvent(side->st[i], side->fork, 0) != hipSuccess) return -1;
+            if (hipStreamWaitEvent(side->st[i], side->fork, 0) != hipSuccess || stream_delay(side->st[i]) != hipSuccess) return -1;
         s1 = side->st[0], s2 = side->st[1], s3 = side->st[2];
     }
     if (A.n_peaks) {
@@ -99,6 +100,7 @@ int launch_analysis(const AnalysisArgs &A, hipStream_t s, const AnalysisSide *si
     if (side && A.n)
         for (int i = 0; i < 3; i++)
             if (hipEventRecord(side->join[i], side->st[i]) != hipSuccess || hipStreamWaitEvent(s, side->join[i], 0) != hipSuccess) return -1;
+    if (side && A.n && stream_delay(s) != hipSuccess) return -1;   // behind the joins (flo_debug_stream_delay)
     return 0;
 }
 

@@ -217,6 +217,7 @@ extern "C" int flo_batch_fill_synthetic(flo_batch *b, uint32_t seed, uint64_t cl
     HIPCHK(c, hipMalloc(&d_off, tmp.size() * 8));
     hipError_t e = hipMemcpyAsync(d_off, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice, c->stream);
     int rc = 0;
+    if (e == hipSuccess) e = stream_delay(c->stream);   // (this launch bypasses timed_launch)
     if (e == hipSuccess)
         rc = launch_synth_fill(b->d_pcm, (const unsigned long long *)d_off, (const unsigned long long *)d_off + b->n_clips, (int)b->n_clips, b->ch, seed, clip_id0, c->stream);
     hipStreamSynchronize(c->stream);
@@ -663,6 +664,7 @@ extern "C" int flo_encode_batch(flo_ctx *c, int mode, size_t n_clips, const floa
         if (!k.host) return fail(c, FLO_ERR_NOMEM, err);
         HIPCHK(c, hipEventRecord(k.up, c->stream));   // (the upload event has served its purpose: reused for "packed")
         HIPCHK(c, hipStreamWaitEvent(c->down_stream, k.up, 0));
+        HIPCHK(c, stream_delay(c->down_stream));
         HIPCHK(c, hipMemcpyAsync(k.host, k.d_packed, k.po[k.count], hipMemcpyDeviceToHost, c->down_stream));
         for (size_t i = 0; i < k.count; i++) out_lens[k.first + i] = sizes[i];
         k.taken = true;
@@ -679,10 +681,12 @@ extern "C" int flo_encode_batch(flo_ctx *c, int mode, size_t n_clips, const floa
         // the batch's padding memset ran on the ctx stream: the uploads must land behind it
         HIPCHK_OR(c, hipEventRecord(k.enc, c->stream), cleanup);
         HIPCHK_OR(c, hipStreamWaitEvent(c->up_stream, k.enc, 0), cleanup);
+        HIPCHK_OR(c, stream_delay(c->up_stream), cleanup);
         if ((rc = batch_upload_all(k.b, pcm + k.first, c->up_stream)) != FLO_OK) return cleanup(rc);
         const double tc = tnow();
         HIPCHK_OR(c, hipEventRecord(k.up, c->up_stream), cleanup);
         HIPCHK_OR(c, hipStreamWaitEvent(c->stream, k.up, 0), cleanup);
+        HIPCHK_OR(c, stream_delay(c->stream), cleanup);
         if ((rc = flo_batch_encode(k.b, 0)) != FLO_OK) return cleanup(rc);
         HIPCHK_OR(c, hipEventRecord(k.enc, c->stream), cleanup);   // this chunk's files are finished behind this point
         k.encoded = true;

@@ -14,6 +14,7 @@
 #include "file_layout.hpp"
 #include "lossy_device.hpp"
 #include "stager.hpp"
+#include "stream_delay.hpp"
 #include "tables.hpp"
 
 using namespace flo;
@@ -141,6 +142,7 @@ int lossy_decode_whole(flo_ctx *c, const TableSet *ts, const uint8_t *bytes, int
 // Launch through `launch` on the ctx stream; with profiling on, bracketed by events under `name`.
 template <typename F>
 inline int timed_launch(flo_ctx *c, const char *name, F &&launch) {
+    HIPCHK(c, stream_delay(c->stream));   // (flo_debug_stream_delay: off, one relaxed load)
     if (!c->profile) {
         int rc = launch();
         return rc == 0 ? FLO_OK : fail(c, FLO_ERR_DEVICE, std::string("launch ") + name + " failed: " +

@@ -64,6 +64,7 @@ int StageRing::fence_in(flo_ctx *c, hipStream_t caller) {
     if (caller != c->stream) {
         HIPCHK(c, hipEventRecord(ev_in_, caller));
         HIPCHK(c, hipStreamWaitEvent(c->stream, ev_in_, 0));
+        HIPCHK(c, stream_delay(c->stream));
     }
     return FLO_OK;
 }

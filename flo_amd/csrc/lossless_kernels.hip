@@ -25,6 +25,7 @@
 #include "container.hpp"
 #include "lossless_kernels.hpp"
 #include "devpool.hpp"
+#include "stream_delay.hpp"
 
 #include "container_kernels.hpp"
 
@@ -1165,6 +1166,10 @@ int lossless_encode_launch(LosslessPlan *p, hipStream_t s, int profile, std::str
     p->stream = s;
     const unsigned nf = (unsigned)p->frames.size();
     hipError_t e;
+    if ((e = stream_delay(s)) != hipSuccess) {   // this group bypasses timed_launch (flo_debug_stream_delay)
+        err = hipGetErrorString(e);
+        return -1;
+    }
     if ((e = hipMemsetAsync(p->d_out, 0, p->out_bytes + 64, s)) != hipSuccess) {
         err = hipGetErrorString(e);
         return -1;
@@ -1229,6 +1234,10 @@ int lossless_encode_launch(LosslessPlan *p, hipStream_t s, int profile, std::str
     for (size_t i = 0; i < p->n_clips; i++) {
         const unsigned nfc = (unsigned)(p->clip_first_frame[i + 1] - p->clip_first_frame[i]);
         F.max_frames = nfc > F.max_frames ? nfc : F.max_frames;
+    }
+    if ((e = stream_delay(s)) != hipSuccess) {
+        err = hipGetErrorString(e);
+        return -1;
     }
     if (launch_finish_files(F, plan_finish(p->n_clips, F.max_frames, false), s) != 0) {
         err = "finish_files launch failed";

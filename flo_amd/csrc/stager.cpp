@@ -2,6 +2,7 @@
 #include "stager.hpp"
 
 #include "devpool.hpp"
+#include "stream_delay.hpp"
 
 #include <cstdlib>
 
@@ -261,7 +262,8 @@ static int upload_direct(Stager *s, const std::vector<UploadSeg> &segs, size_t t
                                    hipEventCreateWithFlags(&s->aux_go, hipEventDisableTiming) != hipSuccess))
                 split = segs.size();
             // the second stream's copies land behind whatever `stream` has been ordered behind (the batch's zero fill)
-            if (split < segs.size() && (hipEventRecord(s->aux_go, stream) != hipSuccess || hipStreamWaitEvent(s->aux_stream, s->aux_go, 0) != hipSuccess))
+            if (split < segs.size() && (hipEventRecord(s->aux_go, stream) != hipSuccess || hipStreamWaitEvent(s->aux_stream, s->aux_go, 0) != hipSuccess ||
+                                        stream_delay(s->aux_stream) != hipSuccess))
                 split = segs.size();
         }
         int dev = 0;
@@ -287,7 +289,7 @@ static int upload_direct(Stager *s, const std::vector<UploadSeg> &segs, size_t t
             if (segs[i].bytes && hipMemcpyAsync(segs[i].dst, segs[i].src, segs[i].bytes, hipMemcpyHostToDevice, stream) != hipSuccess) ok = false;
         if (helper.joinable()) {
             helper.join();
-            if (!aux_ok || hipStreamWaitEvent(stream, s->aux_ev, 0) != hipSuccess) ok = false;
+            if (!aux_ok || hipStreamWaitEvent(stream, s->aux_ev, 0) != hipSuccess || stream_delay(stream) != hipSuccess) ok = false;
         }
         if (!ok) {
             err = "hipMemcpyAsync (upload) failed";

@@ -18,6 +18,7 @@ extern "C" int flo_mdct_forward(flo_ctx *c, const float *frames, size_t n_frames
     if (!d_in.alloc(n_frames * 2048) || !d_out.alloc(n_frames * 1024)) return fail(c, FLO_ERR_DEVICE, "flo_mdct_forward: device buffers");
     hipError_t e = hipMemcpyAsync(d_in.p, frames, n_frames * 2048 * sizeof(float), hipMemcpyHostToDevice, c->stream);
     int lrc = 0;
+    if (e == hipSuccess) e = stream_delay(c->stream);   // (these launches bypass timed_launch)
     if (e == hipSuccess) lrc = launch_mdct_only(ts->dev, d_in.p, n_frames, d_out.p, c->stream);
     if (e == hipSuccess && lrc == 0)
         e = hipMemcpyAsync(coeffs, d_out.p, n_frames * 1024 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
@@ -127,6 +128,7 @@ extern "C" int flo_lossy_quantize_smr(flo_ctx *c, const float *coeffs, const flo
     hipError_t e = hipMemcpyAsync(d_c.p, coeffs, n_vec * 4096, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && smr) e = hipMemcpyAsync(d_smr.p, smr, n_vec * 4096, hipMemcpyHostToDevice, c->stream);
     int lrc = 0;
+    if (e == hipSuccess) e = stream_delay(c->stream);
     if (e == hipSuccess) lrc = launch_quantise_smr(ts->dev, d_c.p, d_smr.p, n_vec, d_q.p, d_sf.p, c->stream);
     if (e == hipSuccess && lrc == 0) e = hipMemcpyAsync(scale_factors, d_sf.p, n_vec * 100, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && lrc == 0 && smr) e = hipMemcpyAsync(q, d_q.p, n_vec * 2048, hipMemcpyDeviceToHost, c->stream);
@@ -151,6 +153,7 @@ extern "C" int flo_sparse_pack(flo_ctx *c, const int16_t *q, size_t n_vec, int f
     if (!d_q.alloc(n_vec * 1024) || !d_slots.alloc(n_vec * 2080) || !d_sizes.alloc(n_vec)) return fail(c, FLO_ERR_DEVICE, "flo_sparse_pack failed");
     hipError_t e = hipMemcpyAsync(d_q.p, q, n_vec * 2048, hipMemcpyHostToDevice, c->stream);
     int lrc = 0;
+    if (e == hipSuccess) e = stream_delay(c->stream);
     if (e == hipSuccess) lrc = launch_sparse_only(d_q.p, n_vec, d_slots.p, d_sizes.p, form, c->stream);
     if (e == hipSuccess && lrc == 0) e = hipMemcpyAsync(slots.data(), d_slots.p, slots.size(), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && lrc == 0) e = hipMemcpyAsync(sizes.data(), d_sizes.p, n_vec * 4, hipMemcpyDeviceToHost, c->stream);

@@ -670,6 +670,18 @@ int flo_ctx_force_path(flo_ctx *ctx, int which);
  * setting (any other argument changes nothing). Results never depend on it: every byte read is written first. Off,
  * the allocation path pays one relaxed atomic load. */
 int flo_debug_pool_fill(int byte);
+/* test hook, process-wide: while microseconds is 0 .. 5000 the library queues a delay of about that long (one wavefront
+ * that sleeps; no memory access, no waiting, no polling) in front of every launch of its own and, on every stream of its
+ * own, right behind every wait for an event, so that the device runs late behind the host; -1 turns it off, which is
+ * the state at start. Returns the previous setting (any other argument changes nothing). Results never depend on it:
+ * every host read and every release of a block waits for the work it depends on. Off, a site pays one relaxed atomic
+ * load. The exchange stream of flo_dist_* is not delayed. */
+int flo_debug_stream_delay(int microseconds);
+/* the number of delays queued so far in this process (by the switch above and by flo_debug_delay_enqueue) */
+uint64_t flo_debug_stream_delays(void);
+/* queues one such delay of 0 .. 5000 microseconds on any stream (hipStream_t), whatever the switch says: for tests that
+ * make a caller's stream run late. Nothing is queued on a stream that is being captured. */
+int flo_debug_delay_enqueue(void *stream, int microseconds);
 /* stream handle (hipStream_t) of the context, for callers that enqueue their own work around the encode */
 void *flo_ctx_stream(flo_ctx *ctx);
 

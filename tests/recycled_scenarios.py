@@ -45,6 +45,9 @@ EXEMPT = {
     "flo_ctx_profile_query": "reads host-side sums of event times",
     "flo_ctx_profile_reset": "destroys events and clears host sums",
     "flo_ctx_stream": "returns the stream handle",
+    "flo_debug_stream_delay": "sets a host atomic (tests/test_gpu_late_streams.py)",
+    "flo_debug_stream_delays": "reads a host counter",
+    "flo_debug_delay_enqueue": "queues a kernel that touches no memory",
     "flo_ctx_reserve_cus": "sets a host field of the encode plan",
     "flo_ctx_reserved_cus": "reads that host field",
     "flo_ctx_upload_path": "reports what the upload probe measured (the probe's own scratch is hipMalloc'ed and written by its copies)",

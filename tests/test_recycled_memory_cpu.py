@@ -3,6 +3,7 @@ name of flo_amd._native.EXPORTS is in some scenario's `covers` or in recycled_sc
 and never in both. No GPU needed."""
 import re
 
+import normalize_recycled  # noqa: F401  (registers the normalise scenario: the registry is whole when this module runs alone)
 import recycled_scenarios as S
 from flo_amd import _native
 
