@@ -13,6 +13,7 @@ Errors surface as FloError(message), the analogue of FloResult<T> = Result<T, St
 import ctypes as C
 import enum
 import math
+import threading
 import weakref
 from typing import NamedTuple
 
@@ -91,7 +92,12 @@ def _analysis_dict(a, peaks):
 
 
 class Context:
-    """One per host thread / GPU (flo_ctx)."""
+    """One per host thread / GPU (flo_ctx). A context, and every object built on it (Batch, Ladder, Corpus, the streaming
+    encoders and decoders, FingerprintIndex, Encoder, Decoder, ...), is used by one thread at a time: it carries no lock. The
+    contexts of a process are independent, so a pool of threads gives each worker its own. An object built without ctx=
+    keeps default_context() of the thread that built it and belongs to that thread. Encoder, LossyEncoder and
+    TransformEncoder hold no device state and keep no context when built without one: each call of theirs runs on the
+    calling thread's default_context()."""
 
     def __init__(self, device: int = 0):
         self._L = _native.lib()
@@ -663,14 +669,19 @@ def debug_delay_enqueue(stream, us):
         raise RuntimeError("flo_debug_delay_enqueue failed (%d)" % rc)
 
 
-_default_ctx = None
+_default = threading.local()   # .ctx: the calling thread's default context
 
 
 def default_context() -> Context:
-    global _default_ctx
-    if _default_ctx is None:
-        _default_ctx = Context(0)
-    return _default_ctx
+    """The calling thread's own context on device 0, made on the thread's first call. The free functions (encode, decode,
+    resample, normalize, ...) and every object built without ctx= use it, so each of them works on the context of the thread
+    that called or built it: the header's rule, one flo_ctx per host thread, holds without the caller doing anything. The
+    same object is returned for as long as the thread lives. Nothing but the thread (and the objects the caller built on it)
+    refers to it, so it is destroyed when the thread has finished and those objects are gone."""
+    ctx = getattr(_default, "ctx", None)
+    if ctx is None:
+        ctx = _default.ctx = Context(0)
+    return ctx
 
 
 class Encoder:
