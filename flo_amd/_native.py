@@ -47,6 +47,7 @@ EXPORTS = [
     "flo_ladder_destroy", "flo_encode_batch_ladder",
     "flo_resample_filter", "flo_resample_out_frames", "flo_batch_resample", "flo_resample",
     "flo_batch_true_peak", "flo_normalize_gain", "flo_normalize_lookahead", "flo_batch_normalize", "flo_normalize",
+    "flo_batch_edit", "flo_batch_active_range", "flo_edit", "flo_edit_tile_frames",
 ]
 
 
@@ -116,6 +117,11 @@ class NormalizeReport(C.Structure):   # flo_normalize_report
     _fields_ = [("input_lufs", C.c_double), ("input_true_peak_dbtp", C.c_double), ("gain_db", C.c_double),
                 ("ceiling_reduction_db", C.c_double), ("input_true_peak", C.c_float), ("gain", C.c_float), ("status", C.c_uint32),
                 ("min_gain_q24", C.c_uint32), ("limited_frames", C.c_uint64)]
+
+
+class EditSegment(C.Structure):   # flo_edit_segment
+    _fields_ = [("start", C.c_uint64), ("frames", C.c_uint64), ("clip", C.c_uint32), ("pad_head", C.c_uint32), ("pad_tail", C.c_uint32),
+                ("fade_in", C.c_uint32), ("fade_out", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class FloError(RuntimeError):
@@ -291,5 +297,9 @@ def lib():
     L.flo_normalize_lookahead.argtypes = [C.c_uint32, C.POINTER(NormalizeOpts), C.POINTER(C.c_uint32), C.c_char_p, sz]
     L.flo_batch_normalize.argtypes = [vp, C.POINTER(NormalizeOpts), C.POINTER(vp), C.POINTER(NormalizeReport)]
     L.flo_normalize.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint8, C.POINTER(NormalizeOpts), C.POINTER(vp), C.POINTER(NormalizeReport)]
+    L.flo_batch_edit.argtypes = [vp, sz, C.POINTER(EditSegment), C.c_uint8, vp, C.POINTER(vp)]
+    L.flo_batch_active_range.argtypes = [vp, C.c_float, vp, vp]
+    L.flo_edit.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint8, C.POINTER(EditSegment), C.c_uint8, vp, C.POINTER(vp), C.POINTER(sz)]
+    L.flo_edit_tile_frames.argtypes = [C.c_uint8, C.c_uint8, C.POINTER(C.c_uint32)]
     _LIB = L
     return L

@@ -182,6 +182,19 @@ class Context:
         finally:
             b.close()
 
+    def edit(self, samples, sample_rate, channels, segment=None, out_channels=None, matrix=None):
+        """flo_edit: one cut of the interleaved f32 clip, padded, faded and mixed to out_channels (one upload, the batch
+        kernel, one fetch). segment: a dict as Batch.edit takes (clip is 0); None: the whole clip"""
+        p = _f32(samples)
+        segs = _edit_segments([dict(segment or {}, clip=0)], [p.size // channels])
+        cout, m = _edit_matrix(channels, out_channels, matrix)
+        out, n = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.flo_edit(self._h, p.ctypes.data, p.size, sample_rate, channels, segs, cout, m.ctypes.data if m is not None else None,
+                                   C.byref(out), C.byref(n)))
+        res = np.frombuffer(C.string_at(out.value, n.value * 4), np.float32).copy() if n.value else np.zeros(0, np.float32)
+        self._L.flo_free(out)
+        return res
+
     def upload_path(self):
         """(path large host uploads take on this host, GB/s the probe measured for pageable-direct, for the pinned ring)"""
         name, a, b = C.create_string_buffer(64), C.c_double(), C.c_double()
@@ -451,6 +464,45 @@ class Batch:
         lens = [n // self.channels * self.channels for n in self.n_interleaved]
         out = Batch(self.ctx, self._made[0], lens, self.sample_rate, self.channels, self._made[1], _handle=h)
         return out, [_normalize_report(reps[i]) for i in range(self.n_clips)]
+
+    def edit(self, segments, channels=None, matrix=None) -> "Batch":
+        """flo_batch_edit: a new batch of the same mode, rate, quality / level and bit depth whose clip k is segment k: a
+        cut of one clip of this batch, padded, faded and mixed to `channels` by `matrix` ([channels][self.channels] f32; None:
+        a copy), every clip in one launch (enqueued; sync() of either batch orders it). A segment is a dict with clip and
+        optionally start (0), frames (to the clip's end), pad_head, pad_tail, fade_in, fade_out (0), all in frames, or a
+        _native.EditSegment. This batch stays valid and unchanged"""
+        frames = [n // self.channels for n in self.n_interleaved]
+        segs = _edit_segments(segments, frames)
+        cout, m = _edit_matrix(self.channels, channels, matrix)
+        h = C.c_void_p()
+        self.ctx._chk(self._L.flo_batch_edit(self._h, len(segs), segs, cout, m.ctypes.data if m is not None else None, C.byref(h)))
+        lens = [(int(g.pad_head) + int(g.frames) + int(g.pad_tail)) * cout for g in segs]
+        return Batch(self.ctx, self._made[0], lens, self.sample_rate, cout, self._made[1], _handle=h)
+
+    def remix(self, matrix) -> "Batch":
+        """every clip whole, mixed to len(matrix) channels by matrix [Cout][self.channels] (Batch.edit)"""
+        return self.edit([dict(clip=i) for i in range(self.n_clips)], None, matrix)
+
+    def to_mono(self) -> "Batch":
+        """every clip whole as one channel: the matrix [[1 / channels] * channels] in f32 (Batch.remix)"""
+        return self.remix(np.array([[1.0 / self.channels] * self.channels], np.float32))
+
+    def active_ranges(self, threshold_db=-60.0) -> np.ndarray:
+        """flo_batch_active_range: (n_clips, 2) uint64, per clip the first frame with a sample above the threshold in magnitude
+        (or NaN) and the last such frame plus one; 0, 0 for a clip without one. The threshold is f32(10^(threshold_db / 20))"""
+        r = np.zeros((2, max(self.n_clips, 1)), np.uint64)
+        thr = np.float32(10.0 ** (float(threshold_db) / 20.0))
+        self.ctx._chk(self._L.flo_batch_active_range(self._h, float(thr), r[0].ctypes.data, r[1].ctypes.data))
+        return np.ascontiguousarray(r[:, :self.n_clips].T)
+
+    def trim_silence(self, threshold_db=-60.0, pre_ms=0.0, post_ms=0.0, fade_ms=0.0):
+        """(a new batch, the active ranges): every clip cut to its active range, widened by pre_ms in front and post_ms behind
+        (inside the clip) and faded in and out over fade_ms (at most the cut). A clip without an active frame becomes a clip
+        of 0 frames. Batch.active_ranges, then Batch.edit"""
+        ranges = self.active_ranges(threshold_db)
+        frames = [n // self.channels for n in self.n_interleaved]
+        segs = trim_segments(ranges, frames, self.sample_rate, pre_ms, post_ms, fade_ms)
+        return self.edit(segs), ranges
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1388,6 +1440,145 @@ def normalize_many(clips, sample_rate, channels, ctx: Context = None, **kw):
             r.close()
     finally:
         b.close()
+
+
+def edit_tile_frames(in_channels, out_channels) -> int:
+    """flo_edit_tile_frames: the output frames one workgroup of the edit kernel makes. Host only: needs no device"""
+    n = C.c_uint32()
+    if _native.lib().flo_edit_tile_frames(in_channels, out_channels, C.byref(n)) != 0:
+        raise FloError(f"unsupported channel counts {in_channels} -> {out_channels}")
+    return int(n.value)
+
+
+def _ms_frames(ms, sample_rate) -> int:
+    return int(math.floor(float(ms) * sample_rate / 1000.0 + 0.5))
+
+
+def trim_segments(ranges, frames, sample_rate, pre_ms=0.0, post_ms=0.0, fade_ms=0.0) -> list:
+    """Batch.trim_silence's segments from the active ranges (first, end) of clips of `frames` frames: start = max(first - pre,
+    0), stop = min(end + post, N), nothing for a clip without an active frame; fades of min(round(fade_ms), the cut)"""
+    pre, post, fade = _ms_frames(pre_ms, sample_rate), _ms_frames(post_ms, sample_rate), _ms_frames(fade_ms, sample_rate)
+    segs = []
+    for i, (first, end) in enumerate(np.asarray(ranges, np.uint64).reshape(-1, 2).tolist()):
+        start, stop = (max(first - pre, 0), min(end + post, int(frames[i]))) if end else (0, 0)
+        f = min(fade, stop - start, (1 << 24) - 1)
+        segs.append(dict(clip=i, start=start, frames=stop - start, fade_in=f, fade_out=f))
+    return segs
+
+
+def _edit_segments(segments, clip_frames):
+    """the flo_edit_segment array of a list of dicts / EditSegment; `frames` missing or None: to the clip's end"""
+    segments = list(segments)
+    out = (_native.EditSegment * max(len(segments), 1))()
+    for k, g in enumerate(segments):
+        if isinstance(g, _native.EditSegment):
+            out[k] = g
+            continue
+        unknown = set(g) - {"clip", "start", "frames", "pad_head", "pad_tail", "fade_in", "fade_out", "reserved"}
+        if unknown:
+            raise FloError(f"segment {k}: unknown keys {sorted(unknown)}")
+        clip, start = int(g.get("clip", 0)), int(g.get("start", 0))
+        frames = g.get("frames")
+        if frames is None:
+            frames = max(int(clip_frames[clip]) - start, 0) if 0 <= clip < len(clip_frames) else 0
+        out[k] = _native.EditSegment(start, int(frames), clip, int(g.get("pad_head", 0)), int(g.get("pad_tail", 0)),
+                                     int(g.get("fade_in", 0)), int(g.get("fade_out", 0)), int(g.get("reserved", 0)))
+    return (_native.EditSegment * len(segments)).from_buffer(out) if segments else (_native.EditSegment * 0)()
+
+
+def _edit_matrix(in_channels, out_channels, matrix):
+    """(out_channels, the matrix as a contiguous f32 array [Cout * Cin] or None)"""
+    if matrix is None:
+        return int(in_channels if out_channels is None else out_channels), None
+    m = np.ascontiguousarray(matrix, np.float32)
+    if m.ndim == 2:
+        if m.shape[1] != in_channels or (out_channels is not None and m.shape[0] != out_channels):
+            raise FloError(f"matrix is {m.shape[0]} x {m.shape[1]}, the mix {out_channels if out_channels is not None else '?'} x {in_channels}")
+        return int(m.shape[0]), m.reshape(-1)
+    cout = int(m.size // in_channels if out_channels is None else out_channels)
+    if m.ndim != 1 or m.size != cout * in_channels or not cout:
+        raise FloError(f"matrix has {m.size} entries, the mix {cout} x {in_channels}")
+    return cout, m
+
+
+def _uploaded(c, clips, sample_rate, channels):
+    ps = [_f32(x) for x in clips]
+    b = Batch(c, MODE_LOSSLESS, [p.size for p in ps], sample_rate, channels, 0)
+    try:
+        for i, p in enumerate(ps):
+            c._chk(c._L.flo_batch_upload(b._h, i, p.ctypes.data))
+        b.sync()
+    except Exception:
+        b.close()
+        raise
+    return b
+
+
+def _fetched(r):
+    try:
+        return [r.download_pcm(i) for i in range(r.n_clips)]
+    finally:
+        r.close()
+
+
+def edit(samples, sample_rate, channels, segment=None, out_channels=None, matrix=None) -> np.ndarray:
+    """one cut of the interleaved f32 clip, made on the device (Context.edit on the default context)"""
+    return default_context().edit(samples, sample_rate, channels, segment, out_channels, matrix)
+
+
+def edit_many(clips, sample_rate, channels, segments, out_channels=None, matrix=None, ctx: Context = None):
+    """segments (Batch.edit) cut from the clips: one upload, one device pass, one fetch; a list of f32 arrays"""
+    b = _uploaded(ctx or default_context(), clips, sample_rate, channels)
+    try:
+        return _fetched(b.edit(segments, out_channels, matrix))
+    finally:
+        b.close()
+
+
+def remix_many(clips, sample_rate, channels, matrix, ctx: Context = None):
+    """every clip mixed to len(matrix) channels by matrix [Cout][channels]: one batch, one launch; a list of f32 arrays"""
+    b = _uploaded(ctx or default_context(), clips, sample_rate, channels)
+    try:
+        return _fetched(b.remix(matrix))
+    finally:
+        b.close()
+
+
+def remix(samples, sample_rate, channels, matrix) -> np.ndarray:
+    """the interleaved f32 clip mixed to len(matrix) channels on the device"""
+    return remix_many([samples], sample_rate, channels, matrix)[0]
+
+
+def active_range_many(clips, sample_rate, channels, threshold_db=-60.0, ctx: Context = None) -> np.ndarray:
+    """(n, 2) uint64: every clip's first active frame and last active frame plus one (Batch.active_ranges)"""
+    b = _uploaded(ctx or default_context(), clips, sample_rate, channels)
+    try:
+        return b.active_ranges(threshold_db)
+    finally:
+        b.close()
+
+
+def active_range(samples, sample_rate, channels, threshold_db=-60.0):
+    """(first, end) of the interleaved f32 clip, measured on the device"""
+    r = active_range_many([samples], sample_rate, channels, threshold_db)
+    return int(r[0, 0]), int(r[0, 1])
+
+
+def trim_silence_many(clips, sample_rate, channels, ctx: Context = None, **kw):
+    """every clip cut to its active range: one upload, two device passes, one fetch; (a list of f32 arrays, the ranges).
+    Keywords as Batch.trim_silence"""
+    b = _uploaded(ctx or default_context(), clips, sample_rate, channels)
+    try:
+        r, ranges = b.trim_silence(**kw)
+        return _fetched(r), ranges
+    finally:
+        b.close()
+
+
+def trim_silence(samples, sample_rate, channels, **kw):
+    """(the interleaved f32 clip cut to its active range, (first, end)): trim_silence_many of one clip"""
+    outs, ranges = trim_silence_many([samples], sample_rate, channels, **kw)
+    return outs[0], (int(ranges[0, 0]), int(ranges[0, 1]))
 
 
 def _encode_analysed(mode, samples, sample_rate, channels, quality_or_level, bit_depth, metadata) -> bytes:

@@ -4,6 +4,10 @@ Mirrors the reference CLI (reflo/src/main.rs:19-93, 218-420): the same sub-comma
 printed fields for the parts that sit on this repository's path -
     encode  <in.wav> <out.flo> [--level N] [--lossy | --transform] [--quality low|medium|high|veryhigh|transparent]
                                [--bitrate KBPS] [--target-kbps KBPS] [--rate HZ] [--lufs N [--ceiling D] [--limit]]
+                               [--mono] [--trim-silence DB]
+    edit    <in.wav> <out.wav> [--mono | --channels N --matrix a,b,...] [--start S] [--duration S]
+                               [--trim-silence DB] [--pre-ms MS] [--post-ms MS] [--fade-in MS] [--fade-out MS]
+                               [--pad-head S] [--pad-tail S]
     resample <in.wav> <out.wav> --rate HZ
     normalize <in.wav> <out.wav> --lufs N [--ceiling D] [--limit]
     curve   <in.wav> [--json]
@@ -37,6 +41,12 @@ Kaiser-windowed sinc, include/flo_hip.h); the encode then analyses and encodes t
 `normalize` and `encode --lufs N` (not in reflo) bring the audio to N LUFS under a true-peak ceiling of D dBTP (default -1) on
 the device (flo_normalize): by a gain that the ceiling may lower, or with --limit by the full gain and a look-ahead limiter.
 In `encode` this comes after --rate and before the analysis, so META describes the audio that is encoded.
+`edit`, `encode --mono` and `encode --trim-silence DB` (not in reflo) cut, pad, fade and remix the audio on the device
+(flo_batch_edit, flo_batch_active_range): --start / --duration pick a window in seconds, --trim-silence DB narrows it to the
+clip's active range (samples above DB dBFS), widened by --pre-ms / --post-ms; the cut is faded over --fade-in / --fade-out
+milliseconds and padded with --pad-head / --pad-tail seconds of silence; --mono averages the channels, --channels N with
+--matrix (N rows of the source's channel count, row-major) mixes them. In `encode` the edits come first, before --rate and
+--lufs, in that order.
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
 """
@@ -68,10 +78,72 @@ def _wav_source_format(audio_bytes: bytes) -> str:
     return "UNKNOWN"
 
 
-def _read_at_rate(audio_bytes: bytes, rate, ctx=None, level=None):
-    """the WAV's samples, converted to `rate` Hz on the device when one is given and differs, then normalised when `level`
-    (a dict of Context.normalize's keywords) is given"""
+def edit_options(mono=False, channels=None, matrix=None, start=None, duration=None, trim_silence=None, pre_ms=0.0, post_ms=0.0,
+                 fade_in=0.0, fade_out=0.0, pad_head=0.0, pad_tail=0.0):
+    """apply_edit's options for the `edit` command's switches, or None when none of them is given"""
+    if isinstance(matrix, str):
+        matrix = [float(v) for v in matrix.split(",") if v.strip()]
+    if mono and (channels is not None or matrix is not None):
+        raise ValueError("--mono excludes --channels and --matrix")
+    if (channels is None) != (matrix is None):
+        raise ValueError("--channels and --matrix go together")
+    o = dict(mono=bool(mono), channels=channels, matrix=matrix, start=start, duration=duration, trim_silence=trim_silence,
+             pre_ms=float(pre_ms), post_ms=float(post_ms), fade_in=float(fade_in), fade_out=float(fade_out),
+             pad_head=float(pad_head), pad_tail=float(pad_tail))
+    idle = dict(mono=False, channels=None, matrix=None, start=None, duration=None, trim_silence=None, pre_ms=0.0, post_ms=0.0,
+                fade_in=0.0, fade_out=0.0, pad_head=0.0, pad_tail=0.0)
+    return None if o == idle else o
+
+
+def apply_edit(samples, sr, ch, opts, ctx=None):
+    """(samples, channels, info) of one cut of the clip on the device (edit_options): one upload, the active range when
+    --trim-silence asks for it, one Batch.edit, one fetch"""
+    c = ctx or api.default_context()
+    p = api._f32(samples)
+    n = p.size // ch
+    secs = lambda v: int(round(float(v) * sr))   # noqa: E731
+    b = api.Batch(c, api.MODE_LOSSLESS, [p.size], sr, ch, 0)
+    try:
+        b.upload(0, p)
+        lo = min(secs(opts["start"]), n) if opts["start"] is not None else 0
+        hi = min(lo + secs(opts["duration"]), n) if opts["duration"] is not None else n
+        info = {}
+        if opts["trim_silence"] is not None:
+            first, end = (int(v) for v in b.active_ranges(opts["trim_silence"])[0])
+            info["active"] = (first, end)
+            seg = api.trim_segments([(first, end)], [n], sr, opts["pre_ms"], opts["post_ms"])[0]
+            lo, hi = max(lo, seg["start"]), min(hi, seg["start"] + seg["frames"])
+            hi = max(hi, lo)
+        frames = hi - lo
+        fade = lambda ms: min(api._ms_frames(ms, sr), frames, (1 << 24) - 1)   # noqa: E731
+        seg = dict(clip=0, start=lo, frames=frames, pad_head=secs(opts["pad_head"]), pad_tail=secs(opts["pad_tail"]),
+                   fade_in=fade(opts["fade_in"]), fade_out=fade(opts["fade_out"]))
+        info["segment"] = seg
+        if opts["mono"]:
+            r = b.edit([seg], None, [[1.0 / ch] * ch])
+        else:
+            r = b.edit([seg], opts["channels"], opts["matrix"])
+        try:
+            return r.download_pcm(0), r.channels, info
+        finally:
+            r.close()
+    finally:
+        b.close()
+
+
+def edit_wav(audio_bytes: bytes, opts, ctx=None):
+    """(wav, info): the WAV cut, padded, faded and remixed on the device, as the 32-bit float WAV `decode` writes"""
     samples, sr, ch = read_wav_bytes(audio_bytes)
+    out, ch, info = apply_edit(samples, sr, ch, opts or edit_options(start=0.0), ctx)
+    return write_wav_bytes(out, sr, ch), info
+
+
+def _read_at_rate(audio_bytes: bytes, rate, ctx=None, level=None, edit=None):
+    """the WAV's samples, edited on the device when `edit` (edit_options) is given, converted to `rate` Hz on the device when
+    one is given and differs, then normalised when `level` (a dict of Context.normalize's keywords) is given"""
+    samples, sr, ch = read_wav_bytes(audio_bytes)
+    if edit is not None:
+        samples, ch, _ = apply_edit(samples, sr, ch, edit, ctx)
     if rate is not None and int(rate) != sr:
         samples, sr = (ctx or api.default_context()).resample(samples, sr, int(rate), ch), int(rate)
     if level is not None:
@@ -98,11 +170,12 @@ def resample_wav(audio_bytes: bytes, rate, ctx=None) -> bytes:
 
 
 def encode_from_audio(audio_bytes: bytes, level=5, lossy=False, quality=0.6, bitrate=None, ctx=None, title=None, artist=None,
-                      album=None, encoding_time=None, rate=None, normalize=None) -> bytes:
-    """reflo::encode_from_audio (reflo/src/lib.rs:183-306) for WAV input; rate: convert to that sample rate first;
-    normalize: then bring to that level (level_options)."""
+                      album=None, encoding_time=None, rate=None, normalize=None, edit=None, pcm=None) -> bytes:
+    """reflo::encode_from_audio (reflo/src/lib.rs:183-306) for WAV input; edit: cut and remix first (edit_options); rate:
+    then convert to that sample rate; normalize: then bring to that level (level_options). pcm: (samples, rate, channels)
+    that the caller has already read, edited, converted and levelled that way: they are encoded as they are."""
     c = ctx or api.default_context()
-    samples, sr, ch = _read_at_rate(audio_bytes, rate, c, normalize)
+    samples, sr, ch = pcm if pcm is not None else _read_at_rate(audio_bytes, rate, c, normalize, edit)
     level = min(int(level), 9)
     is_lossy = bool(lossy or bitrate is not None)
     quality = min(max(float(quality), 0.0), 1.0)
@@ -114,9 +187,11 @@ def encode_from_audio(audio_bytes: bytes, level=5, lossy=False, quality=0.6, bit
     return api.Encoder(sr, ch, 16, c).with_compression(level).encode(samples, mb)
 
 
-def encode_to_target(audio_bytes: bytes, target_kbps, title=None, artist=None, album=None, encoding_time=None, rate=None, normalize=None):
-    """(file, info): the WAV encoded at the best quality of api.DEFAULT_RATE_GRID whose whole file fits target_kbps"""
-    samples, sr, ch = _read_at_rate(audio_bytes, rate, level=normalize)
+def encode_to_target(audio_bytes: bytes, target_kbps, title=None, artist=None, album=None, encoding_time=None, rate=None, normalize=None,
+                     edit=None, pcm=None):
+    """(file, info): the WAV encoded at the best quality of api.DEFAULT_RATE_GRID whose whole file fits target_kbps; pcm as
+    in encode_from_audio"""
+    samples, sr, ch = pcm if pcm is not None else _read_at_rate(audio_bytes, rate, level=normalize, edit=edit)
     shown = int(target_kbps) if float(target_kbps).is_integer() else target_kbps
     mb = meta.cli_metadata(samples.size, sr, ch, _wav_source_format(audio_bytes), True, 0.0, shown, 5, title, artist, album,
                            encoding_time)
@@ -291,6 +366,22 @@ def main(argv=None) -> int:
     e.add_argument("--title", default=None, help="Title metadata")
     e.add_argument("--artist", default=None, help="Artist metadata")
     e.add_argument("--album", default=None, help="Album metadata")
+    ed = sub.add_parser("edit", help="Cut, pad, fade and remix a WAV file on the device")
+    ed.add_argument("input")
+    ed.add_argument("output")
+    ed.add_argument("--channels", type=int, default=None, help="Output channels of --matrix")
+    ed.add_argument("--matrix", default=None, help="Comma-separated mix matrix, one row per output channel")
+    ed.add_argument("--start", type=float, default=None, help="Start of the cut in seconds")
+    ed.add_argument("--duration", type=float, default=None, help="Length of the cut in seconds")
+    ed.add_argument("--pre-ms", type=float, default=0.0, help="Keep this much in front of the active range")
+    ed.add_argument("--post-ms", type=float, default=0.0, help="Keep this much behind the active range")
+    ed.add_argument("--fade-in", type=float, default=0.0, help="Linear fade-in in milliseconds")
+    ed.add_argument("--fade-out", type=float, default=0.0, help="Linear fade-out in milliseconds")
+    ed.add_argument("--pad-head", type=float, default=0.0, help="Seconds of silence in front of the cut")
+    ed.add_argument("--pad-tail", type=float, default=0.0, help="Seconds of silence behind the cut")
+    for p_ in (e, ed):
+        p_.add_argument("--mono", action="store_true", help="Average the channels into one on the device")
+        p_.add_argument("--trim-silence", type=float, default=None, metavar="DB", help="Cut to the range of samples above DB dBFS")
     nm = sub.add_parser("normalize", help="Bring a WAV file to a loudness under a true-peak ceiling on the device")
     nm.add_argument("input")
     nm.add_argument("output")
@@ -348,16 +439,24 @@ def main(argv=None) -> int:
             print(f"  Sample rate: {sr} Hz")
             print(f"  Channels: {ch}")
             print(f"  Duration: {samples.size / ch / sr:.2f}s")
+            edit = edit_options(mono=a.mono, trim_silence=a.trim_silence)
+            level = level_options(a.lufs, a.ceiling, a.limit)
+            pcm = None
+            if edit is not None:
+                print("Editing on the device...")
             if a.rate is not None and a.rate != sr:
                 print(f"Converting to {a.rate} Hz...")
-                samples, sr, ch = _read_at_rate(audio, a.rate)
-            level = level_options(a.lufs, a.ceiling, a.limit)
+                if edit is None:
+                    samples, sr, ch = _read_at_rate(audio, a.rate)
             if level is not None:
                 print(f"Normalising to {a.lufs:g} LUFS under {a.ceiling:g} dBTP{' (limiter)' if a.limit else ''}...")
+            if edit is not None:   # the edit runs once: what it makes is converted, levelled and handed to the encode
+                pcm = samples, sr, ch = _read_at_rate(audio, a.rate, level=level, edit=edit)
+                print(f"  Edited: {ch} channels, {samples.size / ch / sr:.2f}s")
             lossy = a.lossy or a.transform
             if a.target_kbps is not None:
                 print(f"Encoding to flo (lossy, at most {a.target_kbps:g} kbps, measured)...")
-                flo, info = encode_to_target(audio, a.target_kbps, a.title, a.artist, a.album, rate=a.rate, normalize=level)
+                flo, info = encode_to_target(audio, a.target_kbps, a.title, a.artist, a.album, rate=a.rate, normalize=level, pcm=pcm)
                 secs = samples.size / ch / sr
                 print(f"  Quality: {info['quality']:.4f} (candidate {info['index']}){'' if info['fits'] else ' - the target is below the smallest file'}")
                 print(f"  Achieved: {(len(flo) * 8 / 1000 / secs) if secs else 0.0:.1f} kbps ({len(flo)} of {info['target_bytes']} bytes)")
@@ -371,15 +470,33 @@ def main(argv=None) -> int:
                         return 1
                     q = QUALITY[a.quality.lower()]
                     print(f"Encoding to flo (lossy, {a.quality} quality)...")
-                flo = encode_from_audio(audio, a.level, True, q if q is not None else 0.6, a.bitrate, None, a.title, a.artist, a.album, rate=a.rate, normalize=level)
+                flo = encode_from_audio(audio, a.level, True, q if q is not None else 0.6, a.bitrate, None, a.title, a.artist, a.album, rate=a.rate, normalize=level, pcm=pcm)
             else:
                 print("Encoding to flo (lossless)...")
-                flo = encode_from_audio(audio, a.level, title=a.title, artist=a.artist, album=a.album, rate=a.rate, normalize=level)
+                flo = encode_from_audio(audio, a.level, title=a.title, artist=a.artist, album=a.album, rate=a.rate, normalize=level, pcm=pcm)
             open(a.output, "wb").write(flo)
             original = int(samples.size * 4)
             print("Done!")
             print(f"  Output: {a.output}")
             print(f"  Size: {len(flo)} bytes ({original / max(len(flo), 1):.1f}x compression)")
+        elif a.command == "edit":
+            print(f"Reading {a.input}...")
+            audio = open(a.input, "rb").read()
+            samples, sr, ch = read_wav_bytes(audio)
+            print(f"  Sample rate: {sr} Hz")
+            print(f"  Channels: {ch}")
+            print(f"  Duration: {samples.size / ch / sr:.2f}s")
+            opts = edit_options(a.mono, a.channels, a.matrix, a.start, a.duration, a.trim_silence, a.pre_ms, a.post_ms, a.fade_in,
+                                a.fade_out, a.pad_head, a.pad_tail)
+            print("Editing on the device...")
+            wav, info = edit_wav(audio, opts)
+            open(a.output, "wb").write(wav)
+            if "active" in info:
+                print(f"  Active range: frames {info['active'][0]} .. {info['active'][1]}")
+            g = info["segment"]
+            print(f"  Cut: frames {g['start']} .. {g['start'] + g['frames']}, fades {g['fade_in']} / {g['fade_out']}, pads {g['pad_head']} / {g['pad_tail']}")
+            print("Done!")
+            print(f"  Output: {a.output}")
         elif a.command == "resample":
             print(f"Reading {a.input}...")
             audio = open(a.input, "rb").read()

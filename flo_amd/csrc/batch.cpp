@@ -44,13 +44,14 @@ extern "C" void flo_batch_destroy(flo_batch *b) {
     hipStreamSynchronize(b->ctx->stream);
     void *ptrs[] = {b->d_pcm, b->d_plan, b->d_hops, b->d_out, b->d_frame_size, b->d_clip_bytes, b->d_crc, b->d_part, b->d_at,
                     b->d_sprev, b->d_slots, b->d_frame_off, b->d_dbg_coeffs, b->d_dbg_q, b->d_dbg_sfw, b->d_pack_plan, b->d_next, b->d_bmax, b->d_coef,
-                    b->d_crc_ready, b->d_done_q, b->d_inf_mark, b->d_resample, b->d_stamps};
+                    b->d_crc_ready, b->d_done_q, b->d_inf_mark, b->d_resample, b->d_edit, b->d_stamps};
     for (void *p : ptrs)
         if (p) pool_free(p);
     if (b->ev_pack_plan) hipEventDestroy(b->ev_pack_plan);
     if (b->pin_plan) stager_pinned_put(b->ctx->stager, b->pin_plan);
     if (b->pin_sizes) stager_pinned_put(b->ctx->stager, b->pin_sizes);
     if (b->pin_resample) stager_pinned_put(b->ctx->stager, b->pin_resample);
+    if (b->pin_edit) stager_pinned_put(b->ctx->stager, b->pin_edit);
     if (b->ll) lossless_plan_destroy(b->ll);
     delete b;
 }

@@ -1,6 +1,6 @@
 // batch_internal.hpp — the device-resident batch (flo_batch_*, include/flo_hip.h) as the library's source files see it:
 // batch.cpp makes, encodes and releases it; decode.cpp, fidelity.cpp, analysis.cpp, dist.cpp, stages.cpp, stream.cpp,
-// rate.cpp, ladder.cpp and curve_pass.cpp read it; resample.cpp makes one from another. Not part of the C ABI.
+// rate.cpp, ladder.cpp and curve_pass.cpp read it; resample.cpp, normalize.cpp and edit.cpp make one from another. Not part of the C ABI.
 #pragma once
 #include <vector>
 
@@ -65,6 +65,8 @@ struct flo_batch {
     // a batch made by flo_batch_resample (resample.cpp): the filter table and work list of the launch that fills it, device
     // and pinned, kept until the batch goes (the launch is only enqueued)
     void *d_resample = nullptr, *pin_resample = nullptr;
+    // a batch made by flo_batch_edit (edit.cpp): the segments and tile prefix of the launch that fills it, kept likewise
+    void *d_edit = nullptr, *pin_edit = nullptr;
     // lossy clips of n_interleaved % ch != 0 uploaded from the host: the trailing partial sample-frame, which the encoder
     // drops (so it stays out of the device copy) but the analysis covers (flo_batch_analyze_all)
     std::vector<std::vector<float>> tail;

@@ -522,6 +522,51 @@ int flo_batch_normalize(flo_batch *src, const flo_normalize_opts *opts, flo_batc
 int flo_normalize(flo_ctx *ctx, const float *pcm, size_t n_interleaved, uint32_t sample_rate, uint8_t channels,
                   const flo_normalize_opts *opts, float **out, flo_normalize_report *report);
 
+/* ---- trimming, fades, padding and channel remixing: a resident batch becomes a resident batch of cuts, on the device --------
+ * (no counterpart in the reference; DESIGN 4.15 has the definition in full.)
+ * Source: clip i of the source batch has N_i whole sample-frames of Cin channels, x_i[n, c]; a trailing partial sample-frame
+ * is not part of it. Output clip k is one cut of one source clip, described by segment k: T = pad_head + frames + pad_tail
+ * frames of Cout channels. Any number of segments may name the same source clip, overlapping or not; they are independent.
+ * Output frame t, with u = t - pad_head: where u < 0, u >= frames or start + u >= N_clip, every channel is +0.0 (not the mix
+ * of zeros: a negative coefficient would make -0.0). Otherwise, with n = start + u:
+ *   mix: matrix NULL (only with Cout == Cin): y[j] = x[n, j], bit for bit. With a matrix m[Cout][Cin] (row-major f32, every
+ *     entry finite, Cin and Cout in 1 .. 8): a = fl32(m[j][0] * x[n, 0]), then a = fmaf(m[j][i], x[n, i], a) for
+ *     i = 1 .. Cin - 1 in that order, y[j] = a. The first step is a plain product, so m = [[1]] keeps -0.0.
+ *   fade: fade_in and fade_out are each <= frames and < 2^24, so every integer below converts to f32 exactly.
+ *     w_in = fl32((float)u / (float)fade_in) if u < fade_in; with v = frames - 1 - u, w_out = fl32((float)v / (float)fade_out)
+ *     if v < fade_out; both IEEE divisions. Neither applies: out = y, no multiplication. One applies: out = fl32(y * w).
+ *     Both apply: out = fl32(y * fl32(w_in * w_out)).
+ * Active range: frame n of a clip is active when !(fabsf(x[n, c]) <= threshold) for some channel c (a NaN sample is active).
+ *   first = the smallest active frame, end = the largest active frame plus one; first = end = 0 for a clip without one.
+ *   threshold must be >= 0 and not NaN; +inf is allowed.
+ * FLO_ERR_ARG with a message that names the quantity: clip >= n_clips; reserved != 0; fade_in or fade_out longer than
+ *   frames or >= 2^24; matrix NULL with out_channels != the source's channels; a non-finite matrix entry; in_channels or
+ *   out_channels above 8 with a matrix; out_channels above 8 for a lossy batch; a T * out_channels that overflows what
+ *   flo_batch_create accepts; a threshold that is negative or NaN.
+ * flo_batch_edit: a new batch of the same mode, rate, quality / level and bit depth as src with out_channels channels and
+ *   n_out clips, made by one launch (enqueued on the ctx stream; flo_batch_sync on either batch orders it). The work list
+ *   lives in pinned and device memory that the new batch owns until it is destroyed. The source batch stays valid and
+ *   unchanged; n_out == 0 gives a batch of no clips; an output clip does not depend on the batch around it. The new batch
+ *   behaves like an uploaded one: it encodes, analyses, resamples and normalises like any other.
+ * flo_batch_active_range: first[i], end[i] of every clip, [n_clips] each. Synchronous.
+ * flo_edit: one clip from host memory and back (upload, the same kernel, fetch): *out (*n_out interleaved samples)
+ *   malloc'ed, flo_free.
+ * flo_edit_tile_frames: host only, no context: the output frames one workgroup of the kernel makes for this pair of channel
+ *   counts (out_channels >= 1). The tiles of an output clip start at multiples of it. */
+typedef struct flo_edit_segment {
+    uint64_t start, frames;       /* source frames [start, start + frames) of clip `clip`; may reach past its end */
+    uint32_t clip;
+    uint32_t pad_head, pad_tail;  /* frames of +0.0 in front of and behind the cut */
+    uint32_t fade_in, fade_out;   /* linear, in frames of the cut; 0 = none */
+    uint32_t reserved;            /* must be 0 */
+} flo_edit_segment;               /* 40 bytes */
+int flo_batch_edit(flo_batch *src, size_t n_out, const flo_edit_segment *segs, uint8_t out_channels,
+                   const float *matrix /* NULL: copy */, flo_batch **out);
+int flo_batch_active_range(flo_batch *b, float threshold, uint64_t *first, uint64_t *end);
+int flo_edit(flo_ctx *ctx, const float *pcm, size_t n_interleaved, uint32_t sample_rate, uint8_t channels,
+             const flo_edit_segment *seg, uint8_t out_channels, const float *matrix, float **out, size_t *n_out);
+int flo_edit_tile_frames(uint8_t in_channels, uint8_t out_channels, uint32_t *frames);
+
 /* ---- spectral similarity: spectral_similarity (core/analysis.rs:395-437, exported as spectral_similarity_score,
  * lib.rs:1357) over fingerprint sets ----------------------------------------------------------------------------------
  * flo_fingerprint is SpectralFingerprint (analysis.rs:10-26): what flo_analyze / flo_batch_analyze_all return in those
