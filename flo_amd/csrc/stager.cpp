@@ -107,6 +107,13 @@ static bool ensure_ring(Stager *s, std::string &err) {
     for (int i = 0; i < kSlots; i++) {
         if (hipHostMalloc((void **)&s->slot[i], kSlotBytes) != hipSuccess ||
             hipEventCreateWithFlags(&s->ev[i], hipEventDisableTiming) != hipSuccess) {
+            // all or nothing: slot[0] says "the ring exists", so a partly made ring must not stay behind
+            for (int j = 0; j <= i; j++) {
+                if (s->ev[j]) hipEventDestroy(s->ev[j]);
+                if (s->slot[j]) hipHostFree(s->slot[j]);
+                s->ev[j] = nullptr;
+                s->slot[j] = nullptr;
+            }
             err = "pinned staging ring: allocation failed";
             return false;
         }
@@ -209,6 +216,7 @@ static void probe(Stager *s) {
         for (size_t o = 0; o < kProbeBytes; o += (size_t)4 << 20) segs.push_back({(char *)dev + o, host + o, (size_t)4 << 20});
         double t[2] = {0, 0};
         bool ok = ensure_ring(s, err);
+        if (!ok) s->large_path = 1;   // no ring on this host now: the runtime's own path needs nothing of ours
         for (int pass = 0; ok && pass < 2; pass++)        // the first pass warms both paths up (page tables, threads)
             for (int which = 0; ok && which < 2; which++) {
                 const auto t0 = std::chrono::steady_clock::now();

@@ -5,7 +5,9 @@
 // reads pageable memory slowly on some hosts and at nearly the PCIe rate on others, so large uploads take whichever of two
 // paths a one-time probe finds faster on this host: the runtime's pageable copy straight from the caller's memory, or a
 // ring of pinned buffers that a few worker threads fill slice by slice (one core cannot feed PCIe gen5) while the copy
-// engine drains the previous slot; a single clip always goes direct; downloads come back as one pinned transfer per batch.
+// engine drains the previous slot; a call whose segments total 8 MiB or less always goes direct, however many clips it
+// holds, and a single clip above that takes the probed path like any other upload; downloads come back as one pinned
+// transfer per batch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

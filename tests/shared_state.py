@@ -43,9 +43,12 @@ SHARED = [
     (r"encode_one\(.*\)::trace", "one-time initialisation", "whether FLO_TRACE was set at the first one-shot encode (const afterwards)",
      "first use, raced: one-shot lossy encodes"),
     (r"flo::stager_upload\(.*\)::small_limit", "one-time initialisation", "the upload size below which no ring is used (const afterwards)",
-     "same scenario on every context: the batches"),
+     "same scenario on every context: the batches; set to 0 in a child process of its own by "
+     "tests/test_gpu_upload_paths.py::test_every_upload_through_the_ring_in_a_fresh_process"),
     (r"flo::upload_direct\(.*\)::two", "one-time initialisation", "whether large uploads use two copy threads (const afterwards)",
-     "tests/test_gpu_late_streams.py::test_upload_encode_fetch_rounds (one thread)"),
+     "tests/test_gpu_late_streams.py::test_upload_encode_fetch_rounds (one thread); set in a child process of its own by "
+     "tests/test_gpu_upload_paths.py::test_the_split_upload_in_a_fresh_process, and in the second run of "
+     "tests/test_stager_paths_cpu.py"),
     # per thread
     (r"g_create_err(\[abi:cxx11\])?", "thread_local", "flo_ctx_create's error text", "error text stays with its owner"),
 ]
