@@ -12,6 +12,7 @@
 // device, in the host's order of additions, so that only O(blocks + peaks) per clip comes back.
 // Compiled with -ffp-contract=off.
 #include "analysis_device.hpp"
+#include "clip_tiles.hpp"
 #include "stream_delay.hpp"
 
 namespace flo {
@@ -31,13 +32,7 @@ namespace flo {
 __device__ __forceinline__ const AnalysisArgs &an_clip(const AnalysisArgs *__restrict__ clips, const unsigned int *__restrict__ pre,
                                                        unsigned n_clips, int L, unsigned &wg) {
     const unsigned *p = pre + (unsigned long long)L * (n_clips + 1u);
-    const unsigned b = blockIdx.x;
-    unsigned lo = 0, hi = n_clips;   // p[lo] <= b < p[hi]
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (p[mid] <= b) lo = mid;
-        else hi = mid;
-    }
+    const unsigned b = blockIdx.x, lo = tile_clip(p, n_clips, b);
     wg = b - p[lo];
     return clips[lo];
 }

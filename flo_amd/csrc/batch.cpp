@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 #include "batch_internal.hpp"
 #include "curve_pass.hpp"
@@ -44,16 +45,63 @@ extern "C" void flo_batch_destroy(flo_batch *b) {
     hipStreamSynchronize(b->ctx->stream);
     void *ptrs[] = {b->d_pcm, b->d_plan, b->d_hops, b->d_out, b->d_frame_size, b->d_clip_bytes, b->d_crc, b->d_part, b->d_at,
                     b->d_sprev, b->d_slots, b->d_frame_off, b->d_dbg_coeffs, b->d_dbg_q, b->d_dbg_sfw, b->d_pack_plan, b->d_next, b->d_bmax, b->d_coef,
-                    b->d_crc_ready, b->d_done_q, b->d_inf_mark, b->d_resample, b->d_edit, b->d_stamps};
+                    b->d_crc_ready, b->d_done_q, b->d_inf_mark, b->d_work, b->d_stamps};
     for (void *p : ptrs)
         if (p) pool_free(p);
     if (b->ev_pack_plan) hipEventDestroy(b->ev_pack_plan);
     if (b->pin_plan) stager_pinned_put(b->ctx->stager, b->pin_plan);
     if (b->pin_sizes) stager_pinned_put(b->ctx->stager, b->pin_sizes);
-    if (b->pin_resample) stager_pinned_put(b->ctx->stager, b->pin_resample);
-    if (b->pin_edit) stager_pinned_put(b->ctx->stager, b->pin_edit);
+    if (b->pin_work) stager_pinned_put(b->ctx->stager, b->pin_work);
     if (b->ll) lossless_plan_destroy(b->ll);
     delete b;
+}
+
+int batch_derive(const flo_batch *src, size_t n_out, const size_t *n_il, uint32_t sr, uint8_t ch, flo_batch **out) {
+    int rc = flo_batch_create(src->ctx, src->mode, n_out, n_il, sr, ch, src->qol, out);
+    if (rc != FLO_OK) return rc;
+    (*out)->bit_depth = src->bit_depth;
+    (*out)->exact = src->exact;
+    return FLO_OK;
+}
+
+std::vector<uint64_t> batch_whole_frames(const flo_batch *b) {
+    std::vector<uint64_t> frames(b->n_clips);
+    for (size_t i = 0; i < b->n_clips; i++) frames[i] = b->n_il[i] / b->ch;
+    return frames;
+}
+
+int batch_no_pcm(const flo_batch *b, const char *who) { return fail(b->ctx, FLO_ERR_STATE, std::string(who) + ": the batch holds no PCM yet"); }
+
+int work_block_get(flo_ctx *c, size_t bytes, const char *what, void *&pin, void *&dev) {
+    std::string perr;
+    pin = stager_pinned_get(c->stager, bytes, perr);
+    if (!pin) return fail(c, FLO_ERR_NOMEM, perr);
+    hipError_t e = pool_alloc(&dev, bytes);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? FLO_ERR_NOMEM : FLO_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    return FLO_OK;
+}
+
+int batch_one_shot(flo_ctx *c, const char *who, const float *pcm, size_t n_il, uint32_t sr, uint8_t ch,
+                   const std::function<int(flo_batch *, flo_batch **)> &op, float **out, size_t *n_out) {
+    std::unique_ptr<float, decltype(&free)> res(nullptr, free);   // (freed behind the batches, whose destruction waits for the stream)
+    BatchHold a, b;                                               // (b goes first)
+    int rc = flo_batch_create(c, FLO_MODE_LOSSLESS, 1, &n_il, sr, ch, 0, &a.b);
+    if (rc != FLO_OK) return rc;
+    rc = flo_batch_upload(a.b, 0, pcm);
+    if (rc != FLO_OK) return rc;
+    rc = op(a.b, &b.b);
+    if (rc != FLO_OK) return rc;
+    const size_t floats = b.b->n_il[0];
+    res.reset((float *)malloc(floats ? floats * sizeof(float) : 1));
+    if (!res) return fail(c, FLO_ERR_NOMEM, "out of memory");
+    if (floats) {
+        hipError_t e = hipMemcpyAsync(res.get(), b.b->d_pcm + b.b->clip_off[0], floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return fail(c, FLO_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    *out = res.release();
+    if (n_out) *n_out = floats;
+    return FLO_OK;
 }
 
 extern "C" int flo_batch_create(flo_ctx *c, int mode, size_t n_clips, const size_t *n_interleaved, uint32_t sr,

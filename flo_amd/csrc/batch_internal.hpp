@@ -1,7 +1,9 @@
 // batch_internal.hpp — the device-resident batch (flo_batch_*, include/flo_hip.h) as the library's source files see it:
 // batch.cpp makes, encodes and releases it; decode.cpp, fidelity.cpp, analysis.cpp, dist.cpp, stages.cpp, stream.cpp,
-// rate.cpp, ladder.cpp and curve_pass.cpp read it; resample.cpp, normalize.cpp and edit.cpp make one from another. Not part of the C ABI.
+// rate.cpp, ladder.cpp and curve_pass.cpp read it; resample.cpp, normalize.cpp and edit.cpp make one from another, through
+// the helpers at the end of this file. Not part of the C ABI.
 #pragma once
+#include <functional>
 #include <vector>
 
 #include "ctx_internal.hpp"
@@ -62,11 +64,9 @@ struct flo_batch {
     std::vector<uint32_t> h_frame_size;
     // lossless
     LosslessPlan *ll = nullptr;
-    // a batch made by flo_batch_resample (resample.cpp): the filter table and work list of the launch that fills it, device
-    // and pinned, kept until the batch goes (the launch is only enqueued)
-    void *d_resample = nullptr, *pin_resample = nullptr;
-    // a batch made by flo_batch_edit (edit.cpp): the segments and tile prefix of the launch that fills it, kept likewise
-    void *d_edit = nullptr, *pin_edit = nullptr;
+    // a batch made from another by a launch that is only enqueued (flo_batch_resample, flo_batch_edit): that launch's work
+    // block (work_block_get), device and pinned, kept until the batch goes
+    void *d_work = nullptr, *pin_work = nullptr;
     // lossy clips of n_interleaved % ch != 0 uploaded from the host: the trailing partial sample-frame, which the encoder
     // drops (so it stays out of the device copy) but the analysis covers (flo_batch_analyze_all)
     std::vector<std::vector<float>> tail;
@@ -80,6 +80,37 @@ struct flo_batch {
 
 // all clips of a batch from host buffers, through the pinned staging ring (batch.cpp)
 int batch_upload_all(flo_batch *b, const float *const *pcm, hipStream_t stream = nullptr);
+
+// ---- one batch made from another (resample.cpp, normalize.cpp, edit.cpp; all of these are batch.cpp's) -----------------
+// A new batch of n_out clips of n_il[k] floats each at `sr` and `ch`, otherwise like src: its mode and quality (or level),
+// its bit_depth and exact. The one place that knows what a derived batch inherits.
+int batch_derive(const flo_batch *src, size_t n_out, const size_t *n_il, uint32_t sr, uint8_t ch, flo_batch **out);
+// ... on its way to the caller: destroyed on scope exit (which waits for the stream first) unless released
+struct BatchHold {
+    flo_batch *b = nullptr;
+    ~BatchHold() {
+        if (b) flo_batch_destroy(b);
+    }
+    flo_batch *release() {
+        flo_batch *r = b;
+        b = nullptr;
+        return r;
+    }
+};
+// n_il[i] / ch of every clip, whole sample-frames: a kept partial frame (flo_batch::tail) is not carried over
+std::vector<uint64_t> batch_whole_frames(const flo_batch *b);
+// FLO_ERR_STATE with "<who>: the batch holds no PCM yet"
+int batch_no_pcm(const flo_batch *b, const char *who);
+// The work block of a launch that is only enqueued: `bytes` of pinned memory from the stager to fill, and a pool block to
+// copy them into. Each is recorded in the caller's pair as soon as it exists, so the owner releases what there is: a batch
+// passes its own pair (pin_work, d_work; flo_batch_destroy), flo_resample its locals. Pool errors read "<what>: <HIP's text>".
+int work_block_get(flo_ctx *c, size_t bytes, const char *what, void *&pin, void *&dev);
+// One host clip through a batch operation and back: a one-clip lossless batch of `n_il` floats is made and uploaded, op
+// makes another from it, and clip 0 of that comes back as a malloc'd block of *n_out floats (n_out nullable). Both batches
+// are gone on return. Device errors of the copy back read "<who>: <HIP's text>".
+int batch_one_shot(flo_ctx *c, const char *who, const float *pcm, size_t n_il, uint32_t sr, uint8_t ch,
+                   const std::function<int(flo_batch *, flo_batch **)> &op, float **out, size_t *n_out);
+
 // The frame and clip tables of a synced lossy batch's decode, read from the encoder's own records: clip i's PCM at
 // co[i] floats, `total` floats in all (decode.cpp: flo_batch_decode, and the fidelity reports' fused pass)
 int batch_lossy_tables(flo_batch *b, std::vector<unsigned long long> &blob_off, std::vector<unsigned int> &blob_len,

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -57,6 +58,13 @@ struct flo_ctx {
 
 // sets the context's error text and returns `code` (context.cpp)
 int fail(flo_ctx *c, int code, const std::string &msg);
+// the message of an entry point that has no context: into the caller's buffer (nullable), cut to its size
+inline void put_err(char *err, size_t cap, const std::string &m) {
+    if (err && cap) {
+        strncpy(err, m.c_str(), cap - 1);
+        err[cap - 1] = 0;
+    }
+}
 // the text behind flo_last_create_error: failures that have no context to carry it (context.cpp)
 extern thread_local std::string g_create_err;
 // releases flo_ctx::sdec (sdec.cpp)

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "batch_internal.hpp"
+#include "clip_tiles.hpp"
 #include "devmem.hpp"
 #include "edit_kernels.hpp"
 #include "edit_plan.hpp"
@@ -21,8 +22,8 @@ extern "C" int flo_batch_edit(flo_batch *src, size_t n_out, const flo_edit_segme
     *out = nullptr;
     flo_ctx *c = src->ctx;
     const uint8_t cin = src->ch, cout = out_channels;
-    std::vector<uint64_t> n_src(src->n_clips), T;
-    for (size_t i = 0; i < src->n_clips; i++) n_src[i] = src->n_il[i] / cin;   // whole sample-frames, as flo_batch_resample
+    const std::vector<uint64_t> n_src = batch_whole_frames(src);
+    std::vector<uint64_t> T;
     EditSource S;
     S.n_clips = src->n_clips;
     S.clip_frames = n_src.data();
@@ -30,32 +31,25 @@ extern "C" int flo_batch_edit(flo_batch *src, size_t n_out, const flo_edit_segme
     S.lossy = src->mode == FLO_MODE_LOSSY;
     std::string m;
     if (!edit_check(S, n_out, segs, cout, matrix, T, m)) return fail(c, FLO_ERR_ARG, "flo_batch_edit: " + m);
-    if (n_out && !src->pcm_written) return fail(c, FLO_ERR_STATE, "flo_batch_edit: the batch holds no PCM yet");
+    if (n_out && !src->pcm_written) return batch_no_pcm(src, "flo_batch_edit");
     std::vector<size_t> n_il(n_out);
     for (size_t k = 0; k < n_out; k++) n_il[k] = (size_t)(T[k] * cout);
-    flo_batch *b = nullptr;
-    int rc = flo_batch_create(c, src->mode, n_out, n_il.data(), src->sr, cout, src->qol, &b);
+    BatchHold made;
+    int rc = batch_derive(src, n_out, n_il.data(), src->sr, cout, &made.b);
     if (rc != FLO_OK) return rc;
-    b->bit_depth = src->bit_depth;
-    b->exact = src->exact;
-    auto leave = [&](int code) {
-        if (code != FLO_OK) flo_batch_destroy(b);   // (waits for the stream first)
-        else *out = b;
-        return code;
-    };
-    const uint32_t F = edit_tile_frames(cout);
+    flo_batch *b = made.b;
     std::vector<uint32_t> pre;
-    if (!edit_tiles(T.data(), n_out, F, pre) || n_out > 0x7FFFFFFFull) return leave(fail(c, FLO_ERR_ARG, "flo_batch_edit: too many tiles for one launch"));
+    if (!clip_tiles(T.data(), n_out, edit_tile_frames(cout), pre)) return fail(c, FLO_ERR_ARG, "flo_batch_edit: too many tiles for one launch");
     if (n_out && pre[n_out]) {
         hipError_t e = hipSetDevice(c->device);
-        if (e != hipSuccess) return leave(fail(c, FLO_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(c, FLO_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
         // segments | pre: up through pinned memory into a pool block, both the new batch's until it goes
-        const size_t seg_bytes = n_out * sizeof(EditSeg), bytes = seg_bytes + (n_out + 1) * 4;
-        std::string perr;
-        uint8_t *host = (uint8_t *)stager_pinned_get(c->stager, bytes, perr);
-        if (!host) return leave(fail(c, FLO_ERR_NOMEM, perr));
-        b->pin_edit = host;
-        EditSeg *hs = (EditSeg *)host;
+        BlockLayout B;
+        const size_t o_segs = B.take(n_out * sizeof(EditSeg)), o_pre = B.take((n_out + 1) * 4);
+        rc = work_block_get(c, B.bytes, "flo_batch_edit: work list", b->pin_work, b->d_work);
+        if (rc != FLO_OK) return rc;
+        void *const host = b->pin_work, *const dev = b->d_work;
+        EditSeg *hs = B.at<EditSeg>(host, o_segs);
         for (size_t k = 0; k < n_out; k++) {
             const flo_edit_segment &g = segs[k];
             EditSeg s{};
@@ -70,19 +64,14 @@ extern "C" int flo_batch_edit(flo_batch *src, size_t n_out, const flo_edit_segme
             s.fade_out = g.fade_out;
             hs[k] = s;
         }
-        memcpy(host + seg_bytes, pre.data(), (n_out + 1) * 4);
-        uint8_t *dev = nullptr;
-        e = pool_alloc(&dev, bytes);
-        if (e != hipSuccess)
-            return leave(fail(c, e == hipErrorOutOfMemory ? FLO_ERR_NOMEM : FLO_ERR_DEVICE, std::string("flo_batch_edit: work list: ") + hipGetErrorString(e)));
-        b->d_edit = dev;
-        e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) return leave(fail(c, FLO_ERR_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(e)));
+        memcpy(B.at<uint32_t>(host, o_pre), pre.data(), (n_out + 1) * 4);
+        e = hipMemcpyAsync(dev, host, B.bytes, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return fail(c, FLO_ERR_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
         EditArgs A;
         A.src = src->d_pcm;
         A.dst = b->d_pcm;
-        A.segs = (const EditSeg *)dev;
-        A.pre = (const unsigned int *)(dev + seg_bytes);
+        A.segs = B.at<const EditSeg>(dev, o_segs);
+        A.pre = B.at<const unsigned int>(dev, o_pre);
         A.n_segs = (unsigned)n_out;
         A.cin = cin;
         A.cout = cout;
@@ -90,10 +79,11 @@ extern "C" int flo_batch_edit(flo_batch *src, size_t n_out, const flo_edit_segme
         const EditForm form = !matrix ? kEditCopy : cin == 2 && cout == 1 ? kEditTwoToOne : cin == 1 && cout == 2 ? kEditOneToTwo : kEditGeneric;
         static const char *const names[] = {"edit_copy", "edit_2to1", "edit_1to2", "edit_mix"};
         rc = timed_launch(c, names[form], [&] { return launch_edit(A, form, pre[n_out], c->stream); });
-        if (rc != FLO_OK) return leave(rc);
+        if (rc != FLO_OK) return rc;
     }
     b->pcm_written = true;
-    return leave(FLO_OK);
+    *out = made.release();
+    return FLO_OK;
 }
 
 extern "C" int flo_batch_active_range(flo_batch *b, float threshold, uint64_t *first, uint64_t *end) {
@@ -103,18 +93,18 @@ extern "C" int flo_batch_active_range(flo_batch *b, float threshold, uint64_t *f
     if (!edit_threshold(threshold, m)) return fail(c, FLO_ERR_ARG, "flo_batch_active_range: " + m);
     const size_t n = b->n_clips;
     if (!n) return FLO_OK;
-    if (!b->pcm_written) return fail(c, FLO_ERR_STATE, "flo_batch_active_range: the batch holds no PCM yet");
+    if (!b->pcm_written) return batch_no_pcm(b, "flo_batch_active_range");
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> frames(n);
-    for (size_t i = 0; i < n; i++) frames[i] = b->n_il[i] / b->ch;
+    const std::vector<uint64_t> frames = batch_whole_frames(b);
     std::vector<uint32_t> pre;
-    if (!edit_tiles(frames.data(), n, edit_tile_frames(b->ch), pre) || n > 0x7FFFFFFFull)
-        return fail(c, FLO_ERR_ARG, "flo_batch_active_range: too many tiles for one launch");
+    if (!clip_tiles(frames.data(), n, edit_tile_frames(b->ch), pre)) return fail(c, FLO_ERR_ARG, "flo_batch_active_range: too many tiles for one launch");
     for (size_t i = 0; i < n; i++) first[i] = end[i] = 0;
     if (!pre[n]) return FLO_OK;
-    // src_off | frames | first | end | pre in one block that goes up in one copy; first and end start from ~0 and 0 here,
-    // so nothing depends on what the pool block held
-    const size_t o_off = 0, o_frames = n * 8, o_first = 2 * n * 8, o_end = 3 * n * 8, o_pre = 4 * n * 8, bytes = o_pre + (n + 1) * 4;
+    // src_off | frames | first, end | pre in one block that goes up in one copy; first and end start from ~0 and 0 here,
+    // so nothing depends on what the pool block held (and stay one region: they come back in one copy)
+    BlockLayout B;
+    const size_t o_off = B.take(n * 8), o_frames = B.take(n * 8), o_first = B.take(2 * n * 8), o_end = o_first + n * 8, o_pre = B.take((n + 1) * 4),
+                 bytes = B.bytes;
     std::vector<uint8_t> host(bytes, 0);   // (outlives the stream: destroyed behind `quiesce`)
     memcpy(host.data() + o_off, b->clip_off.data(), n * 8);
     memcpy(host.data() + o_frames, frames.data(), n * 8);
@@ -127,11 +117,11 @@ extern "C" int flo_batch_active_range(flo_batch *b, float threshold, uint64_t *f
     HIPCHK(c, hipMemcpyAsync(dev.p, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
     EditActiveArgs A;
     A.src = b->d_pcm;
-    A.src_off = (const unsigned long long *)(dev.p + o_off);
-    A.frames = (const unsigned long long *)(dev.p + o_frames);
-    A.first = (unsigned long long *)(dev.p + o_first);
-    A.end = (unsigned long long *)(dev.p + o_end);
-    A.pre = (const unsigned int *)(dev.p + o_pre);
+    A.src_off = B.at<const unsigned long long>(dev.p, o_off);
+    A.frames = B.at<const unsigned long long>(dev.p, o_frames);
+    A.first = B.at<unsigned long long>(dev.p, o_first);
+    A.end = B.at<unsigned long long>(dev.p, o_end);
+    A.pre = B.at<const unsigned int>(dev.p, o_pre);
     A.n_clips = (unsigned)n;
     A.channels = b->ch;
     A.threshold = threshold;
@@ -154,35 +144,12 @@ extern "C" int flo_edit(flo_ctx *c, const float *pcm, size_t n_interleaved, uint
     *n_out = 0;
     if (channels < 1) return fail(c, FLO_ERR_ARG, "flo_edit: channels must be at least 1");
     if (!sample_rate) return fail(c, FLO_ERR_ARG, "flo_edit: sample_rate must be non-zero");
-    const size_t whole = n_interleaved / channels * channels;
-    flo_batch *a = nullptr, *b = nullptr;
-    float *res = nullptr;
-    auto leave = [&](int code) {
-        if (b) flo_batch_destroy(b);
-        if (a) flo_batch_destroy(a);
-        if (code != FLO_OK) free(res);
-        else *out = res;
-        return code;
-    };
-    int rc = flo_batch_create(c, FLO_MODE_LOSSLESS, 1, &whole, sample_rate, channels, 0, &a);
-    if (rc != FLO_OK) return leave(rc);
-    rc = flo_batch_upload(a, 0, pcm);
-    if (rc != FLO_OK) return leave(rc);
-    rc = flo_batch_edit(a, 1, seg, out_channels, matrix, &b);
-    if (rc != FLO_OK) {
-        const std::string msg = c->err;   // "flo_batch_edit: ..." reads "flo_edit: ..." here
-        const std::string from = "flo_batch_edit: ";
-        if (msg.compare(0, from.size(), from) == 0) fail(c, rc, "flo_edit: " + msg.substr(from.size()));
-        return leave(rc);
-    }
-    const size_t floats = b->n_il[0];
-    res = (float *)malloc(floats ? floats * sizeof(float) : 1);
-    if (!res) return leave(fail(c, FLO_ERR_NOMEM, "out of memory"));
-    if (floats) {
-        hipError_t e = hipMemcpyAsync(res, b->d_pcm + b->clip_off[0], floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return leave(fail(c, FLO_ERR_DEVICE, std::string("flo_edit: ") + hipGetErrorString(e)));
-    }
-    *n_out = floats;
-    return leave(FLO_OK);
+    return batch_one_shot(c, "flo_edit", pcm, n_interleaved / channels * channels, sample_rate, channels, [&](flo_batch *a, flo_batch **b) {
+        const int rc = flo_batch_edit(a, 1, seg, out_channels, matrix, b);
+        if (rc != FLO_OK) {
+            const std::string msg = c->err, from = "flo_batch_edit: ";   // "flo_batch_edit: ..." reads "flo_edit: ..." here
+            if (msg.compare(0, from.size(), from) == 0) fail(c, rc, "flo_edit: " + msg.substr(from.size()));
+        }
+        return rc;
+    }, out, n_out);
 }

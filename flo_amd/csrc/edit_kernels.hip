@@ -15,6 +15,7 @@
 //
 // All forms share ed_mix and ed_weight, so the order of operations is the definition's in every form.
 // Compiled with -ffp-contract=off; the FMAs are explicit, the products single multiplications, the divisions IEEE.
+#include "clip_tiles.hpp"
 #include "edit_kernels.hpp"
 
 namespace flo {
@@ -22,17 +23,6 @@ namespace flo {
 typedef float ed_v4f __attribute__((ext_vector_type(4)));
 typedef float ed_v2f __attribute__((ext_vector_type(2)));
 typedef unsigned int ed_v4u __attribute__((ext_vector_type(4)));
-
-// pre[lo] <= b < pre[lo + 1]: the last such lo, a clip that has tiles
-__device__ __forceinline__ unsigned ed_find_clip(const unsigned *__restrict__ pre, unsigned n, unsigned b) {
-    unsigned lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (pre[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // y[j] of one frame: a = fl32(m[j][0] * x[0]), then a = fmaf(m[j][i], x[i], a) for i = 1 .. cin - 1
 template <unsigned MAXC>
@@ -159,7 +149,7 @@ __device__ __forceinline__ void ed_zero_tile(float *__restrict__ dp, unsigned n,
 template <int FORM>
 __global__ __launch_bounds__(kEditThreads) void edit_kernel(const EditArgs A) {
     const unsigned tid = threadIdx.x;
-    const unsigned k = ed_find_clip(A.pre, A.n_segs, blockIdx.x);
+    const unsigned k = tile_clip(A.pre, A.n_segs, blockIdx.x);
     const unsigned tile = blockIdx.x - A.pre[k];
     const EditSeg *__restrict__ segs = A.segs;
     const EditSeg s = segs[k];
@@ -226,7 +216,7 @@ __global__ __launch_bounds__(kEditThreads) void edit_kernel(const EditArgs A) {
 __global__ __launch_bounds__(kEditThreads) void edit_active_kernel(const EditActiveArgs A) {
     __shared__ unsigned red_lo[kEditThreads / 64], red_hi[kEditThreads / 64];
     const unsigned tid = threadIdx.x;
-    const unsigned clip = ed_find_clip(A.pre, A.n_clips, blockIdx.x);
+    const unsigned clip = tile_clip(A.pre, A.n_clips, blockIdx.x);
     const unsigned tile = blockIdx.x - A.pre[clip];
     const unsigned long long *__restrict__ frames = A.frames, *__restrict__ src_off = A.src_off;
     const unsigned long long n = frames[clip];

@@ -13,7 +13,7 @@ struct EditArgs {
     const float *src = nullptr;   // interleaved f32: segment k's source clip at src + segs[k].src_off
     float *dst = nullptr;         // output clip k at dst + segs[k].dst_off; nothing else is written
     const EditSeg *segs = nullptr;       // [n_segs]
-    const unsigned int *pre = nullptr;   // [n_segs + 1] tiles in front of every output clip (edit_tiles)
+    const unsigned int *pre = nullptr;   // [n_segs + 1] tiles in front of every output clip (clip_tiles)
     unsigned int n_segs = 0, cin = 0, cout = 0;
     float m[kEditMaxMix * kEditMaxMix] = {};   // rows of kEditMaxMix (edit_matrix_rows); unused by the copy form
 };

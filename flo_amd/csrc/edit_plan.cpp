@@ -51,18 +51,6 @@ bool edit_threshold(float threshold, std::string &err) {
     return true;
 }
 
-bool edit_tiles(const uint64_t *frames, size_t n, uint32_t F, std::vector<uint32_t> &pre) {
-    pre.assign(n + 1, 0);
-    uint64_t t = 0;
-    for (size_t i = 0; i < n; i++) {
-        pre[i] = (uint32_t)t;
-        t += frames[i] / F + (frames[i] % F ? 1 : 0);
-        if (t > 0x7FFFFFFFull) return false;
-    }
-    pre[n] = (uint32_t)t;
-    return true;
-}
-
 void edit_matrix_rows(const float *matrix, uint32_t in_channels, uint32_t out_channels, float (&rows)[kEditMaxMix * kEditMaxMix]) {
     for (uint32_t i = 0; i < kEditMaxMix * kEditMaxMix; i++) rows[i] = 0.0f;
     if (!matrix) return;

@@ -81,9 +81,7 @@ bool edit_check(const EditSource &src, size_t n_out, const flo_edit_segment *seg
                 std::vector<uint64_t> &T, std::string &err);
 // threshold >= 0 and not NaN
 bool edit_threshold(float threshold, std::string &err);
-// The flat work list: pre[k] = tiles of clips 0 .. k - 1 of `frames` each cut into tiles of F (n + 1 entries); false when a
-// launch cannot hold them.
-bool edit_tiles(const uint64_t *frames, size_t n, uint32_t F, std::vector<uint32_t> &pre);
+// (the flat work list of a launch: clip_tiles of every clip's frames in tiles of edit_tile_frames(Cout), clip_tiles.hpp)
 // The matrix as the kernel takes it: rows of kEditMaxMix, zeros elsewhere (a checked matrix)
 void edit_matrix_rows(const float *matrix, uint32_t in_channels, uint32_t out_channels, float (&rows)[kEditMaxMix * kEditMaxMix]);
 

@@ -8,16 +8,10 @@
 #include <cstring>
 
 #include "batch_internal.hpp"
+#include "clip_tiles.hpp"
 #include "devmem.hpp"
 #include "normalize_kernels.hpp"
 #include "normalize_plan.hpp"
-
-static void put_err(char *err, size_t cap, const std::string &m) {
-    if (err && cap) {
-        strncpy(err, m.c_str(), cap - 1);
-        err[cap - 1] = 0;
-    }
-}
 
 extern "C" int flo_normalize_lookahead(uint32_t rate, const flo_normalize_opts *opts, uint32_t *frames, char *err, size_t err_cap) {
     std::string m;
@@ -47,43 +41,28 @@ extern "C" int flo_normalize_gain(double integrated_lufs, double sample_peak_dbf
 // The lists of one launch over n clips, laid out in one block that goes up in one copy: the table, the 64-bit lists, then
 // the 32-bit ones. `res` .. end of the block is what the kernels write (limited | min_q | peak_bits) and comes back.
 struct NormLists {
-    size_t n = 0, o_table = 0, o_src = 0, o_dst = 0, o_frames = 0, o_limited = 0, o_pre = 0, o_gain = 0, o_copy = 0, o_minq = 0, o_peak = 0, bytes = 0;
+    BlockLayout B;
+    const size_t n, o_table, o_src, o_dst, o_frames, o_pre, o_gain, o_copy, o_limited, o_minq, o_peak, bytes;   // (taken in this order)
     std::vector<uint8_t> host;
-    explicit NormLists(size_t n_clips) : n(n_clips) {
-        size_t o = 0;
-        auto take = [&](size_t b) {
-            const size_t at = o;
-            o += (b + 15) & ~(size_t)15;
-            return at;
-        };
-        o_table = take(kNormPhases * kNormTaps * 4);
-        o_src = take(n * 8);
-        o_dst = take(n * 8);
-        o_frames = take(n * 8);
-        o_pre = take((n + 1) * 4);
-        o_gain = take(n * 4);
-        o_copy = take(n * 4);
-        o_limited = take(n * 8);
-        o_minq = take(n * 4);
-        o_peak = take(n * 4);
-        bytes = o;
-        host.assign(bytes, 0);
-    }
+    explicit NormLists(size_t n_clips)
+        : n(n_clips), o_table(B.take(kNormPhases * kNormTaps * 4)), o_src(B.take(n * 8)), o_dst(B.take(n * 8)), o_frames(B.take(n * 8)),
+          o_pre(B.take((n + 1) * 4)), o_gain(B.take(n * 4)), o_copy(B.take(n * 4)), o_limited(B.take(n * 8)), o_minq(B.take(n * 4)),
+          o_peak(B.take(n * 4)), bytes(B.bytes), host(bytes, 0) {}
     template <class T>
     T *at(size_t off) {
-        return reinterpret_cast<T *>(host.data() + off);
+        return BlockLayout::at<T>(host.data(), off);
     }
     void point(NormArgs &a, uint8_t *dev) const {
-        a.table = (const float *)(dev + o_table);
-        a.src_off = (const unsigned long long *)(dev + o_src);
-        a.dst_off = (const unsigned long long *)(dev + o_dst);
-        a.frames = (const unsigned long long *)(dev + o_frames);
-        a.pre = (const unsigned int *)(dev + o_pre);
-        a.gain = (const float *)(dev + o_gain);
-        a.copy = (const unsigned int *)(dev + o_copy);
-        a.limited = (unsigned long long *)(dev + o_limited);
-        a.min_q = (unsigned int *)(dev + o_minq);
-        a.peak_bits = (unsigned int *)(dev + o_peak);
+        a.table = BlockLayout::at<const float>(dev, o_table);
+        a.src_off = BlockLayout::at<const unsigned long long>(dev, o_src);
+        a.dst_off = BlockLayout::at<const unsigned long long>(dev, o_dst);
+        a.frames = BlockLayout::at<const unsigned long long>(dev, o_frames);
+        a.pre = BlockLayout::at<const unsigned int>(dev, o_pre);
+        a.gain = BlockLayout::at<const float>(dev, o_gain);
+        a.copy = BlockLayout::at<const unsigned int>(dev, o_copy);
+        a.limited = BlockLayout::at<unsigned long long>(dev, o_limited);
+        a.min_q = BlockLayout::at<unsigned int>(dev, o_minq);
+        a.peak_bits = BlockLayout::at<unsigned int>(dev, o_peak);
         a.n_clips = (unsigned)n;
     }
 };
@@ -94,7 +73,7 @@ static int norm_peaks(flo_ctx *c, const float *d_pcm, const std::vector<uint64_t
     const size_t n = frames.size();
     linear.assign(n, 0.f);
     std::vector<uint32_t> pre;
-    if (!normalize_tiles(0, frames.data(), n, pre) || n > 0x7FFFFFFFull) return fail(c, FLO_ERR_ARG, "too many tiles for one true-peak launch");
+    if (!clip_tiles(frames.data(), n, norm_tile_frames(0), pre)) return fail(c, FLO_ERR_ARG, "too many tiles for one true-peak launch");
     if (!pre[n]) return FLO_OK;
     NormLists Ls(n);   // (outlives the stream: destroyed behind `quiesce`)
     const std::vector<float> h = normalize_table();
@@ -126,12 +105,10 @@ extern "C" int flo_batch_true_peak(flo_batch *b, float *linear) {
     if (!b || (!linear && b->n_clips)) return FLO_ERR_ARG;
     flo_ctx *c = b->ctx;
     if (!b->n_clips) return FLO_OK;
-    if (!b->pcm_written) return fail(c, FLO_ERR_STATE, "flo_batch_true_peak: the batch holds no PCM yet");
+    if (!b->pcm_written) return batch_no_pcm(b, "flo_batch_true_peak");
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> frames(b->n_clips);
-    for (size_t i = 0; i < b->n_clips; i++) frames[i] = b->n_il[i] / b->ch;
     std::vector<float> out;
-    int rc = norm_peaks(c, b->d_pcm, b->clip_off, frames, b->ch, out);
+    int rc = norm_peaks(c, b->d_pcm, b->clip_off, batch_whole_frames(b), b->ch, out);
     if (rc != FLO_OK) return rc;
     memcpy(linear, out.data(), b->n_clips * sizeof(float));
     return FLO_OK;
@@ -152,14 +129,11 @@ extern "C" int flo_batch_normalize(flo_batch *src, const flo_normalize_opts *opt
     if (!normalize_opts(opts, o, m) || !normalize_lookahead(src->sr, o.lookahead_frames, la, m)) return fail(c, FLO_ERR_ARG, "flo_batch_normalize: " + m);
     const size_t n = src->n_clips;
     const uint8_t ch = src->ch;
-    if (n && !src->pcm_written) return fail(c, FLO_ERR_STATE, "flo_batch_normalize: the batch holds no PCM yet");
+    if (n && !src->pcm_written) return batch_no_pcm(src, "flo_batch_normalize");
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> frames(n);
+    const std::vector<uint64_t> frames = batch_whole_frames(src);
     std::vector<size_t> n_il(n);
-    for (size_t i = 0; i < n; i++) {
-        frames[i] = src->n_il[i] / ch;   // whole sample-frames: a kept partial frame (flo_batch::tail) is not carried over
-        n_il[i] = (size_t)(frames[i] * ch);
-    }
+    for (size_t i = 0; i < n; i++) n_il[i] = (size_t)(frames[i] * ch);
     // the measurements: loudness and sample peak of every clip from the batched analysis, the true peak from the envelope
     std::vector<flo_analysis> an(n ? n : 1);
     std::vector<float> tp;
@@ -176,20 +150,13 @@ extern "C" int flo_batch_normalize(flo_batch *src, const flo_normalize_opts *opt
     std::vector<flo_normalize_report> rep(n);
     for (size_t i = 0; i < n; i++) normalize_gain(an[i].integrated_lufs, an[i].sample_peak_dbfs, tp[i], o, rep[i]);
 
-    flo_batch *b = nullptr;
-    int rc = flo_batch_create(c, src->mode, n, n_il.data(), src->sr, ch, src->qol, &b);
+    BatchHold made;
+    int rc = batch_derive(src, n, n_il.data(), src->sr, ch, &made.b);
     if (rc != FLO_OK) return rc;
-    b->bit_depth = src->bit_depth;
-    b->exact = src->exact;
-    auto leave = [&](int code) {
-        if (code != FLO_OK) flo_batch_destroy(b);   // (waits for the stream first)
-        else *out = b;
-        return code;
-    };
+    flo_batch *b = made.b;
     const bool limit = o.mode == FLO_NORM_LIMIT;
     std::vector<uint32_t> pre;
-    if (!normalize_tiles(limit ? la : 0, frames.data(), n, pre) || n > 0x7FFFFFFFull)
-        return leave(fail(c, FLO_ERR_ARG, "flo_batch_normalize: too many tiles for one launch"));
+    if (!clip_tiles(frames.data(), n, norm_tile_frames(limit ? la : 0), pre)) return fail(c, FLO_ERR_ARG, "flo_batch_normalize: too many tiles for one launch");
     if (n && pre[n]) {
         NormLists Ls(n);   // (outlives the stream: destroyed behind `quiesce`)
         const std::vector<float> h = normalize_table();
@@ -205,9 +172,9 @@ extern "C" int flo_batch_normalize(flo_batch *src, const flo_normalize_opts *opt
         }
         DevBuf<uint8_t> dev;
         QuiesceOnExit quiesce(c);
-        if (!dev.alloc(Ls.bytes)) return leave(fail(c, FLO_ERR_NOMEM, "flo_batch_normalize: device memory"));
+        if (!dev.alloc(Ls.bytes)) return fail(c, FLO_ERR_NOMEM, "flo_batch_normalize: device memory");
         hipError_t e = hipMemcpyAsync(dev.p, Ls.host.data(), Ls.bytes, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) return leave(fail(c, FLO_ERR_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(c, FLO_ERR_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
         NormArgs A;
         A.src = src->d_pcm;
         A.dst = b->d_pcm;
@@ -219,7 +186,7 @@ extern "C" int flo_batch_normalize(flo_batch *src, const flo_normalize_opts *opt
         Ls.point(A, dev.p);
         rc = limit ? timed_launch(c, "norm_limit", [&] { return launch_norm_limit(A, pre[n], c->stream); })
                    : timed_launch(c, "norm_gain", [&] { return launch_norm_gain(A, pre[n], c->stream); });
-        if (rc != FLO_OK) return leave(rc);
+        if (rc != FLO_OK) return rc;
         std::vector<uint64_t> limited(n, 0);
         std::vector<uint32_t> minq(n, kNormUnity);
         if (limit) {
@@ -227,7 +194,7 @@ extern "C" int flo_batch_normalize(flo_batch *src, const flo_normalize_opts *opt
             if (e == hipSuccess) e = hipMemcpyAsync(minq.data(), dev.p + Ls.o_minq, n * 4, hipMemcpyDeviceToHost, c->stream);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return leave(fail(c, FLO_ERR_DEVICE, std::string("flo_batch_normalize: ") + hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(c, FLO_ERR_DEVICE, std::string("flo_batch_normalize: ") + hipGetErrorString(e));
         for (size_t i = 0; i < n; i++) {
             rep[i].limited_frames = limited[i];
             rep[i].min_gain_q24 = minq[i];
@@ -235,7 +202,8 @@ extern "C" int flo_batch_normalize(flo_batch *src, const flo_normalize_opts *opt
     }
     if (reports && n) memcpy(reports, rep.data(), n * sizeof(flo_normalize_report));
     b->pcm_written = true;
-    return leave(FLO_OK);
+    *out = made.release();
+    return FLO_OK;
 }
 
 extern "C" int flo_normalize(flo_ctx *c, const float *pcm, size_t n_interleaved, uint32_t sample_rate, uint8_t channels,
@@ -244,27 +212,6 @@ extern "C" int flo_normalize(flo_ctx *c, const float *pcm, size_t n_interleaved,
     *out = nullptr;
     if (channels < 1 || channels > 8) return fail(c, FLO_ERR_ARG, "flo_normalize: 1 to 8 channels");
     if (!sample_rate) return fail(c, FLO_ERR_ARG, "flo_normalize: sample_rate must be non-zero");
-    const size_t whole = n_interleaved / channels * channels;
-    float *res = (float *)malloc(whole ? whole * sizeof(float) : 1);
-    if (!res) return fail(c, FLO_ERR_NOMEM, "out of memory");
-    flo_batch *a = nullptr, *b = nullptr;
-    auto leave = [&](int code) {
-        if (b) flo_batch_destroy(b);
-        if (a) flo_batch_destroy(a);
-        if (code != FLO_OK) free(res);
-        else *out = res;
-        return code;
-    };
-    int rc = flo_batch_create(c, FLO_MODE_LOSSLESS, 1, &whole, sample_rate, channels, 0, &a);
-    if (rc != FLO_OK) return leave(rc);
-    rc = flo_batch_upload(a, 0, pcm);
-    if (rc != FLO_OK) return leave(rc);
-    rc = flo_batch_normalize(a, opts, &b, report);
-    if (rc != FLO_OK) return leave(rc);
-    if (whole) {
-        hipError_t e = hipMemcpyAsync(res, b->d_pcm + b->clip_off[0], whole * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return leave(fail(c, FLO_ERR_DEVICE, std::string("flo_normalize: ") + hipGetErrorString(e)));
-    }
-    return leave(FLO_OK);
+    return batch_one_shot(c, "flo_normalize", pcm, n_interleaved / channels * channels, sample_rate, channels,
+                          [&](flo_batch *a, flo_batch **b) { return flo_batch_normalize(a, opts, b, report); }, out, nullptr);
 }

@@ -21,6 +21,7 @@
 #include <set>
 #include <utility>
 
+#include "clip_tiles.hpp"
 #include "normalize_kernels.hpp"
 
 namespace flo {
@@ -33,17 +34,6 @@ typedef unsigned int np_v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned np_abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
 __device__ __forceinline__ unsigned np_umax(unsigned a, unsigned b) { return a > b ? a : b; }
 __device__ __forceinline__ unsigned np_umin(unsigned a, unsigned b) { return a < b ? a : b; }
-
-// pre[lo] <= b < pre[lo + 1]: the last such lo, a clip that has tiles
-__device__ __forceinline__ unsigned np_find_clip(const unsigned *__restrict__ pre, unsigned n_clips, unsigned b) {
-    unsigned lo = 0, hi = n_clips;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (pre[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // bits[j] = the bits of max(|y|, max_q |e_q|) of the frame whose 64 taps start at plane[f[j]], for kNormGroup frames side
 // by side, eight taps of the four rows at a time: 32 coefficients are live in scalar registers, not 256 (which the compiler
@@ -124,7 +114,7 @@ __device__ __forceinline__ void np_store_tile(const float *__restrict__ src, flo
 __global__ __launch_bounds__(kNormThreads) void norm_peak_kernel(const NormArgs A) {
     __shared__ unsigned red[kNormThreads / 64];
     const unsigned tid = threadIdx.x;
-    const unsigned clip = np_find_clip(A.pre, A.n_clips, blockIdx.x);
+    const unsigned clip = tile_clip(A.pre, A.n_clips, blockIdx.x);
     const unsigned tile = blockIdx.x - A.pre[clip];
     const unsigned long long n = A.frames[clip];
     const float *__restrict__ src = A.src + A.src_off[clip];
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_peak_kernel(const NormArgs 
 }
 
 __global__ __launch_bounds__(kNormThreads) void norm_gain_kernel(const NormArgs A) {
-    const unsigned clip = np_find_clip(A.pre, A.n_clips, blockIdx.x);
+    const unsigned clip = tile_clip(A.pre, A.n_clips, blockIdx.x);
     const unsigned tile = blockIdx.x - A.pre[clip];
     const unsigned long long n = A.frames[clip];
     const unsigned ch = A.channels, F = norm_tile_frames(0);
@@ -164,7 +154,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_limit_kernel(const NormArgs
     __shared__ unsigned red[kNormThreads / 64];
     __shared__ unsigned long long wsum[kNormThreads / 64];
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const unsigned clip = np_find_clip(A.pre, A.n_clips, blockIdx.x);
+    const unsigned clip = tile_clip(A.pre, A.n_clips, blockIdx.x);
     const unsigned tile = blockIdx.x - A.pre[clip];
     const unsigned long long n = A.frames[clip];
     const float *__restrict__ src = A.src + A.src_off[clip];

@@ -11,7 +11,7 @@ struct NormArgs {
     float *dst = nullptr;         // clip i at dst + dst_off[i]; nothing else is written (unused by the peak launch)
     const float *table = nullptr; // h[4][64]
     const unsigned long long *src_off = nullptr, *dst_off = nullptr, *frames = nullptr;   // [n_clips]
-    const unsigned int *pre = nullptr;     // [n_clips + 1] tiles in front of every clip (normalize_tiles)
+    const unsigned int *pre = nullptr;     // [n_clips + 1] tiles in front of every clip (clip_tiles)
     const float *gain = nullptr;           // [n_clips]
     const unsigned int *copy = nullptr;    // [n_clips] non-zero: the clip is copied bit for bit
     unsigned long long *limited = nullptr; // [n_clips] frames with s < 2^24, from 0

@@ -105,17 +105,4 @@ float normalize_skip_bound(const std::vector<float> &h) {
     return f;
 }
 
-bool normalize_tiles(uint32_t A, const uint64_t *frames, size_t n_clips, std::vector<uint32_t> &pre) {
-    const uint64_t F = norm_tile_frames(A);
-    pre.assign(n_clips + 1, 0);
-    uint64_t t = 0;
-    for (size_t i = 0; i < n_clips; i++) {
-        pre[i] = (uint32_t)t;
-        t += (frames[i] + F - 1) / F;
-        if (t > 0x7FFFFFFFull) return false;
-    }
-    pre[n_clips] = (uint32_t)t;
-    return true;
-}
-
 }  // namespace flo

@@ -80,7 +80,6 @@ void normalize_gain(double integrated_lufs, double sample_peak_dbfs, float true_
 // to sum |h y|, the rounding of the product B * max |y| below 2^-23)
 std::vector<float> normalize_table();
 float normalize_skip_bound(const std::vector<float> &h);
-// The flat work list: pre[i] = tiles of clips 0 .. i - 1 (n + 1 entries); false when a launch cannot hold them.
-bool normalize_tiles(uint32_t A, const uint64_t *frames, size_t n_clips, std::vector<uint32_t> &pre);
+// (the flat work list of a launch: clip_tiles of every clip's frames in tiles of norm_tile_frames(A), clip_tiles.hpp)
 
 }  // namespace flo

@@ -49,7 +49,9 @@ __global__ __launch_bounds__(kResampleThreads) void resample_kernel(const float 
     typedef typename std::conditional<STEREO, rs_v2f, float>::type V;   // one staged frame of a plane
     const unsigned tid = threadIdx.x, lane = tid & 63u;
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), n_waves = blockDim.x >> 6;
-    // pre[lo] <= blockIdx.x < pre[lo + 1]: the last such lo, a clip that has tiles
+    // pre[lo] <= blockIdx.x < pre[lo + 1]: the last such lo, a clip that has tiles. This is tile_clip (clip_tiles.hpp) written
+    // out: called as a function, its loop reaches this kernel already rotated and the compiler emits hi + lo for lo + hi;
+    // written out, the code object is the one this kernel has always had
     const unsigned b = blockIdx.x;
     unsigned lo = 0, hi = A.n_clips;
     while (hi - lo > 1) {

@@ -127,16 +127,4 @@ uint32_t resample_lds_bytes(const ResamplePlan &p, uint32_t channels) {
     return p.lds_elems * 4 * resample_pass_channels(channels);
 }
 
-bool resample_tiles(const ResamplePlan &p, const uint64_t *n_out, size_t n_clips, std::vector<uint32_t> &pre) {
-    pre.assign(n_clips + 1, 0);
-    uint64_t t = 0;
-    for (size_t i = 0; i < n_clips; i++) {
-        pre[i] = (uint32_t)t;
-        t += (n_out[i] + p.tile_outputs - 1) / p.tile_outputs;
-        if (t > 0x7FFFFFFFull) return false;
-    }
-    pre[n_clips] = (uint32_t)t;
-    return true;
-}
-
 }  // namespace flo

@@ -107,7 +107,6 @@ bool resample_out_frames(const ResamplePlan &p, uint64_t n_in, uint64_t &n_out);
 // channels a tile stages at a time (1, or 2) and the dynamic LDS that takes
 uint32_t resample_pass_channels(uint32_t channels);
 uint32_t resample_lds_bytes(const ResamplePlan &p, uint32_t channels);
-// The flat work list: pre[i] = tiles of clips 0 .. i - 1 (pre has n + 1 entries); false when a launch cannot hold them.
-bool resample_tiles(const ResamplePlan &p, const uint64_t *n_out, size_t n_clips, std::vector<uint32_t> &pre);
+// (the flat work list of a launch: clip_tiles of every clip's n_out in tiles of tile_outputs, clip_tiles.hpp)
 
 }  // namespace flo

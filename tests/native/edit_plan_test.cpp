@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "../../flo_amd/csrc/clip_tiles.hpp"
 #include "../../flo_amd/csrc/edit_plan.hpp"
 
 using namespace flo;
@@ -136,7 +137,7 @@ static bool check_geometry() {
         const uint64_t lens[] = {0, 1, F - 1, F, F + 1, 2 * (uint64_t)F + 5};
         const uint32_t want[] = {0, 1, 1, 1, 2, 3};
         std::vector<uint32_t> pre;
-        CHECK(edit_tiles(lens, 6, F, pre) && pre.size() == 7, "the prefix of six clips");
+        CHECK(clip_tiles(lens, 6, F, pre) && pre.size() == 7, "the prefix of six clips");
         uint32_t t = 0;
         for (int i = 0; i < 6; i++) {
             CHECK(pre[i] == t, "pre[%d] of %u channels is %u, not %u", i, c, pre[i], t);
@@ -152,8 +153,8 @@ static bool check_geometry() {
     }
     const uint64_t huge[2] = {0x7FFFFFFFull * 16, 17};
     std::vector<uint32_t> pre;
-    CHECK(!edit_tiles(huge, 2, 16, pre), "more than 2^31 - 1 tiles are refused");
-    CHECK(edit_tiles(huge, 1, 16, pre) && pre[1] == 0x7FFFFFFFu, "2^31 - 1 tiles are accepted");
+    CHECK(!clip_tiles(huge, 2, 16, pre), "more than 2^31 - 1 tiles are refused");
+    CHECK(clip_tiles(huge, 1, 16, pre) && pre[1] == 0x7FFFFFFFu, "2^31 - 1 tiles are accepted");
     return true;
 }
 
@@ -202,7 +203,7 @@ static int dump() {
         const uint32_t F = edit_tile_frames(cout);
         const uint64_t T = edit_out_frames(s);
         std::vector<uint32_t> pre;
-        if (!edit_tiles(&T, 1, F, pre)) return 1;
+        if (!clip_tiles(&T, 1, F, pre)) return 1;
         printf("%u %u", F, pre[1]);
         for (uint32_t k = 0; k < pre[1]; k++) printf(" %u", edit_tile_class(s, k, F));
         printf("\n");

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../../flo_amd/csrc/clip_tiles.hpp"
 #include "../../flo_amd/csrc/normalize_plan.hpp"
 
 using namespace flo;
@@ -166,7 +167,7 @@ static bool check_cover() {
         const uint64_t F = norm_tile_frames(A);
         std::vector<uint64_t> frames = {0, 1, F - 1, F, F + 1, 0, 0, 2 * F + 1, 3 * F + 5, 4 * A + 63, 0};
         std::vector<uint32_t> pre;
-        CHECK(normalize_tiles(A, frames.data(), frames.size(), pre) && pre.size() == frames.size() + 1 && pre[0] == 0, "A = %u: tiles", A);
+        CHECK(clip_tiles(frames.data(), frames.size(), norm_tile_frames(A), pre) && pre.size() == frames.size() + 1 && pre[0] == 0, "A = %u: tiles", A);
         std::vector<std::vector<uint8_t>> hits(frames.size());
         for (size_t i = 0; i < frames.size(); i++) hits[i].assign(frames[i], 0);
         for (uint32_t b = 0; b < pre.back(); b++) {
@@ -189,7 +190,7 @@ static bool check_cover() {
     }
     std::vector<uint64_t> huge = {1ull << 62, 1ull << 62};
     std::vector<uint32_t> pre;
-    CHECK(!normalize_tiles(72, huge.data(), huge.size(), pre), "more tiles than a launch holds are refused");
+    CHECK(!clip_tiles(huge.data(), huge.size(), norm_tile_frames(72), pre), "more tiles than a launch holds are refused");
     return true;
 }
 

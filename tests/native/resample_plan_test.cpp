@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../../flo_amd/csrc/clip_tiles.hpp"
 #include "../../flo_amd/csrc/resample_plan.hpp"
 
 using namespace flo;
@@ -85,7 +86,7 @@ static bool check_geometry(const ResamplePlan &P) {
     const uint64_t tile = P.tile_outputs;
     const std::vector<uint64_t> n_out = {0, 1, 0, 2, T / 2, tile - 1, tile, tile + 1, 2 * tile + 17, 0};
     std::vector<uint32_t> pre;
-    CHECK(resample_tiles(P, n_out.data(), n_out.size(), pre) && pre.size() == n_out.size() + 1 && pre[0] == 0, "tiles");
+    CHECK(clip_tiles(n_out.data(), n_out.size(), P.tile_outputs, pre) && pre.size() == n_out.size() + 1 && pre[0] == 0, "tiles");
     for (size_t c = 0; c < n_out.size(); c++) CHECK(pre[c + 1] - pre[c] == (n_out[c] + tile - 1) / tile, "clip %zu: tiles", c);
     std::vector<std::vector<uint8_t>> made(n_out.size());
     for (size_t c = 0; c < n_out.size(); c++) made[c].assign(n_out[c], 0);
@@ -193,7 +194,7 @@ static int dump() {
             n_out.push_back(n);
         }
         std::vector<uint32_t> pre;
-        if (!resample_tiles(P, n_out.data(), n_out.size(), pre)) return fprintf(stderr, "tiles\n"), 1;
+        if (!clip_tiles(n_out.data(), n_out.size(), P.tile_outputs, pre)) return fprintf(stderr, "tiles\n"), 1;
         for (size_t i = 0; i < n_out.size(); i++) printf(" %llu:%u", (unsigned long long)n_out[i], pre[i + 1] - pre[i]);
         printf("\n");
     }

@@ -316,6 +316,37 @@ def test_the_result_is_a_first_class_batch(ctx, kind):
 
 
 @gpu
+def test_a_chain_of_derived_batches_keeps_its_work_and_its_bit_depth(ctx):
+    """resample -> normalise -> to_mono, each source closed as soon as its successor exists and the test itself waiting for
+    nothing before the encode: each batch lives on the work block its own launch was queued with, the bit depth of 24 passes
+    through all three, and the empty and the one-frame clip stand in every prefix. Every file equals the file of the same
+    clip taken alone through the one-clip calls"""
+    rng = np.random.default_rng(41)
+    lens = (0, 1, 4097)
+    clips = [(rng.uniform(-0.4, 0.4, n * 2) * np.repeat(np.sin(np.arange(n) / 200.0) ** 2 + 0.05, 2)).astype(F32) for n in lens]
+    mono = np.array([[1.0 / 2] * 2], F32)
+    want = []
+    for x in clips:
+        y = flo_amd.resample(x, 48000, 44100, 2)
+        z = flo_amd.remix(flo_amd.normalize(y, 44100, 2)[0], 44100, 2, mono)
+        want.append(flo_amd.default_context().encode_lossless(z, 44100, 1, bit_depth=24))
+    b = _batch_of(ctx, clips, 48000, 2, flo_amd.MODE_LOSSLESS, 5)
+    try:
+        b.set_bit_depth(24)
+        for step in (lambda s: s.resample(44100), lambda s: s.normalize()[0], lambda s: s.to_mono()):
+            nxt = step(b)
+            b.close()
+            b = nxt
+        b.encode()
+        b.sync()
+        assert b.channels == 1 and b.sample_rate == 44100
+        for i in range(len(lens)):
+            assert b.fetch(i) == want[i], i
+    finally:
+        b.close()
+
+
+@gpu
 def test_errors_leave_no_batch_and_a_usable_context(ctx):
     clips = [np.arange(20, dtype=F32), np.arange(8, dtype=F32)]
     nan_m, big = np.array([[0.5, np.nan]], F32), np.full((9, 9), 0.1, F32)
