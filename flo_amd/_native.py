@@ -48,6 +48,7 @@ EXPORTS = [
     "flo_resample_filter", "flo_resample_out_frames", "flo_batch_resample", "flo_resample",
     "flo_batch_true_peak", "flo_normalize_gain", "flo_normalize_lookahead", "flo_batch_normalize", "flo_normalize",
     "flo_batch_edit", "flo_batch_active_range", "flo_edit", "flo_edit_tile_frames",
+    "flo_batch_mix", "flo_mix",
 ]
 
 
@@ -122,6 +123,11 @@ class NormalizeReport(C.Structure):   # flo_normalize_report
 class EditSegment(C.Structure):   # flo_edit_segment
     _fields_ = [("start", C.c_uint64), ("frames", C.c_uint64), ("clip", C.c_uint32), ("pad_head", C.c_uint32), ("pad_tail", C.c_uint32),
                 ("fade_in", C.c_uint32), ("fade_out", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MixPart(C.Structure):   # flo_mix_part
+    _fields_ = [("start", C.c_uint64), ("frames", C.c_uint64), ("at", C.c_uint64), ("out", C.c_uint32), ("batch", C.c_uint32), ("clip", C.c_uint32),
+                ("fade_in", C.c_uint32), ("fade_out", C.c_uint32), ("gain", C.c_float)]
 
 
 class FloError(RuntimeError):
@@ -301,5 +307,7 @@ def lib():
     L.flo_batch_active_range.argtypes = [vp, C.c_float, vp, vp]
     L.flo_edit.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint8, C.POINTER(EditSegment), C.c_uint8, vp, C.POINTER(vp), C.POINTER(sz)]
     L.flo_edit_tile_frames.argtypes = [C.c_uint8, C.c_uint8, C.POINTER(C.c_uint32)]
+    L.flo_batch_mix.argtypes = [C.POINTER(vp), sz, sz, C.POINTER(C.c_uint64), sz, C.POINTER(MixPart), C.POINTER(vp)]
+    L.flo_mix.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.c_uint32, C.c_uint8, sz, C.POINTER(MixPart), C.c_uint64, C.POINTER(vp), C.POINTER(sz)]
     _LIB = L
     return L

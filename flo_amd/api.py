@@ -195,6 +195,21 @@ class Context:
         self._L.flo_free(out)
         return res
 
+    def mix(self, clips, sample_rate, channels, parts, out_frames=None):
+        """flo_mix: one output clip summed from parts of the interleaved f32 clips (one upload, the batch kernel, one fetch).
+        parts: dicts as Batch.mix takes (batch and out are 0); out_frames None: the end of the furthest part"""
+        ps = [_f32(x) for x in clips]
+        arr = _mix_parts(parts, [[p.size // channels for p in ps]])
+        if out_frames is None:
+            out_frames = max([int(g.at) + int(g.frames) for g in arr], default=0)
+        ptrs = (C.c_void_p * max(len(ps), 1))(*[p.ctypes.data for p in ps])
+        lens = (C.c_size_t * max(len(ps), 1))(*[p.size for p in ps])
+        out, n = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.flo_mix(self._h, len(ps), ptrs, lens, sample_rate, channels, len(arr), arr, int(out_frames), C.byref(out), C.byref(n)))
+        res = np.frombuffer(C.string_at(out.value, n.value * 4), np.float32).copy() if n.value else np.zeros(0, np.float32)
+        self._L.flo_free(out)
+        return res
+
     def upload_path(self):
         """(path large host uploads take on this host, GB/s the probe measured for pageable-direct, for the pinned ring)"""
         name, a, b = C.create_string_buffer(64), C.c_double(), C.c_double()
@@ -503,6 +518,38 @@ class Batch:
         frames = [n // self.channels for n in self.n_interleaved]
         segs = trim_segments(ranges, frames, self.sample_rate, pre_ms, post_ms, fade_ms)
         return self.edit(segs), ranges
+
+    def mix(self, parts, out_frames=None, others=()) -> "Batch":
+        """flo_batch_mix: a new batch of this batch's mode, rate, channels, quality / level and bit depth whose clip k is the
+        sum of the parts with out == k, in list order, every clip in one launch (enqueued; sync() of any of the batches
+        orders it). The sources are (self, *others): batches of this context, rate and channel count. A part is a dict with
+        out and clip and optionally batch (0: this batch), start (0), frames (to the clip's end), at (0), gain (1.0),
+        fade_in, fade_out (0), all in frames, or a _native.MixPart; parts are listed with `out` non-decreasing. Source
+        frames [start, start + frames) land on output frames [at, at + frames), times gain and the linear fades of
+        Batch.edit; a part is cut at its source's end and at the output's end. A frame no part covers is +0.0.
+        out_frames: the frames of every output clip; None: every output ends with its furthest part, and there are
+        1 + max(out) of them. The sources stay valid and unchanged"""
+        srcs = (self,) + tuple(others)
+        arr = _mix_parts(parts, [[n // b.channels for n in b.n_interleaved] for b in srcs])
+        if out_frames is None:
+            out_frames = _mix_out_frames(arr)
+        frames = [int(t) for t in out_frames]
+        T = (C.c_uint64 * max(len(frames), 1))(*frames)
+        hs = (C.c_void_p * len(srcs))(*[b._h.value for b in srcs])
+        h = C.c_void_p()
+        self.ctx._chk(self._L.flo_batch_mix(hs, len(srcs), len(frames), T, len(arr), arr, C.byref(h)))
+        return Batch(self.ctx, self._made[0], [t * self.channels for t in frames], self.sample_rate, self.channels, self._made[1], _handle=h)
+
+    def concat(self, groups, crossfade_ms=0.0) -> "Batch":
+        """a new batch whose clip k plays the clips groups[k] (a list of clip indices of this batch) end to end, neighbours
+        overlapping by crossfade_ms (concat_parts has the rule and what a linear crossfade sums to). Batch.mix"""
+        frames = [n // self.channels for n in self.n_interleaved]
+        parts, T = [], []
+        for k, g in enumerate(groups):
+            p, t = concat_parts(frames, self.sample_rate, crossfade_ms, out=k, clips=list(g))
+            parts += p
+            T.append(t)
+        return self.mix(parts, T)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1484,6 +1531,70 @@ def _edit_segments(segments, clip_frames):
         out[k] = _native.EditSegment(start, int(frames), clip, int(g.get("pad_head", 0)), int(g.get("pad_tail", 0)),
                                      int(g.get("fade_in", 0)), int(g.get("fade_out", 0)), int(g.get("reserved", 0)))
     return (_native.EditSegment * len(segments)).from_buffer(out) if segments else (_native.EditSegment * 0)()
+
+
+def _mix_parts(parts, clip_frames):
+    """the flo_mix_part array of a list of dicts / MixPart; clip_frames[b][i]: the frames of clip i of source b. `frames`
+    missing or None: to the clip's end"""
+    parts = list(parts)
+    out = (_native.MixPart * max(len(parts), 1))()
+    for k, g in enumerate(parts):
+        if isinstance(g, _native.MixPart):
+            out[k] = g
+            continue
+        unknown = set(g) - {"out", "batch", "clip", "start", "frames", "at", "gain", "fade_in", "fade_out"}
+        if unknown:
+            raise FloError(f"part {k}: unknown keys {sorted(unknown)}")
+        if "out" not in g or "clip" not in g:
+            raise FloError(f"part {k}: out and clip are required")
+        batch, clip, start = int(g.get("batch", 0)), int(g["clip"]), int(g.get("start", 0))
+        frames = g.get("frames")
+        if frames is None:
+            known = 0 <= batch < len(clip_frames) and 0 <= clip < len(clip_frames[batch])
+            frames = max(int(clip_frames[batch][clip]) - start, 0) if known else 0
+        out[k] = _native.MixPart(start, int(frames), int(g.get("at", 0)), int(g["out"]), batch, clip, int(g.get("fade_in", 0)),
+                                 int(g.get("fade_out", 0)), float(g.get("gain", 1.0)))
+    return (_native.MixPart * len(parts)).from_buffer(out) if parts else (_native.MixPart * 0)()
+
+
+def _mix_out_frames(parts) -> list:
+    """out_frames=None of Batch.mix: 1 + max(out) outputs, each ending with its furthest part (at + frames)"""
+    T = [0] * (1 + max([int(g.out) for g in parts], default=-1))
+    for g in parts:
+        T[g.out] = max(T[g.out], int(g.at) + int(g.frames))
+    return T
+
+
+def concat_parts(frames, sample_rate, crossfade_ms=0.0, out=0, clips=None, batch=0):
+    """(parts, T) of one output that plays clips (indices into `frames`, the frames of every clip of source `batch`; None:
+    all of them in order) end to end: Batch.mix's parts of output `out` and its length. Neighbours j, j + 1 overlap by
+    xf_j = min(round(crossfade_ms * sample_rate / 1000), N_j, N_j+1) frames (at most 2^24 - 1, the longest fade):
+    at_j = at_j-1 + N_j-1 - xf_j-1, fade_in = xf_j-1 (0 for the first), fade_out = xf_j (0 for the last). Pure Python, no device.
+    The fades are Batch.edit's linear ones, kept as they are: over a crossfade of xf frames the weights of the clip that
+    leaves and of the clip that enters are (xf - 1 - u) / xf and u / xf, which sum to (xf - 1) / xf, not 1. Other curves are
+    out of scope."""
+    idx = list(range(len(frames))) if clips is None else [int(i) for i in clips]
+    want = _ms_frames(crossfade_ms, sample_rate)
+    n = [int(frames[i]) for i in idx]
+    xf = [min(want, n[j], n[j + 1], (1 << 24) - 1) for j in range(len(n) - 1)]
+    parts, at = [], 0
+    for j, i in enumerate(idx):
+        if j:
+            at += n[j - 1] - xf[j - 1]
+        parts.append(dict(out=int(out), batch=int(batch), clip=i, start=0, frames=n[j], at=at, gain=1.0,
+                          fade_in=xf[j - 1] if j else 0, fade_out=xf[j] if j < len(xf) else 0))
+    return parts, (at + n[-1] if n else 0)
+
+
+def mix(clips, sample_rate, channels, parts, out_frames=None) -> np.ndarray:
+    """one clip summed from parts of the interleaved f32 clips, on the device (Context.mix on the default context)"""
+    return default_context().mix(clips, sample_rate, channels, parts, out_frames)
+
+
+def concat(clips, sample_rate, channels, crossfade_ms=0.0) -> np.ndarray:
+    """the interleaved f32 clips end to end, neighbours crossfaded over crossfade_ms (concat_parts), on the device"""
+    parts, T = concat_parts([_f32(x).size // channels for x in clips], sample_rate, crossfade_ms)
+    return mix(clips, sample_rate, channels, parts, T)
 
 
 def _edit_matrix(in_channels, out_channels, matrix):

@@ -8,6 +8,8 @@ printed fields for the parts that sit on this repository's path -
     edit    <in.wav> <out.wav> [--mono | --channels N --matrix a,b,...] [--start S] [--duration S]
                                [--trim-silence DB] [--pre-ms MS] [--post-ms MS] [--fade-in MS] [--fade-out MS]
                                [--pad-head S] [--pad-tail S]
+    mix     <in1.wav> <in2.wav> ... --out <out.wav> [--gains g,g,...] [--at-ms a,a,...]
+    concat  <in1.wav> <in2.wav> ... --out <out.wav> [--crossfade-ms MS]
     resample <in.wav> <out.wav> --rate HZ
     normalize <in.wav> <out.wav> --lufs N [--ceiling D] [--limit]
     curve   <in.wav> [--json]
@@ -47,10 +49,15 @@ clip's active range (samples above DB dBFS), widened by --pre-ms / --post-ms; th
 milliseconds and padded with --pad-head / --pad-tail seconds of silence; --mono averages the channels, --channels N with
 --matrix (N rows of the source's channel count, row-major) mixes them. In `encode` the edits come first, before --rate and
 --lufs, in that order.
+`mix` and `concat` (not in reflo) sum or join several WAV files of one sample rate and channel count on the device
+(flo_mix): `mix` lays file i at --at-ms a_i milliseconds (default 0) times --gains g_i (default 1), the output ending with
+the file that ends last; `concat` plays the files end to end, neighbours overlapping in a linear crossfade of
+--crossfade-ms milliseconds (default 0: gapless). Files of another rate or channel count go through `resample` or `edit` first.
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
 """
 import argparse
+import math
 import sys
 
 import json
@@ -149,6 +156,52 @@ def _read_at_rate(audio_bytes: bytes, rate, ctx=None, level=None, edit=None):
     if level is not None:
         samples, _ = (ctx or api.default_context()).normalize(samples, sr, ch, **level)
     return samples, sr, ch
+
+
+def mix_options(n_inputs, gains=None, at_ms=None):
+    """(gains, at_ms) of the `mix` command for n_inputs files: comma-separated lists or sequences, one entry per file;
+    None: every gain 1, every file at 0 ms"""
+    def numbers(v, default, what):
+        if v is None:
+            return [default] * n_inputs
+        vals = [float(x) for x in v.split(",")] if isinstance(v, str) else [float(x) for x in v]
+        if len(vals) != n_inputs:
+            raise ValueError(f"{what} has {len(vals)} entries for {n_inputs} input files")
+        return vals
+    g, at = numbers(gains, 1.0, "--gains"), numbers(at_ms, 0.0, "--at-ms")
+    if any(a < 0 for a in at):
+        raise ValueError("--at-ms must not be negative")
+    return g, at
+
+
+def _same_format(wavs):
+    """([samples], sample_rate, channels) of WAV files that share both"""
+    if not wavs:
+        raise ValueError("no input files")
+    clips = [read_wav_bytes(w) for w in wavs]
+    sr, ch = clips[0][1], clips[0][2]
+    for i, (_, r, c) in enumerate(clips):
+        if (r, c) != (sr, ch):
+            raise ValueError(f"input {i + 1} is {r} Hz with {c} channels, input 1 is {sr} Hz with {ch}: "
+                             "bring them to one format with `resample` and `edit --channels` first")
+    return [c[0] for c in clips], sr, ch
+
+
+def mix_wavs(wavs, gains=None, at_ms=None, ctx=None) -> bytes:
+    """the sum of the WAV files (bytes each), file i at at_ms[i] milliseconds times gains[i] (mix_options), as the 32-bit
+    float WAV `decode` writes: one upload, one device pass, one fetch (Context.mix)"""
+    clips, sr, ch = _same_format(wavs)
+    g, at = mix_options(len(clips), gains, at_ms)
+    parts = [dict(out=0, clip=i, at=int(math.floor(at[i] * sr / 1000.0 + 0.5)), gain=g[i]) for i in range(len(clips))]
+    return write_wav_bytes((ctx or api.default_context()).mix(clips, sr, ch, parts), sr, ch)
+
+
+def concat_wavs(wavs, crossfade_ms=0.0, ctx=None) -> bytes:
+    """the WAV files (bytes each) end to end, neighbours crossfaded over crossfade_ms (api.concat_parts), as the 32-bit float
+    WAV `decode` writes"""
+    clips, sr, ch = _same_format(wavs)
+    parts, T = api.concat_parts([c.size // ch for c in clips], sr, crossfade_ms)
+    return write_wav_bytes((ctx or api.default_context()).mix(clips, sr, ch, parts, T), sr, ch)
 
 
 def level_options(lufs, ceiling=-1.0, limit=False):
@@ -389,6 +442,15 @@ def main(argv=None) -> int:
         p_.add_argument("--lufs", type=float, default=None, required=need, help="Target integrated loudness in LUFS")
         p_.add_argument("--ceiling", type=float, default=-1.0, help="True-peak ceiling in dBTP (default -1)")
         p_.add_argument("--limit", action="store_true", help="Apply the full gain and hold the ceiling with a look-ahead limiter")
+    mx = sub.add_parser("mix", help="Sum several WAV files at chosen gains and offsets on the device")
+    mx.add_argument("inputs", nargs="+")
+    mx.add_argument("--out", required=True, help="Output WAV file")
+    mx.add_argument("--gains", default=None, help="Comma-separated linear gains, one per input (default 1)")
+    mx.add_argument("--at-ms", default=None, help="Comma-separated start offsets in milliseconds, one per input (default 0)")
+    cc = sub.add_parser("concat", help="Join several WAV files end to end on the device")
+    cc.add_argument("inputs", nargs="+")
+    cc.add_argument("--out", required=True, help="Output WAV file")
+    cc.add_argument("--crossfade-ms", type=float, default=0.0, help="Linear crossfade between neighbours in milliseconds (default 0)")
     rs = sub.add_parser("resample", help="Convert a WAV file to another sample rate on the device")
     rs.add_argument("input")
     rs.add_argument("output")
@@ -497,6 +559,22 @@ def main(argv=None) -> int:
             print(f"  Cut: frames {g['start']} .. {g['start'] + g['frames']}, fades {g['fade_in']} / {g['fade_out']}, pads {g['pad_head']} / {g['pad_tail']}")
             print("Done!")
             print(f"  Output: {a.output}")
+        elif a.command in ("mix", "concat"):
+            print(f"Reading {len(a.inputs)} files...")
+            wavs = [open(p, "rb").read() for p in a.inputs]
+            if a.command == "mix":
+                print("Mixing on the device...")
+                wav = mix_wavs(wavs, a.gains, a.at_ms)
+            else:
+                print(f"Joining on the device (crossfade {a.crossfade_ms:g} ms)...")
+                wav = concat_wavs(wavs, a.crossfade_ms)
+            open(a.out, "wb").write(wav)
+            samples, sr, ch = read_wav_bytes(wav)
+            print(f"  Sample rate: {sr} Hz")
+            print(f"  Channels: {ch}")
+            print(f"  Duration: {samples.size / ch / sr:.2f}s")
+            print("Done!")
+            print(f"  Output: {a.out}")
         elif a.command == "resample":
             print(f"Reading {a.input}...")
             audio = open(a.input, "rb").read()

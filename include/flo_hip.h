@@ -567,6 +567,48 @@ int flo_edit(flo_ctx *ctx, const float *pcm, size_t n_interleaved, uint32_t samp
              const flo_edit_segment *seg, uint8_t out_channels, const float *matrix, float **out, size_t *n_out);
 int flo_edit_tile_frames(uint8_t in_channels, uint8_t out_channels, uint32_t *frames);
 
+/* ---- mixing and concatenation: several resident batches become one resident batch of sums of their clips, on the device ----
+ * (no counterpart in the reference; DESIGN 4.17 has the definition in full.)
+ * Sources: n_srcs >= 1 resident batches of one context, one sample rate and one channel count C. Clip i of a source has N_i
+ * whole sample-frames; a trailing partial sample-frame is not part of it. The output batch has n_out clips, clip k of
+ * out_frames[k] = T_k frames of C channels. A list of n_parts parts says what is laid where: source frames
+ * [start, start + frames) of clip `clip` of srcs[batch] land on output frames [at, at + frames) of output clip `out`, times
+ * `gain`, faded linearly over fade_in frames at the part's start and fade_out frames at its end.
+ * The list: `out` is non-decreasing along it; inside one output clip the list order is the order of summation, which need
+ * not be the order in time; any number of parts may name the same source clip, and they may overlap; an output clip may
+ * have no part at all.
+ * Part p is live on output frame t of clip k = p.out when at <= t < at + frames, t < T_k and start + (t - at) < N: parts
+ * that reach past the source's end or past the output's end are cut there, not refused. For a live frame, u = t - at and
+ * v = frames - 1 - u; the fade weight is flo_batch_edit's: w_in = fl32((float)u / (float)fade_in) if u < fade_in,
+ * w_out = fl32((float)v / (float)fade_out) if v < fade_out, both IEEE divisions, w = fl32(w_in * w_out) where both apply.
+ * The part's coefficient is k_p = gain where no fade applies, else k_p = fl32(gain * w).
+ * Output sample (t, c): a = +0.0f; for every part of clip k that is live on t, in list order,
+ * a = fmaf(k_p, x_p[start + u, c], a); the result is a. So a frame that no part covers is +0.0; one part at gain 1
+ * reproduces the source bit for bit except that -0.0 becomes +0.0 (fmaf(1, -0, +0) = +0); one part at gain 1 with fades
+ * gives fl32(w * x), flo_batch_edit's value up to the same sign of zero.
+ * FLO_ERR_ARG with a message that names the quantity: n_srcs == 0 or a NULL source; sources of different context, rate or
+ *   channel count; out >= n_out; out decreasing along the list; batch >= n_srcs; clip >= n_clips of that batch; fade_in or
+ *   fade_out longer than frames or >= 2^24; a non-finite gain; at + frames or start + frames wrapping 64 bits;
+ *   n_parts >= 2^32; T_k * C beyond what flo_batch_create accepts; too many tiles for one launch. FLO_ERR_STATE when a
+ *   source that some part names holds no PCM yet.
+ * flo_batch_mix: a new batch of the mode, quality / level and bit depth of srcs[0], at the common rate and C channels, made
+ *   by one launch (enqueued on the ctx stream; flo_batch_sync on any of the batches orders it). The work list lives in
+ *   pinned and device memory that the new batch owns until it is destroyed. The sources stay valid and unchanged. The new
+ *   batch behaves like an uploaded one: it encodes, analyses, resamples, normalises and edits like any other. One workgroup
+ *   makes flo_edit_tile_frames(C, C) output frames of one clip; it scans all parts of its clip.
+ * flo_mix: n_clips clips from host memory as one source (every part has batch == 0 and out == 0) and the one output clip
+ *   of out_frames frames back: *out (*n_out interleaved samples) malloc'ed, flo_free. */
+typedef struct flo_mix_part {
+    uint64_t start, frames, at;   /* source frames [start, start + frames) land on output frames [at, at + frames) */
+    uint32_t out, batch, clip;    /* output clip; index into srcs; clip of that batch */
+    uint32_t fade_in, fade_out;   /* linear, in frames of the part; 0 = none */
+    float gain;
+} flo_mix_part;                   /* 48 bytes */
+int flo_batch_mix(flo_batch *const *srcs, size_t n_srcs, size_t n_out, const uint64_t *out_frames, size_t n_parts,
+                  const flo_mix_part *parts, flo_batch **out);
+int flo_mix(flo_ctx *ctx, size_t n_clips, const float *const *pcm, const size_t *n_interleaved, uint32_t sample_rate,
+            uint8_t channels, size_t n_parts, const flo_mix_part *parts, uint64_t out_frames, float **out, size_t *n_out);
+
 /* ---- spectral similarity: spectral_similarity (core/analysis.rs:395-437, exported as spectral_similarity_score,
  * lib.rs:1357) over fingerprint sets ----------------------------------------------------------------------------------
  * flo_fingerprint is SpectralFingerprint (analysis.rs:10-26): what flo_analyze / flo_batch_analyze_all return in those
