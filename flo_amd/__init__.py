@@ -17,6 +17,7 @@ from .api import normalize, normalize_gain, normalize_lookahead, normalize_many,
 from .api import (active_range, active_range_many, edit, edit_many, edit_tile_frames, remix, remix_many, trim_silence,  # noqa: F401
                   trim_silence_many)
 from .api import concat, concat_parts, mix  # noqa: F401
+from .api import conv_geometry, conv_mode, convolve, fir_design, fir_filter  # noqa: F401
 from .api import (FINGERPRINT_DTYPE, FingerprintIndex, extract_dominant_frequencies, fingerprint_array,  # noqa: F401
                   fingerprints_from_files, spectral_similarity)
 from .api import FIDELITY_BLOCK_DTYPE, FIDELITY_DTYPE, compare, fidelity_dict  # noqa: F401

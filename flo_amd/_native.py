@@ -49,6 +49,7 @@ EXPORTS = [
     "flo_batch_true_peak", "flo_normalize_gain", "flo_normalize_lookahead", "flo_batch_normalize", "flo_normalize",
     "flo_batch_edit", "flo_batch_active_range", "flo_edit", "flo_edit_tile_frames",
     "flo_batch_mix", "flo_mix",
+    "flo_batch_convolve", "flo_convolve", "flo_conv_geometry", "flo_fir_design",
 ]
 
 
@@ -128,6 +129,19 @@ class EditSegment(C.Structure):   # flo_edit_segment
 class MixPart(C.Structure):   # flo_mix_part
     _fields_ = [("start", C.c_uint64), ("frames", C.c_uint64), ("at", C.c_uint64), ("out", C.c_uint32), ("batch", C.c_uint32), ("clip", C.c_uint32),
                 ("fade_in", C.c_uint32), ("fade_out", C.c_uint32), ("gain", C.c_float)]
+
+
+class ConvJob(C.Structure):   # flo_conv_job
+    _fields_ = [("frames", C.c_uint64), ("skip", C.c_uint64), ("ir_start", C.c_uint64), ("clip", C.c_uint32), ("ir", C.c_uint32),
+                ("taps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ConvInfo(C.Structure):   # flo_conv_info
+    _fields_ = [("tile_frames", C.c_uint32), ("tap_chunk", C.c_uint32), ("lane_outputs", C.c_uint32)]
+
+
+CONV_MAX_TAPS = 65536
+FIR_LOWPASS, FIR_HIGHPASS, FIR_BANDPASS, FIR_BANDSTOP = 0, 1, 2, 3
 
 
 class FloError(RuntimeError):
@@ -309,5 +323,9 @@ def lib():
     L.flo_edit_tile_frames.argtypes = [C.c_uint8, C.c_uint8, C.POINTER(C.c_uint32)]
     L.flo_batch_mix.argtypes = [C.POINTER(vp), sz, sz, C.POINTER(C.c_uint64), sz, C.POINTER(MixPart), C.POINTER(vp)]
     L.flo_mix.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.c_uint32, C.c_uint8, sz, C.POINTER(MixPart), C.c_uint64, C.POINTER(vp), C.POINTER(sz)]
+    L.flo_batch_convolve.argtypes = [vp, vp, sz, C.POINTER(ConvJob), C.POINTER(vp)]
+    L.flo_convolve.argtypes = [vp, vp, sz, vp, sz, C.c_uint32, C.c_uint8, C.c_uint8, C.POINTER(ConvJob), C.POINTER(vp), C.POINTER(sz)]
+    L.flo_conv_geometry.argtypes = [C.c_uint8, C.c_uint8, C.POINTER(ConvInfo)]
+    L.flo_fir_design.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.c_double, C.POINTER(vp), C.c_char_p, sz]
     _LIB = L
     return L

@@ -210,6 +210,20 @@ class Context:
         self._L.flo_free(out)
         return res
 
+    def convolve(self, samples, ir, sample_rate, channels, ir_channels=1, job=None, *, mode="head", taps=None):
+        """flo_convolve: the interleaved f32 clip filtered by the interleaved f32 response `ir` of ir_channels (1 or channels)
+        channels (one upload each, the batch kernel, one fetch). job: a dict as Batch.convolve takes (clip and ir are 0) or a
+        _native.ConvJob; None: the whole response in `mode` (Batch.convolve), at most `taps` taps"""
+        p, h = _f32(samples), _f32(ir)
+        jobs = _conv_jobs(None if job is None else [job if isinstance(job, _native.ConvJob) else dict(job, clip=0, ir=0)],
+                          [p.size // channels], [h.size // ir_channels], 0, mode, taps)
+        out, n = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.flo_convolve(self._h, p.ctypes.data, p.size, h.ctypes.data, h.size, sample_rate, channels, ir_channels, jobs,
+                                       C.byref(out), C.byref(n)))
+        res = np.frombuffer(C.string_at(out.value, n.value * 4), np.float32).copy() if n.value else np.zeros(0, np.float32)
+        self._L.flo_free(out)
+        return res
+
     def upload_path(self):
         """(path large host uploads take on this host, GB/s the probe measured for pageable-direct, for the pinned ring)"""
         name, a, b = C.create_string_buffer(64), C.c_double(), C.c_double()
@@ -550,6 +564,32 @@ class Batch:
             parts += p
             T.append(t)
         return self.mix(parts, T)
+
+    def convolve(self, irs, jobs=None, *, ir=0, mode="head", taps=None) -> "Batch":
+        """flo_batch_convolve: a new batch of this batch's mode, rate, channels, quality / level and bit depth whose clip k is
+        job k: a clip of this batch filtered by a clip of `irs` (a batch of this context and rate with 1 or self.channels
+        channels; it may be this batch), every clip in one launch (enqueued; sync() of any of the three batches orders it).
+        Output sample (t, c) is the FMA chain over taps k = 0 .. K - 1 of h[k, c] * x[t + skip - k, c], +0.0 outside the clip.
+        A job is a dict with clip and optionally ir (0), frames (the source clip's frames), skip (0), ir_start (0), taps (to
+        the response's end), or a _native.ConvJob. Without jobs every clip gets one job against response `ir` (an index, or a
+        list with one index per clip), at most `taps` taps, in `mode`: "head": skip 0, frames N (causal, the tail is cut);
+        "full": frames N + K - 1 (0 when either is empty); "centered": skip (K - 1) // 2, frames N (for linear-phase
+        filters). Both batches stay valid and unchanged"""
+        arr = _conv_jobs(jobs, [n // self.channels for n in self.n_interleaved], [n // irs.channels for n in irs.n_interleaved], ir, mode, taps)
+        h = C.c_void_p()
+        self.ctx._chk(self._L.flo_batch_convolve(self._h, irs._h, len(arr), arr, C.byref(h)))
+        return Batch(self.ctx, self._made[0], [int(g.frames) * self.channels for g in arr], self.sample_rate, self.channels, self._made[1], _handle=h)
+
+    def filter(self, kind, f_lo=None, f_hi=None, taps=255, beta=9.0) -> "Batch":
+        """every clip through the linear-phase FIR fir_design(kind, self.sample_rate, f_lo, f_hi, taps, beta), delay taken
+        off: the table as a one-clip mono batch of this context, then convolve(..., mode="centered")"""
+        table = fir_design(kind, self.sample_rate, f_lo, f_hi, taps, beta)
+        irs = Batch(self.ctx, MODE_LOSSLESS, [table.size], self.sample_rate, 1, 0)
+        try:
+            irs.upload(0, table)
+            return self.convolve(irs, mode="centered")
+        finally:
+            irs.close()   # (waits for the stream: the launch has read the response before it goes)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1595,6 +1635,95 @@ def concat(clips, sample_rate, channels, crossfade_ms=0.0) -> np.ndarray:
     """the interleaved f32 clips end to end, neighbours crossfaded over crossfade_ms (concat_parts), on the device"""
     parts, T = concat_parts([_f32(x).size // channels for x in clips], sample_rate, crossfade_ms)
     return mix(clips, sample_rate, channels, parts, T)
+
+
+def conv_geometry(channels, ir_channels=1) -> dict:
+    """flo_conv_geometry: tile_frames, tap_chunk and lane_outputs of the FIR kernel variant these channel counts select. Host
+    only: needs no device"""
+    info = _native.ConvInfo()
+    if _native.lib().flo_conv_geometry(channels, ir_channels, C.byref(info)) != 0:
+        raise FloError(f"unsupported channel counts {channels} with a response of {ir_channels}")
+    return dict(tile_frames=int(info.tile_frames), tap_chunk=int(info.tap_chunk), lane_outputs=int(info.lane_outputs))
+
+
+_FIR_KINDS = {"lowpass": _native.FIR_LOWPASS, "highpass": _native.FIR_HIGHPASS, "bandpass": _native.FIR_BANDPASS, "bandstop": _native.FIR_BANDSTOP}
+
+
+def fir_design(kind, rate, f_lo=None, f_hi=None, taps=255, beta=9.0) -> np.ndarray:
+    """flo_fir_design: the f32 table of a Kaiser-windowed sinc FIR of `taps` (odd) coefficients at `rate`. kind: "lowpass"
+    (below f_hi), "highpass" (above f_lo), "bandpass" (f_lo .. f_hi), "bandstop", or the FLO_FIR_* number. A low-pass given
+    only f_lo, or a high-pass given only f_hi, takes that as its one frequency. Host only: needs no device"""
+    k = _FIR_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+    if not isinstance(k, int):
+        raise FloError(f"unknown filter kind {kind!r}: one of {sorted(_FIR_KINDS)}")
+    if k == _native.FIR_LOWPASS and f_hi is None:
+        f_hi = f_lo
+    if k == _native.FIR_HIGHPASS and f_lo is None:
+        f_lo = f_hi
+    L = _native.lib()
+    tab, err = C.c_void_p(), C.create_string_buffer(256)
+    if L.flo_fir_design(k, int(rate), float(f_lo or 0.0), float(f_hi or 0.0), int(taps), float(beta), C.byref(tab), err, 256) != 0:
+        raise FloError("flo_fir_design: " + err.value.decode())
+    table = np.frombuffer(C.string_at(tab.value, int(taps) * 4), np.float32).copy()
+    L.flo_free(tab)
+    return table
+
+
+def conv_mode(mode, n, k):
+    """(skip, frames) of Batch.convolve's `mode` for a clip of n frames and a response of k taps"""
+    if mode == "head":
+        return 0, n
+    if mode == "full":
+        return 0, (n + k - 1 if n and k else 0)
+    if mode == "centered":
+        return (k - 1) // 2 if k else 0, n
+    raise FloError(f"unknown mode {mode!r}: one of 'head', 'full', 'centered'")
+
+
+def _conv_jobs(jobs, clip_frames, ir_frames, ir=0, mode="head", taps=None):
+    """the flo_conv_job array of a list of dicts / ConvJob, or (jobs None) of one job per clip against response `ir` in `mode`"""
+    cap = 0xFFFFFFFF if taps is None else int(taps)
+
+    def k_of(j, start, most):
+        p = int(ir_frames[j]) if 0 <= j < len(ir_frames) else 0
+        return min(most, p - min(start, p))
+
+    if jobs is None:
+        irs = [int(x) for x in ir] if isinstance(ir, (list, tuple)) else [int(ir)] * len(clip_frames)
+        if len(irs) != len(clip_frames):
+            raise FloError(f"ir has {len(irs)} entries, the batch {len(clip_frames)} clips")
+        conv_mode(mode, 0, 0)
+        jobs = [dict(clip=i, ir=j, taps=cap, **dict(zip(("skip", "frames"), conv_mode(mode, int(n), k_of(j, 0, cap)))))
+                for i, (n, j) in enumerate(zip(clip_frames, irs))]
+    jobs = list(jobs)
+    out = (_native.ConvJob * max(len(jobs), 1))()
+    for k, g in enumerate(jobs):
+        if isinstance(g, _native.ConvJob):
+            out[k] = g
+            continue
+        unknown = set(g) - {"clip", "ir", "frames", "skip", "ir_start", "taps", "reserved"}
+        if unknown:
+            raise FloError(f"job {k}: unknown keys {sorted(unknown)}")
+        if "clip" not in g:
+            raise FloError(f"job {k}: clip is required")
+        clip = int(g["clip"])
+        frames = g.get("frames")
+        if frames is None:
+            frames = int(clip_frames[clip]) if 0 <= clip < len(clip_frames) else 0
+        t = g.get("taps")
+        out[k] = _native.ConvJob(int(frames), int(g.get("skip", 0)), int(g.get("ir_start", 0)), clip, int(g.get("ir", 0)),
+                                 0xFFFFFFFF if t is None else int(t), int(g.get("reserved", 0)))
+    return (_native.ConvJob * len(jobs)).from_buffer(out) if jobs else (_native.ConvJob * 0)()
+
+
+def convolve(samples, ir, sample_rate, channels, ir_channels=1, job=None, *, mode="head", taps=None) -> np.ndarray:
+    """the interleaved f32 clip filtered by the response `ir` on the device (Context.convolve on the default context)"""
+    return default_context().convolve(samples, ir, sample_rate, channels, ir_channels, job, mode=mode, taps=taps)
+
+
+def fir_filter(samples, sample_rate, channels, kind, f_lo=None, f_hi=None, taps=255, beta=9.0) -> np.ndarray:
+    """the interleaved f32 clip through fir_design's linear-phase filter, delay taken off (convolve, mode "centered")"""
+    return convolve(samples, fir_design(kind, sample_rate, f_lo, f_hi, taps, beta), sample_rate, channels, 1, mode="centered")
 
 
 def _edit_matrix(in_channels, out_channels, matrix):

@@ -10,6 +10,8 @@ printed fields for the parts that sit on this repository's path -
                                [--pad-head S] [--pad-tail S]
     mix     <in1.wav> <in2.wav> ... --out <out.wav> [--gains g,g,...] [--at-ms a,a,...]
     concat  <in1.wav> <in2.wav> ... --out <out.wav> [--crossfade-ms MS]
+    filter  <in.wav> <out.wav> (--lowpass HZ | --highpass HZ | --bandpass LO,HI | --bandstop LO,HI) [--taps N] [--beta B]
+    convolve <in.wav> <ir.wav> <out.wav> [--tail]
     resample <in.wav> <out.wav> --rate HZ
     normalize <in.wav> <out.wav> --lufs N [--ceiling D] [--limit]
     curve   <in.wav> [--json]
@@ -53,6 +55,11 @@ milliseconds and padded with --pad-head / --pad-tail seconds of silence; --mono 
 (flo_mix): `mix` lays file i at --at-ms a_i milliseconds (default 0) times --gains g_i (default 1), the output ending with
 the file that ends last; `concat` plays the files end to end, neighbours overlapping in a linear crossfade of
 --crossfade-ms milliseconds (default 0: gapless). Files of another rate or channel count go through `resample` or `edit` first.
+`filter` and `convolve` (not in reflo) run a direct-form FIR over the audio on the device (flo_convolve): `filter` designs a
+linear-phase Kaiser-windowed sinc of --taps coefficients (odd, default 255) and --beta (default 9) and takes its delay off, so
+the output is as long as the input; `convolve` applies the response in ir.wav (mono, or with the input's channels: channel c
+by channel c), cut to the input's length or with --tail in full. A response at another rate goes through `resample` first, a
+stereo response on a mono input through `edit --mono` or `edit --channels`.
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
 """
@@ -202,6 +209,42 @@ def concat_wavs(wavs, crossfade_ms=0.0, ctx=None) -> bytes:
     clips, sr, ch = _same_format(wavs)
     parts, T = api.concat_parts([c.size // ch for c in clips], sr, crossfade_ms)
     return write_wav_bytes((ctx or api.default_context()).mix(clips, sr, ch, parts, T), sr, ch)
+
+
+def filter_options(lowpass=None, highpass=None, bandpass=None, bandstop=None):
+    """(kind, f_lo, f_hi) of the `filter` command: exactly one of the four; the band options are "LO,HI" or a pair"""
+    given = [(k, v) for k, v in (("lowpass", lowpass), ("highpass", highpass), ("bandpass", bandpass), ("bandstop", bandstop)) if v is not None]
+    if len(given) != 1:
+        raise ValueError("exactly one of --lowpass, --highpass, --bandpass and --bandstop is required")
+    kind, v = given[0]
+    if kind == "lowpass":
+        return kind, None, float(v)
+    if kind == "highpass":
+        return kind, float(v), None
+    pair = [float(x) for x in (v.split(",") if isinstance(v, str) else v)]
+    if len(pair) != 2:
+        raise ValueError(f"--{kind} takes two frequencies, LO,HI")
+    return kind, pair[0], pair[1]
+
+
+def filter_wav(wav, kind, f_lo=None, f_hi=None, taps=255, beta=9.0, ctx=None) -> bytes:
+    """the WAV file (bytes) through api.fir_design's filter, delay taken off, as the 32-bit float WAV `decode` writes"""
+    samples, sr, ch = read_wav_bytes(wav)
+    table = api.fir_design(kind, sr, f_lo, f_hi, taps, beta)
+    return write_wav_bytes((ctx or api.default_context()).convolve(samples, table, sr, ch, 1, mode="centered"), sr, ch)
+
+
+def convolve_wavs(wav, ir_wav, tail=False, ctx=None) -> bytes:
+    """the WAV file (bytes) filtered by the response in ir_wav (mono or of the same channels, at the same rate), cut to the
+    input's length or (tail) in full, as the 32-bit float WAV `decode` writes"""
+    samples, sr, ch = read_wav_bytes(wav)
+    ir, ir_sr, ir_ch = read_wav_bytes(ir_wav)
+    if ir_sr != sr:
+        raise ValueError(f"the response is {ir_sr} Hz, the input {sr} Hz: bring the response to {sr} Hz with `resample` first")
+    if ir_ch not in (1, ch):
+        raise ValueError(f"the response has {ir_ch} channels, the input {ch}: a response is mono or has the input's channels; "
+                         "bring either to the other's with `edit --mono` or `edit --channels` first")
+    return write_wav_bytes((ctx or api.default_context()).convolve(samples, ir, sr, ch, ir_ch, mode="full" if tail else "head"), sr, ch)
 
 
 def level_options(lufs, ceiling=-1.0, limit=False):
@@ -451,6 +494,21 @@ def main(argv=None) -> int:
     cc.add_argument("inputs", nargs="+")
     cc.add_argument("--out", required=True, help="Output WAV file")
     cc.add_argument("--crossfade-ms", type=float, default=0.0, help="Linear crossfade between neighbours in milliseconds (default 0)")
+    fl = sub.add_parser("filter", help="Low-, high-, band-pass or band-stop a WAV file with a linear-phase FIR on the device")
+    fl.add_argument("input")
+    fl.add_argument("output")
+    which = fl.add_mutually_exclusive_group(required=True)
+    which.add_argument("--lowpass", type=float, default=None, metavar="HZ", help="Keep what lies below HZ")
+    which.add_argument("--highpass", type=float, default=None, metavar="HZ", help="Keep what lies above HZ")
+    which.add_argument("--bandpass", default=None, metavar="LO,HI", help="Keep what lies between LO and HI Hz")
+    which.add_argument("--bandstop", default=None, metavar="LO,HI", help="Remove what lies between LO and HI Hz")
+    fl.add_argument("--taps", type=int, default=255, help="Filter length, odd (default 255)")
+    fl.add_argument("--beta", type=float, default=9.0, help="Kaiser window beta (default 9)")
+    cv = sub.add_parser("convolve", help="Convolve a WAV file with an impulse response on the device")
+    cv.add_argument("input")
+    cv.add_argument("ir")
+    cv.add_argument("output")
+    cv.add_argument("--tail", action="store_true", help="Keep the response's tail: the output is input + response - 1 frames long")
     rs = sub.add_parser("resample", help="Convert a WAV file to another sample rate on the device")
     rs.add_argument("input")
     rs.add_argument("output")
@@ -575,6 +633,23 @@ def main(argv=None) -> int:
             print(f"  Duration: {samples.size / ch / sr:.2f}s")
             print("Done!")
             print(f"  Output: {a.out}")
+        elif a.command in ("filter", "convolve"):
+            print(f"Reading {a.input}...")
+            audio = open(a.input, "rb").read()
+            samples, sr, ch = read_wav_bytes(audio)
+            print(f"  Sample rate: {sr} Hz")
+            print(f"  Channels: {ch}")
+            print(f"  Duration: {samples.size / ch / sr:.2f}s")
+            if a.command == "filter":
+                kind, f_lo, f_hi = filter_options(a.lowpass, a.highpass, a.bandpass, a.bandstop)
+                print(f"Filtering on the device ({kind}, {a.taps} taps)...")
+                wav = filter_wav(audio, kind, f_lo, f_hi, a.taps, a.beta)
+            else:
+                print(f"Convolving with {a.ir} on the device...")
+                wav = convolve_wavs(audio, open(a.ir, "rb").read(), a.tail)
+            open(a.output, "wb").write(wav)
+            print("Done!")
+            print(f"  Output: {a.output}")
         elif a.command == "resample":
             print(f"Reading {a.input}...")
             audio = open(a.input, "rb").read()

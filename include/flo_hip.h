@@ -609,6 +609,61 @@ int flo_batch_mix(flo_batch *const *srcs, size_t n_srcs, size_t n_out, const uin
 int flo_mix(flo_ctx *ctx, size_t n_clips, const float *const *pcm, const size_t *n_interleaved, uint32_t sample_rate,
             uint8_t channels, size_t n_parts, const flo_mix_part *parts, uint64_t out_frames, float **out, size_t *n_out);
 
+/* ---- FIR filtering and convolution: the clips of a resident batch filtered by clips of another, on the device ---------------
+ * (no counterpart in the reference; DESIGN 4.18 has the definition in full.)
+ * Sources: src is a resident batch of C channels (1 .. 8) at rate R; clip i has N_i whole sample-frames x_i[n, c], a trailing
+ * partial sample-frame is not part of it. irs is a resident batch of the same context and the same rate with Ch channels,
+ * Ch == 1 or Ch == C; clip j has P_j whole frames. irs == src is allowed.
+ * Output clip k is described by job k. With N and P the frames of source clip `clip` and of response clip `ir`:
+ *   K = min(taps, P - min(ir_start, P)) taps, so taps = UINT32_MAX means "to the end of the response clip";
+ *   h[k, c] is frame ir_start + k of response clip `ir`, channel (Ch == 1 ? 0 : c).
+ * Output clip k has T = frames frames of C channels. Sample (t, c): a = +0.0f; for k = 0 .. K - 1 in ascending order, with
+ * m = t + skip - k as a mathematical integer and xv = x[m, c] if 0 <= m < N, else +0.0f: a = fmaf(h[k, c], xv, a). The result
+ * is a. Every tap is applied, against +0.0 outside the clip; no tap is skipped. So:
+ *   K == 0 gives +0.0 everywhere;
+ *   h = [1] with skip = 0 reproduces the source, except that -0.0 becomes +0.0 (fmaf(1, -0, +0) = +0);
+ *   a NaN tap makes every sample of its channel NaN; an infinite tap makes NaN wherever it meets a zero (every frame outside
+ *   the clip is one: inf * 0 is NaN, and NaN stays) and an infinity elsewhere;
+ *   the result depends on the job alone: not on the batch around it, the tile, the tap chunk or the kernel variant.
+ * There is no gain and there are no fades: flo_batch_mix on the result does wet/dry.
+ * FLO_ERR_ARG with a message that names the quantity: a NULL batch; batches of different contexts; different rates (see
+ *   flo_batch_resample); channels of src outside 1 .. 8; Ch other than 1 or C; clip >= n_clips of src; ir >= n_clips of irs;
+ *   reserved != 0; K > FLO_CONV_MAX_TAPS; frames + skip wrapping 64 bits; frames * C beyond what flo_batch_create accepts; too
+ *   many tiles for one launch. FLO_ERR_STATE when a batch that some job names holds no PCM yet.
+ * flo_batch_convolve: a new batch of the mode, quality / level and bit depth of src, at its rate and C channels, made by one
+ *   launch (enqueued on the ctx stream; flo_batch_sync on any of the three batches orders it). The work list lives in pinned
+ *   and device memory that the new batch owns until it is destroyed. The sources stay valid and unchanged; n_out == 0 gives a
+ *   batch of no clips. The new batch behaves like an uploaded one.
+ * flo_convolve: one clip and one response from host memory and back (clip == ir == 0; upload, the same kernel, fetch): *out
+ *   (*n_out interleaved samples) malloc'ed, flo_free.
+ * flo_conv_geometry: host only, no context: the geometry of the kernel variant these two channel counts select. The tiles
+ *   of an output clip start at multiples of tile_frames; taps are staged tap_chunk at a time; one lane owns lane_outputs
+ *   consecutive output frames.
+ * flo_fir_design: host only, no context: a windowed-sinc FIR of taps = 2H + 1 coefficients (odd, 3 .. 65535) at `rate`,
+ *   *table malloc'ed (flo_free). All arithmetic is f64, the table is rounded to f32 once at the end. With
+ *   g[k] = (2f/R) sinc(2f (k - H)/R) I0(beta sqrt(1 - ((k - H)/H)^2)) / I0(beta) and lp(f)[k] = g[k] / sum(g):
+ *   LOWPASS = lp(f_hi); HIGHPASS = delta[k - H] - lp(f_lo); BANDPASS = lp(f_hi) - lp(f_lo); BANDSTOP = delta - BANDPASS.
+ *   beta is finite in 0 .. 16; the frequencies a kind uses are in Hz, 0 < f < rate / 2, f_lo < f_hi where both are used; the
+ *   one a kind does not use is ignored. FLO_ERR_ARG with a message in err otherwise. */
+#define FLO_CONV_MAX_TAPS 65536u
+#define FLO_FIR_LOWPASS 0u
+#define FLO_FIR_HIGHPASS 1u
+#define FLO_FIR_BANDPASS 2u
+#define FLO_FIR_BANDSTOP 3u
+typedef struct flo_conv_job {
+    uint64_t frames, skip, ir_start;   /* T; the delay taken off the front; the response's first frame */
+    uint32_t clip, ir, taps, reserved; /* clip of src; clip of irs; at most this many taps; must be 0 */
+} flo_conv_job;                        /* 40 bytes */
+typedef struct flo_conv_info {
+    uint32_t tile_frames, tap_chunk, lane_outputs;
+} flo_conv_info;
+int flo_batch_convolve(flo_batch *src, flo_batch *irs, size_t n_out, const flo_conv_job *jobs, flo_batch **out);
+int flo_convolve(flo_ctx *ctx, const float *pcm, size_t n_interleaved, const float *ir, size_t ir_interleaved,
+                 uint32_t sample_rate, uint8_t channels, uint8_t ir_channels, const flo_conv_job *job, float **out, size_t *n_out);
+int flo_conv_geometry(uint8_t channels, uint8_t ir_channels, flo_conv_info *info);
+int flo_fir_design(uint32_t kind, uint32_t rate, double f_lo, double f_hi, uint32_t taps, double beta, float **table, char *err,
+                   size_t err_cap);
+
 /* ---- spectral similarity: spectral_similarity (core/analysis.rs:395-437, exported as spectral_similarity_score,
  * lib.rs:1357) over fingerprint sets ----------------------------------------------------------------------------------
  * flo_fingerprint is SpectralFingerprint (analysis.rs:10-26): what flo_analyze / flo_batch_analyze_all return in those
