@@ -18,6 +18,7 @@ from .api import (active_range, active_range_many, edit, edit_many, edit_tile_fr
                   trim_silence_many)
 from .api import concat, concat_parts, mix  # noqa: F401
 from .api import conv_geometry, conv_mode, convolve, fir_design, fir_filter  # noqa: F401
+from .api import conv_fft_geometry  # noqa: F401
 from .api import (FINGERPRINT_DTYPE, FingerprintIndex, extract_dominant_frequencies, fingerprint_array,  # noqa: F401
                   fingerprints_from_files, spectral_similarity)
 from .api import FIDELITY_BLOCK_DTYPE, FIDELITY_DTYPE, compare, fidelity_dict  # noqa: F401

@@ -50,6 +50,7 @@ EXPORTS = [
     "flo_batch_edit", "flo_batch_active_range", "flo_edit", "flo_edit_tile_frames",
     "flo_batch_mix", "flo_mix",
     "flo_batch_convolve", "flo_convolve", "flo_conv_geometry", "flo_fir_design",
+    "flo_batch_convolve_fft", "flo_convolve_fft", "flo_conv_fft_geometry",
 ]
 
 
@@ -140,7 +141,12 @@ class ConvInfo(C.Structure):   # flo_conv_info
     _fields_ = [("tile_frames", C.c_uint32), ("tap_chunk", C.c_uint32), ("lane_outputs", C.c_uint32)]
 
 
+class ConvFftInfo(C.Structure):   # flo_conv_fft_info
+    _fields_ = [("block_frames", C.c_uint32), ("lane_blocks", C.c_uint32), ("max_taps", C.c_uint32), ("crossover_taps", C.c_uint32)]
+
+
 CONV_MAX_TAPS = 65536
+CONV_FFT_MAX_TAPS = 1048576
 FIR_LOWPASS, FIR_HIGHPASS, FIR_BANDPASS, FIR_BANDSTOP = 0, 1, 2, 3
 
 
@@ -326,6 +332,9 @@ def lib():
     L.flo_batch_convolve.argtypes = [vp, vp, sz, C.POINTER(ConvJob), C.POINTER(vp)]
     L.flo_convolve.argtypes = [vp, vp, sz, vp, sz, C.c_uint32, C.c_uint8, C.c_uint8, C.POINTER(ConvJob), C.POINTER(vp), C.POINTER(sz)]
     L.flo_conv_geometry.argtypes = [C.c_uint8, C.c_uint8, C.POINTER(ConvInfo)]
+    L.flo_batch_convolve_fft.argtypes = L.flo_batch_convolve.argtypes
+    L.flo_convolve_fft.argtypes = L.flo_convolve.argtypes
+    L.flo_conv_fft_geometry.argtypes = [C.c_uint8, C.c_uint8, C.POINTER(ConvFftInfo)]
     L.flo_fir_design.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.c_double, C.POINTER(vp), C.c_char_p, sz]
     _LIB = L
     return L

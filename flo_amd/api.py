@@ -210,16 +210,17 @@ class Context:
         self._L.flo_free(out)
         return res
 
-    def convolve(self, samples, ir, sample_rate, channels, ir_channels=1, job=None, *, mode="head", taps=None):
+    def convolve(self, samples, ir, sample_rate, channels, ir_channels=1, job=None, *, mode="head", taps=None, method="direct"):
         """flo_convolve: the interleaved f32 clip filtered by the interleaved f32 response `ir` of ir_channels (1 or channels)
         channels (one upload each, the batch kernel, one fetch). job: a dict as Batch.convolve takes (clip and ir are 0) or a
-        _native.ConvJob; None: the whole response in `mode` (Batch.convolve), at most `taps` taps"""
+        _native.ConvJob; None: the whole response in `mode` (Batch.convolve), at most `taps` taps. method: as Batch.convolve
+        ("fft", or "auto" from crossover_taps on: flo_convolve_fft)"""
         p, h = _f32(samples), _f32(ir)
         jobs = _conv_jobs(None if job is None else [job if isinstance(job, _native.ConvJob) else dict(job, clip=0, ir=0)],
                           [p.size // channels], [h.size // ir_channels], 0, mode, taps)
         out, n = C.c_void_p(), C.c_size_t()
-        self._chk(self._L.flo_convolve(self._h, p.ctypes.data, p.size, h.ctypes.data, h.size, sample_rate, channels, ir_channels, jobs,
-                                       C.byref(out), C.byref(n)))
+        fn = self._L.flo_convolve_fft if _conv_takes_fft(method, jobs, [h.size // ir_channels], channels, ir_channels) else self._L.flo_convolve
+        self._chk(fn(self._h, p.ctypes.data, p.size, h.ctypes.data, h.size, sample_rate, channels, ir_channels, jobs, C.byref(out), C.byref(n)))
         res = np.frombuffer(C.string_at(out.value, n.value * 4), np.float32).copy() if n.value else np.zeros(0, np.float32)
         self._L.flo_free(out)
         return res
@@ -565,7 +566,7 @@ class Batch:
             T.append(t)
         return self.mix(parts, T)
 
-    def convolve(self, irs, jobs=None, *, ir=0, mode="head", taps=None) -> "Batch":
+    def convolve(self, irs, jobs=None, *, ir=0, mode="head", taps=None, method="direct") -> "Batch":
         """flo_batch_convolve: a new batch of this batch's mode, rate, channels, quality / level and bit depth whose clip k is
         job k: a clip of this batch filtered by a clip of `irs` (a batch of this context and rate with 1 or self.channels
         channels; it may be this batch), every clip in one launch (enqueued; sync() of any of the three batches orders it).
@@ -574,10 +575,16 @@ class Batch:
         the response's end), or a _native.ConvJob. Without jobs every clip gets one job against response `ir` (an index, or a
         list with one index per clip), at most `taps` taps, in `mode`: "head": skip 0, frames N (causal, the tail is cut);
         "full": frames N + K - 1 (0 when either is empty); "centered": skip (K - 1) // 2, frames N (for linear-phase
-        filters). Both batches stay valid and unchanged"""
-        arr = _conv_jobs(jobs, [n // self.channels for n in self.n_interleaved], [n // irs.channels for n in irs.n_interleaved], ir, mode, taps)
+        filters). Both batches stay valid and unchanged.
+        method: "direct" (the default: that chain, to the bit); "fft": flo_batch_convolve_fft, the partitioned FFT path for
+        long responses, which approximates the chain in f32 and takes up to FLO_CONV_FFT_MAX_TAPS taps; "auto": the FFT path
+        when the largest K of the call is at least conv_fft_geometry()["crossover_taps"]. The FFT path is not merely
+        enqueued: its scratch goes back to the pool before the call returns, so the call returns when its launches have run"""
+        ir_frames = [n // irs.channels for n in irs.n_interleaved]
+        arr = _conv_jobs(jobs, [n // self.channels for n in self.n_interleaved], ir_frames, ir, mode, taps)
         h = C.c_void_p()
-        self.ctx._chk(self._L.flo_batch_convolve(self._h, irs._h, len(arr), arr, C.byref(h)))
+        fn = self._L.flo_batch_convolve_fft if _conv_takes_fft(method, arr, ir_frames, self.channels, irs.channels) else self._L.flo_batch_convolve
+        self.ctx._chk(fn(self._h, irs._h, len(arr), arr, C.byref(h)))
         return Batch(self.ctx, self._made[0], [int(g.frames) * self.channels for g in arr], self.sample_rate, self.channels, self._made[1], _handle=h)
 
     def filter(self, kind, f_lo=None, f_hi=None, taps=255, beta=9.0) -> "Batch":
@@ -1646,6 +1653,33 @@ def conv_geometry(channels, ir_channels=1) -> dict:
     return dict(tile_frames=int(info.tile_frames), tap_chunk=int(info.tap_chunk), lane_outputs=int(info.lane_outputs))
 
 
+def conv_fft_geometry(channels=2, ir_channels=1) -> dict:
+    """flo_conv_fft_geometry: block_frames, lane_blocks, max_taps and crossover_taps of the partitioned FFT convolution. Host
+    only: needs no device"""
+    info = _native.ConvFftInfo()
+    if _native.lib().flo_conv_fft_geometry(channels, ir_channels, C.byref(info)) != 0:
+        raise FloError(f"unsupported channel counts {channels} with a response of {ir_channels}")
+    return dict(block_frames=int(info.block_frames), lane_blocks=int(info.lane_blocks), max_taps=int(info.max_taps),
+                crossover_taps=int(info.crossover_taps))
+
+
+def _conv_takes_fft(method, jobs, ir_frames, channels=2, ir_channels=1):
+    """whether `method` sends this flo_conv_job array down the FFT path; "auto" goes by the call's largest K"""
+    if method == "direct":
+        return False
+    if method == "fft":
+        return True
+    if method != "auto":
+        raise FloError(f"unknown method {method!r}: one of 'direct', 'fft', 'auto'")
+    most = 0
+    for g in jobs:
+        p = int(ir_frames[g.ir]) if g.ir < len(ir_frames) else 0
+        most = max(most, min(int(g.taps), p - min(int(g.ir_start), p)))
+    # (channel counts the library refuses: the direct call carries the message)
+    info = _native.ConvFftInfo()
+    return _native.lib().flo_conv_fft_geometry(channels, ir_channels, C.byref(info)) == 0 and most >= info.crossover_taps
+
+
 _FIR_KINDS = {"lowpass": _native.FIR_LOWPASS, "highpass": _native.FIR_HIGHPASS, "bandpass": _native.FIR_BANDPASS, "bandstop": _native.FIR_BANDSTOP}
 
 
@@ -1716,9 +1750,9 @@ def _conv_jobs(jobs, clip_frames, ir_frames, ir=0, mode="head", taps=None):
     return (_native.ConvJob * len(jobs)).from_buffer(out) if jobs else (_native.ConvJob * 0)()
 
 
-def convolve(samples, ir, sample_rate, channels, ir_channels=1, job=None, *, mode="head", taps=None) -> np.ndarray:
+def convolve(samples, ir, sample_rate, channels, ir_channels=1, job=None, *, mode="head", taps=None, method="direct") -> np.ndarray:
     """the interleaved f32 clip filtered by the response `ir` on the device (Context.convolve on the default context)"""
-    return default_context().convolve(samples, ir, sample_rate, channels, ir_channels, job, mode=mode, taps=taps)
+    return default_context().convolve(samples, ir, sample_rate, channels, ir_channels, job, mode=mode, taps=taps, method=method)
 
 
 def fir_filter(samples, sample_rate, channels, kind, f_lo=None, f_hi=None, taps=255, beta=9.0) -> np.ndarray:

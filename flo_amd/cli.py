@@ -11,7 +11,7 @@ printed fields for the parts that sit on this repository's path -
     mix     <in1.wav> <in2.wav> ... --out <out.wav> [--gains g,g,...] [--at-ms a,a,...]
     concat  <in1.wav> <in2.wav> ... --out <out.wav> [--crossfade-ms MS]
     filter  <in.wav> <out.wav> (--lowpass HZ | --highpass HZ | --bandpass LO,HI | --bandstop LO,HI) [--taps N] [--beta B]
-    convolve <in.wav> <ir.wav> <out.wav> [--tail]
+    convolve <in.wav> <ir.wav> <out.wav> [--tail] [--method direct|fft|auto]
     resample <in.wav> <out.wav> --rate HZ
     normalize <in.wav> <out.wav> --lufs N [--ceiling D] [--limit]
     curve   <in.wav> [--json]
@@ -58,7 +58,9 @@ the file that ends last; `concat` plays the files end to end, neighbours overlap
 `filter` and `convolve` (not in reflo) run a direct-form FIR over the audio on the device (flo_convolve): `filter` designs a
 linear-phase Kaiser-windowed sinc of --taps coefficients (odd, default 255) and --beta (default 9) and takes its delay off, so
 the output is as long as the input; `convolve` applies the response in ir.wav (mono, or with the input's channels: channel c
-by channel c), cut to the input's length or with --tail in full. A response at another rate goes through `resample` first, a
+by channel c), cut to the input's length or with --tail in full; --method fft takes the partitioned FFT path for long
+responses (flo_convolve_fft: up to 1048576 taps, an f32 approximation of the direct chain), auto takes it from the measured
+crossover on, direct (the default) never. A response at another rate goes through `resample` first, a
 stereo response on a mono input through `edit --mono` or `edit --channels`.
 The quality names map as in the reference CLI (main.rs:236-242): low 0.2, medium 0.4, high 0.6, veryhigh 0.8,
 transparent 1.0 - NOT the QualityPreset values the library API uses (lossy/mod.rs:39-47).
@@ -234,7 +236,7 @@ def filter_wav(wav, kind, f_lo=None, f_hi=None, taps=255, beta=9.0, ctx=None) ->
     return write_wav_bytes((ctx or api.default_context()).convolve(samples, table, sr, ch, 1, mode="centered"), sr, ch)
 
 
-def convolve_wavs(wav, ir_wav, tail=False, ctx=None) -> bytes:
+def convolve_wavs(wav, ir_wav, tail=False, ctx=None, method="direct") -> bytes:
     """the WAV file (bytes) filtered by the response in ir_wav (mono or of the same channels, at the same rate), cut to the
     input's length or (tail) in full, as the 32-bit float WAV `decode` writes"""
     samples, sr, ch = read_wav_bytes(wav)
@@ -244,7 +246,7 @@ def convolve_wavs(wav, ir_wav, tail=False, ctx=None) -> bytes:
     if ir_ch not in (1, ch):
         raise ValueError(f"the response has {ir_ch} channels, the input {ch}: a response is mono or has the input's channels; "
                          "bring either to the other's with `edit --mono` or `edit --channels` first")
-    return write_wav_bytes((ctx or api.default_context()).convolve(samples, ir, sr, ch, ir_ch, mode="full" if tail else "head"), sr, ch)
+    return write_wav_bytes((ctx or api.default_context()).convolve(samples, ir, sr, ch, ir_ch, mode="full" if tail else "head", method=method), sr, ch)
 
 
 def level_options(lufs, ceiling=-1.0, limit=False):
@@ -509,6 +511,8 @@ def main(argv=None) -> int:
     cv.add_argument("ir")
     cv.add_argument("output")
     cv.add_argument("--tail", action="store_true", help="Keep the response's tail: the output is input + response - 1 frames long")
+    cv.add_argument("--method", choices=("direct", "fft", "auto"), default="direct",
+                    help="direct: the FIR chain (default); fft: partitioned FFT convolution for long responses; auto: by the measured crossover")
     rs = sub.add_parser("resample", help="Convert a WAV file to another sample rate on the device")
     rs.add_argument("input")
     rs.add_argument("output")
@@ -646,7 +650,7 @@ def main(argv=None) -> int:
                 wav = filter_wav(audio, kind, f_lo, f_hi, a.taps, a.beta)
             else:
                 print(f"Convolving with {a.ir} on the device...")
-                wav = convolve_wavs(audio, open(a.ir, "rb").read(), a.tail)
+                wav = convolve_wavs(audio, open(a.ir, "rb").read(), a.tail, method=a.method)
             open(a.output, "wb").write(wav)
             print("Done!")
             print(f"  Output: {a.output}")

@@ -111,6 +111,13 @@ int work_block_get(flo_ctx *c, size_t bytes, const char *what, void *&pin, void 
 int batch_one_shot(flo_ctx *c, const char *who, const float *pcm, size_t n_il, uint32_t sr, uint8_t ch,
                    const std::function<int(flo_batch *, flo_batch **)> &op, float **out, size_t *n_out);
 
+// One host clip and one host response through a convolution of batches and back (flo_convolve, flo_convolve_fft;
+// convolve.cpp): both are uploaded, op makes the batch, clip 0 comes back malloc'd. Messages of `batch_who` read `who`.
+typedef int (*ConvBatchOp)(flo_batch *, flo_batch *, size_t, const flo_conv_job *, flo_batch **);
+int conv_one_clip(flo_ctx *c, const std::string &who, const std::string &batch_who, ConvBatchOp op, const float *pcm, size_t n_interleaved,
+                  const float *ir, size_t ir_interleaved, uint32_t sample_rate, uint8_t channels, uint8_t ir_channels, const flo_conv_job *job,
+                  float **out, size_t *n_out);
+
 // The frame and clip tables of a synced lossy batch's decode, read from the encoder's own records: clip i's PCM at
 // co[i] floats, `total` floats in all (decode.cpp: flo_batch_decode, and the fidelity reports' fused pass)
 int batch_lossy_tables(flo_batch *b, std::vector<unsigned long long> &blob_off, std::vector<unsigned int> &blob_len,

@@ -6,7 +6,7 @@
 namespace flo {
 
 bool conv_check(const ConvSource &src, const ConvSource &irs, size_t n_out, const flo_conv_job *jobs, std::vector<uint32_t> &K,
-                std::vector<uint32_t> &pre, std::string &err) {
+                std::vector<uint32_t> &pre, std::string &err, const ConvLimits &lim) {
     auto bad = [&](const std::string &m) {
         err = m;
         return false;
@@ -31,13 +31,13 @@ bool conv_check(const ConvSource &src, const ConvSource &irs, size_t n_out, cons
         if (j.ir >= irs.n_clips) return bad("ir " + std::to_string(j.ir) + of + " is not below n_clips " + std::to_string(irs.n_clips) + " of irs");
         if (j.reserved != 0) return bad("reserved" + of + " is not 0");
         K[k] = conv_taps(j.taps, irs.clip_frames[j.ir], j.ir_start);
-        if (K[k] > FLO_CONV_MAX_TAPS)
-            return bad("taps" + of + ": " + std::to_string(K[k]) + " taps are above FLO_CONV_MAX_TAPS " + std::to_string(FLO_CONV_MAX_TAPS));
+        if (K[k] > lim.max_taps)
+            return bad("taps" + of + ": " + std::to_string(K[k]) + " taps are above " + lim.max_taps_name + " " + std::to_string(lim.max_taps));
         if (j.frames + j.skip < j.frames) return bad("frames + skip" + of + " wraps 64 bits");
         if (j.frames > most) return bad("frames " + std::to_string(j.frames) + of + " times channels overflows");
         T[k] = j.frames;
     }
-    if (!clip_tiles(T.data(), n_out, kConvTileFrames, pre)) return bad("too many tiles for one launch");
+    if (!clip_tiles(T.data(), n_out, lim.tile_frames, pre)) return bad("too many tiles for one launch");
     return true;
 }
 

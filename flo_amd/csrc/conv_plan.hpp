@@ -70,10 +70,17 @@ struct ConvSource {
     size_t n_clips = 0;
     const uint64_t *clip_frames = nullptr;   // [n_clips] whole frames
 };
-// The checks of flo_batch_convolve: K[k] of every job and pre, the tile prefix of clip_tiles(frames, n_out, kConvTileFrames);
+// What differs between the callers of conv_check: the direct path's limits are the default; the partitioned FFT path
+// (fftconv_plan.cpp) has a limit and a tile of its own.
+struct ConvLimits {
+    uint32_t max_taps = FLO_CONV_MAX_TAPS;
+    const char *max_taps_name = "FLO_CONV_MAX_TAPS";
+    uint64_t tile_frames = kConvTileFrames;
+};
+// The checks of flo_batch_convolve: K[k] of every job and pre, the tile prefix of clip_tiles(frames, n_out, lim.tile_frames);
 // or false with a message that names the quantity.
 bool conv_check(const ConvSource &src, const ConvSource &irs, size_t n_out, const flo_conv_job *jobs, std::vector<uint32_t> &K,
-                std::vector<uint32_t> &pre, std::string &err);
+                std::vector<uint32_t> &pre, std::string &err, const ConvLimits &lim = ConvLimits());
 
 // flo_fir_design without the C wrapping (fir_design.cpp): the table in f64, or false with a message
 bool fir_design(uint32_t kind, uint32_t rate, double f_lo, double f_hi, uint32_t taps, double beta, std::vector<double> &h, std::string &err);

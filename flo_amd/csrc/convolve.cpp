@@ -84,17 +84,18 @@ extern "C" int flo_batch_convolve(flo_batch *src, flo_batch *irs, size_t n_out, 
     return FLO_OK;
 }
 
-extern "C" int flo_convolve(flo_ctx *c, const float *pcm, size_t n_interleaved, const float *ir, size_t ir_interleaved, uint32_t sample_rate,
-                            uint8_t channels, uint8_t ir_channels, const flo_conv_job *job, float **out, size_t *n_out) {
+int conv_one_clip(flo_ctx *c, const std::string &who, const std::string &batch_who, ConvBatchOp op, const float *pcm, size_t n_interleaved,
+                  const float *ir, size_t ir_interleaved, uint32_t sample_rate, uint8_t channels, uint8_t ir_channels, const flo_conv_job *job,
+                  float **out, size_t *n_out) {
     if (!c || !out || !n_out || (n_interleaved && !pcm) || (ir_interleaved && !ir)) return FLO_ERR_ARG;
     *out = nullptr;
     *n_out = 0;
-    if (channels < 1) return fail(c, FLO_ERR_ARG, "flo_convolve: channels must be at least 1");
-    if (ir_channels < 1) return fail(c, FLO_ERR_ARG, "flo_convolve: ir_channels must be at least 1");
-    if (!sample_rate) return fail(c, FLO_ERR_ARG, "flo_convolve: sample_rate must be non-zero");
-    if (!job) return fail(c, FLO_ERR_ARG, "flo_convolve: job is NULL");
-    if (job->clip != 0) return fail(c, FLO_ERR_ARG, "flo_convolve: clip " + std::to_string(job->clip) + " is not 0: there is one clip");
-    if (job->ir != 0) return fail(c, FLO_ERR_ARG, "flo_convolve: ir " + std::to_string(job->ir) + " is not 0: there is one response");
+    if (channels < 1) return fail(c, FLO_ERR_ARG, who + ": channels must be at least 1");
+    if (ir_channels < 1) return fail(c, FLO_ERR_ARG, who + ": ir_channels must be at least 1");
+    if (!sample_rate) return fail(c, FLO_ERR_ARG, who + ": sample_rate must be non-zero");
+    if (!job) return fail(c, FLO_ERR_ARG, who + ": job is NULL");
+    if (job->clip != 0) return fail(c, FLO_ERR_ARG, who + ": clip " + std::to_string(job->clip) + " is not 0: there is one clip");
+    if (job->ir != 0) return fail(c, FLO_ERR_ARG, who + ": ir " + std::to_string(job->ir) + " is not 0: there is one response");
     const size_t len = n_interleaved / channels * channels, ir_len = ir_interleaved / ir_channels * ir_channels;
     std::unique_ptr<float, decltype(&free)> res(nullptr, free);   // (freed behind the batches, whose destruction waits for the stream)
     BatchHold a, h, b;                                            // (b goes first)
@@ -106,10 +107,10 @@ extern "C" int flo_convolve(flo_ctx *c, const float *pcm, size_t n_interleaved, 
     if (rc != FLO_OK) return rc;
     rc = batch_upload_all(h.b, &ir);
     if (rc != FLO_OK) return rc;
-    rc = flo_batch_convolve(a.b, h.b, 1, job, &b.b);
+    rc = op(a.b, h.b, 1, job, &b.b);
     if (rc != FLO_OK) {
-        const std::string msg = c->err, from = "flo_batch_convolve: ";   // "flo_batch_convolve: ..." reads "flo_convolve: ..." here
-        if (msg.compare(0, from.size(), from) == 0) fail(c, rc, "flo_convolve: " + msg.substr(from.size()));
+        const std::string msg = c->err, from = batch_who + ": ";   // "flo_batch_convolve: ..." reads "flo_convolve: ..." here
+        if (msg.compare(0, from.size(), from) == 0) fail(c, rc, who + ": " + msg.substr(from.size()));
         return rc;
     }
     const size_t floats = b.b->n_il[0];
@@ -118,9 +119,15 @@ extern "C" int flo_convolve(flo_ctx *c, const float *pcm, size_t n_interleaved, 
     if (floats) {
         hipError_t e = hipMemcpyAsync(res.get(), b.b->d_pcm + b.b->clip_off[0], floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return fail(c, FLO_ERR_DEVICE, std::string("flo_convolve: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(c, FLO_ERR_DEVICE, who + ": " + hipGetErrorString(e));
     }
     *out = res.release();
     *n_out = floats;
     return FLO_OK;
+}
+
+extern "C" int flo_convolve(flo_ctx *c, const float *pcm, size_t n_interleaved, const float *ir, size_t ir_interleaved, uint32_t sample_rate,
+                            uint8_t channels, uint8_t ir_channels, const flo_conv_job *job, float **out, size_t *n_out) {
+    return conv_one_clip(c, "flo_convolve", "flo_batch_convolve", flo_batch_convolve, pcm, n_interleaved, ir, ir_interleaved, sample_rate, channels,
+                         ir_channels, job, out, n_out);
 }

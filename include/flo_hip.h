@@ -664,6 +664,38 @@ int flo_conv_geometry(uint8_t channels, uint8_t ir_channels, flo_conv_info *info
 int flo_fir_design(uint32_t kind, uint32_t rate, double f_lo, double f_hi, uint32_t taps, double beta, float **table, char *err,
                    size_t err_cap);
 
+/* ---- partitioned FFT convolution: the same jobs for long responses, on the device ------------------------------------------
+ * (no counterpart in the reference; DESIGN 4.19 has the definition in full.)
+ * A second way to run a list of flo_conv_job: sources, jobs, K, h[k, c], Ch, irs == src and the skip clamp min(skip, N + K)
+ * mean what they mean above. The result approximates the chain above in f32; it does not reproduce it to the bit.
+ * Uniformly partitioned overlap-save with B = block_frames, F = 2B, Pn = ceil(K / B):
+ *   partition p is taps [pB, min((p + 1)B, K)) of channel c, zero-padded to F, real-FFT'd to H_p;
+ *   segment q of a job (q may be negative) is source frames [(q - 1)B + skip, (q + 1)B + skip), +0.0 outside [0, N),
+ *     real-FFT'd to X_q; a segment wholly outside the clip is zero and takes no part;
+ *   output block b is frames [bB, (b + 1)B) of the output, ragged at T: Y_b = sum over p = 0 .. Pn - 1 of X_{b-p} * H_p,
+ *     accumulated from zero in ascending p; the last B values of irfft(Y_b) are the block.
+ *   There are no atomics: a job's output depends on the job alone, not on the batch, the job's place in the list, the
+ *   grouping of the scratch (FLO_CONV_FFT_GROUP_BYTES, read per call, default 1 GiB) or what the scratch held before.
+ *   A NaN or infinite sample or tap leaves every block it reaches (q in [b - Pn + 1, b]; any partition) unspecified and no
+ *   other; no call refuses them. Blocks whose every segment or partition is zero compare equal to zero; K == 0 gives zeros.
+ * FLO_ERR_ARG and FLO_ERR_STATE as for flo_batch_convolve, in the same order, with K > FLO_CONV_FFT_MAX_TAPS in the place of
+ *   K > FLO_CONV_MAX_TAPS. A failed call leaves no batch and a usable context.
+ * flo_batch_convolve_fft: a new batch like flo_batch_convolve's. Responses are transformed once per distinct
+ *   (ir, ir_start, K) of the call; segment spectra live in pool scratch that goes back before the call returns, so the call
+ *   returns when its launches have run.
+ * flo_convolve_fft: flo_convolve over this path.
+ * flo_conv_fft_geometry: host only, no context: block_frames (B); lane_blocks, the output blocks a lane accumulates side by
+ *   side (a tile is lane_blocks * B output frames); max_taps; crossover_taps, the smallest measured K from which this path
+ *   is no slower than the direct one (what method "auto" of the Python package goes by). */
+#define FLO_CONV_FFT_MAX_TAPS 1048576u
+typedef struct flo_conv_fft_info {
+    uint32_t block_frames, lane_blocks, max_taps, crossover_taps;
+} flo_conv_fft_info;                   /* 16 bytes */
+int flo_batch_convolve_fft(flo_batch *src, flo_batch *irs, size_t n_out, const flo_conv_job *jobs, flo_batch **out);
+int flo_convolve_fft(flo_ctx *ctx, const float *pcm, size_t n_interleaved, const float *ir, size_t ir_interleaved,
+                     uint32_t sample_rate, uint8_t channels, uint8_t ir_channels, const flo_conv_job *job, float **out, size_t *n_out);
+int flo_conv_fft_geometry(uint8_t channels, uint8_t ir_channels, flo_conv_fft_info *info);
+
 /* ---- spectral similarity: spectral_similarity (core/analysis.rs:395-437, exported as spectral_similarity_score,
  * lib.rs:1357) over fingerprint sets ----------------------------------------------------------------------------------
  * flo_fingerprint is SpectralFingerprint (analysis.rs:10-26): what flo_analyze / flo_batch_analyze_all return in those
